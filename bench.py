@@ -19,9 +19,17 @@ Workload (configs[1] of BASELINE.json; synthetic because standard-224 is an S3 d
   * a step = one pass of scan -> probe -> classify over the whole read batch (slk_classify_batch_device).
 Multi-GPU: table replicated, reads sharded (each rank its own batch), no data-path collective => "weak" scaling.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused lane kernel, bound by its table probes);
-`cpu_baseline` times the CPU restatement under oracle/ (OpenMP, all host cores) on a bounded sample -- a reported
-baseline, not the target.
+Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the fused lane kernel, bound by its table probes).
+A plain run does only what that line needs: set up, warm up, time the K steps, print.  --full adds the measurements that take
+runs of their own after the timed region: `cpu_baseline` (the CPU restatement under oracle/, OpenMP, all host cores, on a
+bounded sample -- a reported baseline, not the target) and the part's random-request rate that the roofline is held against
+(without --full the roofline quotes the constant GATHER_CEILING_GLPS and says so).
+
+--dump-outputs DIR: after the timed steps, the arrays the last step handed its caller (taxon, classified, num_distinct,
+total_kmers, num_hits and, on the replicated path, num_probes) go to DIR/<name>.npy as float64, for a fixed seeded sample of at
+most DUMP_SAMPLE_READS reads of the batch (their indices in DIR/read_index.npy); in an N-rank run every rank writes its
+share of the sample, rank r > 0 as DIR/rank<r>_<name>.npy.  The inputs depend only on the arguments, so two builds can be
+compared output for output.
 
 --table-sharded (BASELINE.json configs[3]): the library is larger than one GPU's HBM, so rank g holds only the records whose key
 falls to it (fmix64(key) mod N; slk_index_set_shard) -- by default 5.0e9 records per rank, 4.0e10 at N = 8 (> 288 GB of table) --
@@ -56,6 +64,8 @@ K, M, SPACES = 35, 31, 7
 READ_LEN = 150
 TAX_EXTENT = 3080008  # README.md:374 of the reference (NCBI taxonomy array extent)
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", os.environ.get("SLK_TRAFFIC_FILE", "r04_traffic.json"))
+DUMP_SAMPLE_READS = 1 << 19   # --dump-outputs, over all ranks: at most 7 arrays x 2^19 reads x 8 bytes = 29 MB
+DUMP_SEED = 4242
 
 
 def log(*a):
@@ -150,6 +160,27 @@ def kernel_source_hash():
         h.update(name.encode())
         h.update(open(os.path.join(d, name), "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(out_dir, arrays, n_reads, rank, world):
+    """--dump-outputs: {name: device tensor whose first n_reads entries are per read} -> out_dir/<name>.npy (float64) for a fixed
+    seeded sample of the reads, the same for every run with the same arguments."""
+    import torch
+    per_rank = max(1, DUMP_SAMPLE_READS // world)
+    if n_reads <= per_rank:
+        idx = np.arange(n_reads, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n_reads, per_rank, replace=False)).astype(np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if rank else ""
+    np.save(os.path.join(out_dir, prefix + "read_index.npy"), idx.astype(np.float64))
+    nbytes = idx.size * 8
+    d_idx = torch.from_numpy(idx).to(next(iter(arrays.values())).device)
+    for name, t in arrays.items():
+        a = t[:n_reads].index_select(0, d_idx).cpu().numpy().astype(np.float64)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+        nbytes += a.nbytes
+    log(f"rank {rank}: outputs of the last timed step, {idx.size} of {n_reads} reads, {nbytes / 1e6:.1f} MB -> {out_dir}")
 
 
 def free_port():
@@ -435,6 +466,9 @@ def table_sharded(args, rank, world, local_rank):
     outs = sc.classify_many([batch] * args.steps, thresholds=(0.0,), min_hit_groups=2, profile=True)   # K steps = K batches in the pipeline
     barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: outs[-1][k] for k in ("taxon", "classified", "num_distinct", "total_kmers", "num_hits")},
+                     n_reads, rank, world)
     progress("table-sharded: jobs alone")
     step_ms = list(getattr(sc, "step_ms", []))
     alone = sc.jobs_alone(batch) if world == 1 and not args.collectives_at_one_rank else None   # (after the timed region)
@@ -521,8 +555,13 @@ def main():
     ap.add_argument("--genomes", type=int, default=8192)
     ap.add_argument("--genome-len", type=int, default=1 << 20)
     ap.add_argument("--load-factor", type=float, default=0.0, help="cells-used fraction of the table (0: the engine's default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ceiling", action="store_true", help="do not measure the random-request rate after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: the CPU baseline and the random-request rate after the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-read outputs (a fixed seeded sample) to DIR/<name>.npy as float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-ceiling", action="store_true",
+                    help="do not measure the random-request rate after the timed region (--full, --table-sharded)")
     ap.add_argument("--table-sharded", action="store_true",
                     help="BASELINE configs[3]: every rank holds 1/N of the table, minimizers and taxa cross the links (RCCL all-to-all)")
     ap.add_argument("--records-per-rank", type=float, default=5.0e9, help="--table-sharded: records of one rank's shard")
@@ -537,6 +576,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.dry_run:
+        raise SystemExit("--dump-outputs: a dry run computes no outputs")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))  # (no GPU call has been made in this process)
     from slacken_amd import dist as sdist
@@ -652,6 +695,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t_start
     st.synchronize()   # (the engine's own check of the queued calls: raises if a device-side error was flagged)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"taxon": d_taxon, "classified": d_cls, "num_distinct": d_nd, "total_kmers": d_tk,
+                                         "num_hits": d_nh, "num_probes": d_np}, n_reads, rank, world)
     step_dev_ms = np.array([a.elapsed_time(b) for a, b in ev]) if args.steps else np.zeros(1)
     stage_ms = np.array(st.last_stage_ms())  # the engine's own events of the LAST timed step: [fused, 0, ~0] on the hot path
     elapsed = sdist.max_over_ranks(elapsed, dist, None if args.rehearse_on_one_gpu else device)
@@ -684,14 +730,15 @@ def main():
         else:
             traffic_note = f"profiles/{os.path.basename(TRAFFIC_FILE)} is for other kernel sources or another workload: not quoted"
 
-    # ---- after the timed region: the CPU baseline, then the part's random-request rate on THIS box (the index is closed for it)
+    # ---- after the timed region, with --full: the CPU baseline, then the part's random-request rate on THIS box (the index is
+    # closed for it)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("cpu baseline")
         cpu = cpu_baseline(torch, slacken_amd, args, parents, genome_cat, genome_taxa, G, device)
     deferred = st.last_deferred()
     ceiling, ceiling_src, ceil_meas = GATHER_CEILING_GLPS, "constant of round 2 (FALLBACK: not measured in this run)", None
-    if rank == 0 and not args.no_ceiling:
+    if args.full and rank == 0 and not args.no_ceiling:
         progress("request-rate ceiling")
         table_bytes = int(info.table_bytes)
         del d_bases, d_offsets, genome_cat

@@ -491,3 +491,26 @@ def test_bench_two_ranks_rehearsal():
     assert line["config"]["reads_per_gpu_per_step"] == 1_000_000
     assert abs(line["value"] - 2 * 1.0 / (line["ms_per_step"] * 1e-3)) < 0.01 * line["value"]     # whole-job reads / max-rank time
     assert line["roofline"]["frac"] > 0.0     # (two processes time-share the GPU here: the event timings mean nothing)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`python bench.py --dump-outputs DIR`: a plain run (no CPU baseline, no request-rate run) writes the per-read arrays of its
+    last timed step for a fixed sample of the reads, as float64 and within 64 MB; a second run with the same arguments writes the
+    same arrays."""
+    args = ("--steps", "2", "--warmup", "1", "--records", "2e8", "--reads", "1e6", "--genomes", "64", "--genome-len", "262144")
+    names = ("read_index", "taxon", "classified", "num_distinct", "total_kmers", "num_hits", "num_probes")
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        line = _run_bench(*args, "--dump-outputs", str(d))
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+        assert "not measured in this run" in line["roofline"]["random_line_ceiling_source"]
+        dumps.append({n: np.load(d / f"{n}.npy") for n in names})
+    a, b = dumps
+    idx = a["read_index"].astype(np.int64)
+    assert len(idx) == 1 << 19 and np.all(np.diff(idx) > 0) and idx[-1] < 1_000_000
+    assert sum(x.nbytes for x in a.values()) <= 64e6
+    for n in names:
+        assert a[n].dtype == np.float64 and a[n].shape == idx.shape and np.array_equal(a[n], b[n]), n
+    assert a["classified"].mean() > 0.5 and np.all(a["taxon"][a["classified"] == 1] > 0)
+    assert np.all(a["total_kmers"] <= 150 - 35 + 1)

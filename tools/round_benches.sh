@@ -4,7 +4,7 @@
 # taxonomy, the CLI end to end.  Copy what should be judged into profiles/.
 D=${1:-gpurun_out/round}
 mkdir -p $D
-python3 bench.py > $D/bench_default.json 2> $D/bench_default.err || exit 1
+timeout -k 10 600 python3 bench.py --full > $D/bench_default.json 2> $D/bench_default.err || exit 1
 timeout -k 10 500 python3 tools/bench_extras.py > $D/extras.json 2> $D/extras.err || exit 1
 timeout -k 10 300 python3 tools/bench_long.py > $D/long.json 2> $D/long.err || exit 1
 timeout -k 10 300 python3 tools/bench_long_mixed.py > $D/long_mixed.json 2> $D/long_mixed.err || exit 1
