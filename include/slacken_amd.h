@@ -409,6 +409,26 @@ int32_t slk_stream_last_stage_ms(slk_stream *st, float out_ms[3]);
  * (longer than 1000 bases, or more than 12 distinct taxa); 0 if that call did not take the lane kernel.  Synchronises st. */
 int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count);
 
+/* ---- Bracken weights: replaces BrackenWeights.buildWeights (S/slacken/BrackenWeights.scala:294-352) -- every read of length
+ * read_len at every position of every record (readClassifications :251-268) classified against the index (classify :276-285:
+ * resolveTree with confidence 0 and minHitGroups 2) and counted by (dest, source) (groupBy, :350).
+ *   slk_bracken_create   read_len >= k (else SLK_E_INVALID; the reference leaves it undefined); max_fragment: the pieces records
+ *                        are cut into (splitToMaxLength, :152-164), 0 = FRAGMENT_MAX = 1 MiB (:303); one id column only
+ *                        (SLK_E_UNSUPPORTED otherwise, as the staged device entries)
+ *   slk_bracken_add      R whole records (any length, any host memory; bases WITHOUT whitespace, as after regexp_replace :311)
+ *                        with the taxon each came from (TaxonFragment.taxon).  Synchronous on st.  The counts do not depend on how
+ *                        the records are split into calls or on their order.
+ *   slk_bracken_result   the triples so far, dest ascending then source ascending; *n = their number; cap 0 queries only
+ *                        that, 0 < cap < *n gives SLK_E_CAPACITY
+ * The ordinal the reference gives a segment's trailing hit lacks the segment's position (:230); this engine reproduces what
+ * that does to the reads near a piece start. */
+typedef struct slk_bracken slk_bracken;
+int32_t slk_bracken_create(slk_index *ix, int32_t read_len, uint64_t max_fragment, slk_bracken **out);
+int32_t slk_bracken_add(slk_bracken *b, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const int32_t *source_taxa,
+                        uint64_t R);
+int32_t slk_bracken_result(slk_bracken *b, uint64_t *n, int32_t *dest, int32_t *source, uint64_t *count, uint64_t cap);
+void slk_bracken_destroy(slk_bracken *b);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,7 +79,7 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
            "slk_shard_of", "slk_stream_set_merged_hits", "slk_classify_hits_device", "slk_shard_batch_rows", "slk_shard_chunk", "slk_shard_step_device",
            "slk_stream_last_deferred", "slk_table_slot", "slk_table_hash_of",
-           "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy"]
+           "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy"]
 
 
 def lib_path():
@@ -159,6 +159,11 @@ def lib():
     L.slk_shard_chunk.restype = C.c_uint32
     L.slk_shard_step_device.argtypes = [vp, vp, C.POINTER(ShardLists), C.POINTER(ShardLookup), C.POINTER(ShardLists), C.POINTER(ShardResults)]
     L.slk_stream_last_deferred.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.slk_bracken_create.argtypes = [vp, C.c_int32, C.c_uint64, C.POINTER(vp)]
+    L.slk_bracken_add.argtypes = [vp, vp, u8p, u64p, i32p, C.c_uint64]
+    L.slk_bracken_result.argtypes = [vp, C.POINTER(C.c_uint64), i32p, i32p, u64p, C.c_uint64]
+    L.slk_bracken_destroy.argtypes = [vp]
+    L.slk_bracken_destroy.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -298,6 +303,43 @@ class Index:
     def close(self):
         if getattr(self, "h", None):
             lib().slk_index_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BrackenWeights:
+    """Bracken weights against an index (slk_bracken_*: BrackenWeights.buildWeights, S/slacken/BrackenWeights.scala:294-352).
+    add() takes whole records (no whitespace) with the taxon each came from; result() gives (dest, source, count) as numpy
+    arrays, dest ascending then source ascending."""
+
+    def __init__(self, index, read_len, max_fragment=0, stream=None):
+        self.index = index
+        self.stream = stream if stream is not None else index.stream()
+        h = C.c_void_p()
+        _check(lib().slk_bracken_create(index.h, int(read_len), int(max_fragment), C.byref(h)))
+        self.h = h
+
+    def add(self, bases, offsets, source_taxa):
+        bases, offsets, taxa = _np(bases, np.uint8), _np(offsets, np.uint64), _np(source_taxa, np.int32)
+        assert offsets.size == taxa.size + 1
+        _check(lib().slk_bracken_add(self.h, self.stream.h, _ptr(bases), _ptr(offsets), _ptr(taxa), taxa.size))
+
+    def result(self):
+        n = C.c_uint64(0)
+        _check(lib().slk_bracken_result(self.h, C.byref(n), None, None, None, 0))
+        dest, source, count = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_bracken_result(self.h, C.byref(n), _ptr(dest), _ptr(source), _ptr(count), n.value))
+        return dest, source, count
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slk_bracken_destroy(self.h)
             self.h = None
 
     def __del__(self):

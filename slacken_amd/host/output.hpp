@@ -444,4 +444,28 @@ class OutputSink {
   }
 };
 
+// BrackenWeights.writeKmerDistrib (S/slacken/BrackenWeights.scala:377-431): the header, then one line per destination taxon,
+// "dest\tsource:count:total source:count:total ..." where total is the source's reads over all destinations (groupData).  Spark
+// leaves the line order open; here the destinations ascend and so do the sources within a line.  Triples in any order.
+inline std::string kmer_distrib_text(const std::vector<int32_t> &dest, const std::vector<int32_t> &source, const std::vector<uint64_t> &count) {
+  std::map<int32_t, uint64_t> total;
+  std::map<int32_t, std::map<int32_t, uint64_t>> by_dest;
+  for (size_t i = 0; i < dest.size(); i++) {
+    total[source[i]] += count[i];
+    by_dest[dest[i]][source[i]] += count[i];
+  }
+  std::string s = "mapped_taxid\tgenome_taxids:kmers_mapped:total_genome_kmers\n";
+  for (auto &d : by_dest) {
+    s += std::to_string(d.first);
+    char sep = '\t';
+    for (auto &sc : d.second) {
+      s += sep;
+      s += std::to_string(sc.first) + ":" + std::to_string(sc.second) + ":" + std::to_string(total[sc.first]);
+      sep = ' ';
+    }
+    s += '\n';
+  }
+  return s;
+}
+
 }  // namespace slk_host

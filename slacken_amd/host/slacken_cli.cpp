@@ -296,7 +296,26 @@ struct ClassifyOpts {
   // GoldSetOptions (Dynamic.scala:62): a user-supplied taxon set to compare the detected set with, or to build the library from
   std::string gold_set, promote_rank;
   bool classify_with_gold = false;
+  int bracken_length = 0;       // --bracken-length (Slacken.scala:220,259): Bracken weights for the dynamic library as well
 };
+
+static std::vector<int> parse_device_list(const std::string &v) {   // --devices: `all` or e.g. 0,1,2,3
+  std::vector<int> out;
+  if (v == "all") {
+    for (int d = 0; d < slk_device_count(); d++) out.push_back(d);
+    if (out.empty()) die("--devices all: no GPU visible");
+    return out;
+  }
+  size_t p0 = 0;
+  while (p0 <= v.size()) {
+    size_t p1 = v.find(',', p0);
+    if (p1 == std::string::npos) p1 = v.size();
+    if (p1 == p0 || !isdigit((unsigned char)v[p0])) die("--devices wants `all` or a comma-separated list of device numbers");
+    out.push_back(std::stoi(v.substr(p0, p1 - p0)));
+    p0 = p1 + 1;
+  }
+  return out;
+}
 
 static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
   ClassifyOpts o;
@@ -313,23 +332,7 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
     else if (a == "--nodetailed") o.detailed = false;
     else if (a == "-c" || a == "--confidence") { while (i + 1 < argc && (isdigit(argv[i + 1][0]) || argv[i + 1][0] == '.')) o.thresholds.push_back(std::stod(argv[++i])); }
     else if (a == "--sample-regex") o.sample_regex = next();
-    else if (a == "--devices") {
-      std::string v = next();
-      o.devices.clear();
-      if (v == "all") {
-        for (int d = 0; d < slk_device_count(); d++) o.devices.push_back(d);
-        if (o.devices.empty()) die("--devices all: no GPU visible");
-      } else {
-        size_t p0 = 0;
-        while (p0 <= v.size()) {
-          size_t p1 = v.find(',', p0);
-          if (p1 == std::string::npos) p1 = v.size();
-          if (p1 == p0 || !isdigit((unsigned char)v[p0])) die("--devices wants `all` or a comma-separated list of device numbers");
-          o.devices.push_back(std::stoi(v.substr(p0, p1 - p0)));
-          p0 = p1 + 1;
-        }
-      }
-    }
+    else if (a == "--devices") o.devices = parse_device_list(next());
     else if (a == "--shard-table") { if (two_step) die("--shard-table is for classify (the dynamic library of classify2 is small)"); o.shard_table = true; }
     else if (two_step && (a == "-l" || a == "--library")) o.library = next();
     else if (two_step && a == "--rank") o.rank = next();
@@ -340,8 +343,12 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
     else if (two_step && (a == "-g" || a == "--gold-set")) o.gold_set = next();
     else if (two_step && a == "--classify-with-gold") o.classify_with_gold = true;
     else if (two_step && a == "--promote-gold-set") o.promote_rank = next();
-    else if (two_step && (a == "--bracken-length" || a == "--index-reports"))
-      die(a + " is not supported by this engine (Bracken weights and index reports are outside the classify path)");
+    else if (two_step && a == "--bracken-length") {
+      o.bracken_length = std::stoi(next());
+      if (o.bracken_length < 1) die("--bracken-length must be a positive number of bases");
+    }
+    else if (two_step && a == "--index-reports")
+      die(a + " is not supported by this engine (index reports are outside the classify path)");
     else if (!a.empty() && a[0] == '@') { std::ifstream lf(a.substr(1)); std::string l; while (std::getline(lf, l)) if (!trim(l).empty()) o.files.push_back(trim(l)); }
     else if (!a.empty() && a[0] == '-') die("unknown option " + a);
     else o.files.push_back(a);
@@ -1018,6 +1025,80 @@ static void load_index(const std::string &location, IndexParams &ip, Taxonomy &t
   std::cerr << "index: " << n_records << " records, k=" << ip.k << " m=" << ip.m << " spaces=" << ip.spaces << std::endl;
 }
 
+// ---- Bracken weights (BrackenWeights.scala) for bracken-build and classify2 --bracken-length ----
+// Records arrive in batches (add); within a batch, record r goes to replica r mod n of --devices, and each replica adds its share
+// on a thread of its own (bracken.hip).  Host memory holds one batch at a time.  finish() sums the replicas' triples into the
+// kmer_distrib file.
+class BrackenRun {
+  DeviceIndex &dev_;
+  std::vector<slk_stream *> st_;
+  std::vector<slk_bracken *> b_;
+
+ public:
+  static constexpr uint64_t BATCH_BYTES = 1ULL << 30;   // per replica: one engine batch (bracken.hip: batch_bytes)
+  BrackenRun(DeviceIndex &dev, int read_len) : dev_(dev), st_(dev.ixs.size(), nullptr), b_(dev.ixs.size(), nullptr) {
+    for (size_t g = 0; g < dev.ixs.size(); g++) {
+      SLK_CALL(slk_stream_create(dev.ixs[g], &st_[g]));
+      SLK_CALL(slk_bracken_create(dev.ixs[g], read_len, 0, &b_[g]));
+    }
+  }
+  ~BrackenRun() {
+    for (slk_bracken *b : b_) slk_bracken_destroy(b);
+    for (slk_stream *s : st_) if (s) slk_stream_destroy(s);
+  }
+  size_t replicas() const { return b_.size(); }
+  // bases without whitespace (regexp_replace, BrackenWeights.scala:311)
+  void add(const std::vector<uint8_t> &bases, const std::vector<uint64_t> &offsets, const std::vector<int32_t> &taxa) {
+    const size_t n = b_.size();
+    std::vector<std::string> err(n);
+    std::vector<std::thread> th;
+    for (size_t g = 0; g < n; g++)
+      th.emplace_back([&, g] {
+        std::vector<uint8_t> bb;
+        std::vector<uint64_t> oo(1, 0);
+        std::vector<int32_t> tt;
+        const uint8_t *base = bases.data();
+        const uint64_t *off = offsets.data();
+        const int32_t *tx = taxa.data();
+        size_t R = taxa.size();
+        if (n > 1) {   // this replica's records
+          for (size_t r = g; r < taxa.size(); r += n) {
+            bb.insert(bb.end(), bases.begin() + offsets[r], bases.begin() + offsets[r + 1]);
+            oo.push_back(bb.size());
+            tt.push_back(taxa[r]);
+          }
+          base = bb.data(); off = oo.data(); tx = tt.data(); R = tt.size();
+        }
+        if (R && slk_bracken_add(b_[g], st_[g], base, off, tx, R) != SLK_OK) err[g] = std::string("slk_bracken_add: ") + slk_last_error();
+      });
+    for (auto &x : th) x.join();
+    for (auto &e : err) if (!e.empty()) die(e);
+  }
+  void finish(const std::string &out_file) {
+    std::vector<int32_t> d, s;
+    std::vector<uint64_t> c;
+    for (slk_bracken *b : b_) {
+      uint64_t m = 0;
+      SLK_CALL(slk_bracken_result(b, &m, nullptr, nullptr, nullptr, 0));
+      const size_t at = d.size();
+      d.resize(at + m); s.resize(at + m); c.resize(at + m);
+      SLK_CALL(slk_bracken_result(b, &m, d.data() + at, s.data() + at, c.data() + at, m));
+    }
+    const fs::path out(out_file);
+    if (out.has_parent_path()) fs::create_directories(out.parent_path());
+    std::ofstream f(out_file);
+    if (!f) die("cannot write " + out_file);
+    f << kmer_distrib_text(d, s, c);
+    std::cerr << "wrote " << out_file << std::endl;
+  }
+};
+
+// append one record with its whitespace removed
+static void append_stripped(std::vector<uint8_t> &bases, std::vector<uint64_t> &offsets, std::string_view sq) {
+  for (char ch : sq) if (!isspace((unsigned char)ch)) bases.push_back((uint8_t)ch);
+  offsets.push_back(bases.size());
+}
+
 static int cmd_classify(int argc, char **argv) {
   ClassifyOpts o = parse_classify_opts(argc, argv, false);
   IndexParams ip;
@@ -1135,6 +1216,8 @@ static int cmd_classify2(int argc, char **argv) {
     DeviceIndex base;
     base.devices = o.devices;
     load_index(o.index, ip, tax, base);
+    if (o.bracken_length > 0 && o.bracken_length < ip.k)
+      die("--bracken-length " + std::to_string(o.bracken_length) + " is shorter than k = " + std::to_string(ip.k));
     slk_index_info info;
     SLK_CALL(slk_index_get_info(base.ix, &info));
     max_taxon = info.taxonomy_size - 1;
@@ -1264,6 +1347,101 @@ static int cmd_classify2(int argc, char **argv) {
   SLK_CALL(slk_index_get_info(dyn.ix, &info));
   std::cerr << "dynamic index: " << info.records << " records" << std::endl;
   classify_and_write(dyn, ip, tax, o);
+  if (o.bracken_length > 0) {   // Dynamic.scala:339-344: the dynamic library's genomes against the dynamic index
+    Timer t("Bracken weights");
+    BrackenRun br(dyn, o.bracken_length);
+    std::vector<uint8_t> bb;
+    std::vector<uint64_t> oo(1, 0);
+    std::vector<int32_t> tt;
+    for (size_t r = 0; r < taxa.size(); r++) {
+      append_stripped(bb, oo, std::string_view((const char *)bases.data() + offsets[r], offsets[r + 1] - offsets[r]));
+      tt.push_back(taxa[r]);
+      if (bb.size() >= BrackenRun::BATCH_BYTES * br.replicas()) { br.add(bb, oo, tt); bb.clear(); oo.assign(1, 0); tt.clear(); }
+    }
+    br.add(bb, oo, tt);
+    br.finish(o.output + "/database" + std::to_string(o.bracken_length) + "mers.kmer_distrib");
+  }
+  return 0;
+}
+
+// bracken-build (Slacken.scala:264-279): BrackenWeights.buildAndWriteWeights over the whole library, taxa = GenomeLibrary.taxonSet
+// (GenomeLibrary.scala:35-44: the labelled taxa with their ancestors; a label outside the taxonomy is dropped)
+static int cmd_bracken_build(int argc, char **argv) {
+  std::string index, library;
+  int read_len = 100;
+  std::vector<int> devices{0};
+  for (int i = 0; i < argc; i++) {
+    std::string a = argv[i];
+    auto next = [&]() { if (i + 1 >= argc) die("missing value for " + a); return std::string(argv[++i]); };
+    if (a == "-i" || a == "--index") index = next();
+    else if (a == "-l" || a == "--library") library = next();
+    else if (a == "--read-len") read_len = std::stoi(next());
+    else if (a == "--devices") devices = parse_device_list(next());
+    else if (a == "--shard-table") die("--shard-table is not supported by bracken-build: the library is replicated on each device");
+    else die("unknown option " + a);
+  }
+  if (index.empty() || library.empty()) die("usage: bracken-build -i INDEX --library DIR [--read-len L (100)] [--devices LIST]");
+  if (read_len < 1) die("--read-len must be a positive number of bases");
+  IndexParams ip;
+  Taxonomy tax;
+  DeviceIndex dev;
+  dev.devices = devices;
+  load_index(index, ip, tax, dev);
+  if (read_len < ip.k) die("--read-len " + std::to_string(read_len) + " is shorter than k = " + std::to_string(ip.k));
+  std::unordered_map<std::string, Taxon> labels;
+  {
+    std::ifstream lf(library + "/seqid2taxid.map");
+    if (!lf) die("cannot open " + library + "/seqid2taxid.map");
+    std::string l;
+    while (std::getline(lf, l)) {
+      size_t tab = l.find('\t');
+      if (tab == std::string::npos) continue;
+      const Taxon t = (Taxon)std::stoi(l.substr(tab + 1));
+      if (t > 0 && t < tax.size()) labels[l.substr(0, tab)] = t;
+    }
+  }
+  std::vector<std::string> fna;
+  find_fna(fs::path(library) / "library", fna);
+  // the records stream through: one batch per replica in host memory at a time
+  Timer t("Bracken weights");
+  BrackenRun br(dev, read_len);
+  std::vector<uint8_t> bases;
+  std::vector<uint64_t> offsets(1, 0);
+  std::vector<int32_t> taxa;
+  uint64_t n_seq = 0, n_bases = 0;
+  for (auto &file : fna) {
+    AsyncRecordStream rs(file);
+    std::string_view h, sq;
+    while (rs.next(h, sq)) {
+      auto it = labels.find(std::string(h));
+      if (it == labels.end()) continue;
+      append_stripped(bases, offsets, sq);
+      taxa.push_back(it->second);
+      if (bases.size() >= BrackenRun::BATCH_BYTES * br.replicas()) {
+        n_seq += taxa.size(); n_bases += bases.size();
+        br.add(bases, offsets, taxa);
+        bases.clear(); offsets.assign(1, 0); taxa.clear();
+      }
+    }
+  }
+  n_seq += taxa.size(); n_bases += bases.size();
+  br.add(bases, offsets, taxa);
+  std::cerr << "Bracken weights of " << n_seq << " sequences, " << n_bases << " bases, read length " << read_len << std::endl;
+  br.finish(index + "_bracken/database" + std::to_string(read_len) + "mers.kmer_distrib");
+  return 0;
+}
+
+// kmer-distrib TRIPLES_TSV: the kmer_distrib text of "dest \t source \t count" lines (host only: the file format without a GPU)
+static int cmd_kmer_distrib(int argc, char **argv) {
+  if (argc < 1) die("usage: kmer-distrib TRIPLES_TSV");
+  std::ifstream f(argv[0]);
+  if (!f) die(std::string("cannot open ") + argv[0]);
+  std::vector<int32_t> d, s;
+  std::vector<uint64_t> c;
+  long long a, b;
+  unsigned long long n;
+  while (f >> a >> b >> n) { d.push_back((int32_t)a); s.push_back((int32_t)b); c.push_back(n); }
+  std::cout << kmer_distrib_text(d, s, c);
   return 0;
 }
 
@@ -1291,8 +1469,12 @@ static const char *HELP =
     "  -R, --reads N (100) | -C, --min-count N | -D, --min-distinct N, --init-confidence X (0.15)\n"
     "  -g, --gold-set FILE (a taxon per line: the detected set is compared with it), --classify-with-gold (the dynamic library is built\n"
     "  from the gold set instead of a detected one), --promote-gold-set RANK (gold taxa without sequence in the library: keep the\n"
-    "  ancestors they are promoted to down to RANK)\n"
-    "host-only helpers: report TAXONOMY_DIR COUNTS_TSV | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
+    "  ancestors they are promoted to down to RANK), --bracken-length L (Bracken weights of the dynamic library's genomes for reads of\n"
+    "  length L, written to OUTPUT/databaseLmers.kmer_distrib)\n"
+    "  slacken-amd bracken-build -i INDEX --library DIR [--read-len L (100)] [--devices LIST] (Slacken.scala:264-279): Bracken weights\n"
+    "  of every genome of DIR labelled in DIR/seqid2taxid.map, written to INDEX_bracken/databaseLmers.kmer_distrib; the records are\n"
+    "  shared out over the devices\n"
+    "host-only helpers: report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
     "environment: SLK_HOST_THREADS (formatting/decoding threads), SLK_INPUT_STREAMS (input files read side by side, default 8),\n"
     "             SLK_PARSE_THREADS (threads parsing one plain input file, default min(8, cores/2)), SLK_GZIP_LEVEL (1..9, default zlib's),\n"
     "             SLK_GZ_THREADS (threads inflating one gzip input file, default min(16, cores / files read side by side); 0: zlib),\n"
@@ -1302,7 +1484,7 @@ static const char *HELP =
 int main(int argc, char **argv) {
   int i = 1;
   while (i < argc && std::string(argv[i]) == "--partitions") i += 2;  // global Spark option of the reference: accepted, unused
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1316,8 +1498,10 @@ int main(int argc, char **argv) {
     if (cmd == "records") return cmd_records(argc - i, argv + i);
     if (cmd == "repeated") return cmd_repeated(argc - i, argv + i);
     if (cmd == "taxonomy") return cmd_taxonomy(argc - i, argv + i);
+    if (cmd == "bracken-build") return cmd_bracken_build(argc - i, argv + i);
+    if (cmd == "kmer-distrib") return cmd_kmer_distrib(argc - i, argv + i);
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command " + cmd + " (this engine implements `classify` and `classify2`; the reference's other subcommands are out of scope)");
+  die("unknown command " + cmd + " (this engine implements `classify`, `classify2` and `bracken-build`; the reference's other subcommands are out of scope)");
 }
