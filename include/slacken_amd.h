@@ -417,7 +417,11 @@ int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count);
  *                        (SLK_E_UNSUPPORTED otherwise, as the staged device entries)
  *   slk_bracken_add      R whole records (any length, any host memory; bases WITHOUT whitespace, as after regexp_replace :311)
  *                        with the taxon each came from (TaxonFragment.taxon).  Synchronous on st.  The counts do not depend on how
- *                        the records are split into calls or on their order.
+ *                        the records are split into calls or on their order.  A call that fails after its arguments were
+ *                        accepted (SLK_E_CAPACITY: more (source, dest) pairs than the map holds, SLK_BRACKEN_MAP_LOG2; SLK_E_HIP)
+ *                        has counted an unknown part of its records: the handle is spent.  Every later slk_bracken_add and
+ *                        slk_bracken_result on it returns SLK_E_STATE; slk_bracken_destroy is what remains.  A call refused
+ *                        with SLK_E_INVALID counted nothing and leaves the handle usable.
  *   slk_bracken_result   the triples so far, dest ascending then source ascending; *n = their number; cap 0 queries only
  *                        that, 0 < cap < *n gives SLK_E_CAPACITY
  * The ordinal the reference gives a segment's trailing hit lacks the segment's position (:230); this engine reproduces what

@@ -304,6 +304,7 @@ struct slk_bracken {
   std::vector<uint64_t> h_offsets, h_chunk0;
   std::vector<int32_t> h_source;
   std::vector<uint32_t> h_chunk_piece;
+  bool spent = false;   // a batch failed: the map holds part of it, so no count of this handle can be trusted any more
 };
 
 static int32_t br_grow_map(slk_bracken *b, hipStream_t s, uint64_t cap) {
@@ -330,7 +331,15 @@ static int32_t br_read_map(slk_bracken *b, hipStream_t s, std::vector<uint64_t> 
   return SLK_OK;
 }
 
-static int32_t br_run_batch(slk_bracken *b, slk_stream *st) {
+static void br_clear_batch(slk_bracken *b) {
+  b->h_bases.clear();
+  b->h_offsets.assign(1, 0);
+  b->h_chunk0.clear();
+  b->h_source.clear();
+  b->h_chunk_piece.clear();
+}
+
+static int32_t br_run_batch_device(slk_bracken *b, slk_stream *st) {
   const uint64_t R = b->h_source.size();
   if (R == 0) return SLK_OK;
   slk_index *ix = b->ix;
@@ -400,14 +409,23 @@ static int32_t br_run_batch(slk_bracken *b, slk_stream *st) {
     HIPCHK(hipMemcpyAsync(&status, b->status.p, 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
   }
-  if (status & 2)   // the handle is spent: its counts are incomplete
+  if (status & 2)
     return fail(SLK_E_CAPACITY, "bracken: more (source, dest) pairs than the map holds (%llu; SLK_BRACKEN_MAP_LOG2)",
                 (unsigned long long)b->map_cap);
-  b->h_bases.clear();
-  b->h_offsets.assign(1, 0);
-  b->h_chunk0.clear();
-  b->h_source.clear();
-  b->h_chunk_piece.clear();
+  return SLK_OK;
+}
+
+// Runs the batch assembled on the host and empties it, whatever the outcome.  A batch that failed has added an unknown part of its
+// runs to the map: the handle is spent, and slk_bracken_add / slk_bracken_result refuse it from then on.
+static int32_t br_run_batch(slk_bracken *b, slk_stream *st) {
+  const int32_t rc = br_run_batch_device(b, st);
+  br_clear_batch(b);
+  if (rc) b->spent = true;
+  return rc;
+}
+
+static int32_t br_check_spent(const slk_bracken *b) {
+  if (b->spent) return fail(SLK_E_STATE, "bracken: an earlier slk_bracken_add failed, the counts of this handle are incomplete");
   return SLK_OK;
 }
 
@@ -450,7 +468,9 @@ int32_t slk_bracken_create(slk_index *ix, int32_t read_len, uint64_t max_fragmen
 int32_t slk_bracken_add(slk_bracken *b, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const int32_t *source_taxa,
                         uint64_t R) {
   if (!b) return fail(SLK_E_INVALID, "null handle");
-  int32_t rc = check_ready(b->ix, st, true);
+  int32_t rc = br_check_spent(b);
+  if (rc) return rc;
+  rc = check_ready(b->ix, st, true);
   if (rc) return rc;
   if (R && (!bases || !offsets || !source_taxa)) return fail(SLK_E_INVALID, "null argument");
   for (uint64_t r = 0; r < R; r++) {
@@ -488,7 +508,9 @@ int32_t slk_bracken_add(slk_bracken *b, slk_stream *st, const uint8_t *bases, co
 int32_t slk_bracken_result(slk_bracken *b, uint64_t *n, int32_t *dest, int32_t *source, uint64_t *count, uint64_t cap) {
   if (!b || !n) return fail(SLK_E_INVALID, "null argument");
   if (cap && (!dest || !source || !count)) return fail(SLK_E_INVALID, "null argument");
-  int32_t rc = set_device(b->ix);
+  int32_t rc = br_check_spent(b);
+  if (rc) return rc;
+  rc = set_device(b->ix);
   if (rc) return rc;
   std::vector<uint64_t> keys, counts;
   rc = br_read_map(b, nullptr, keys, counts);

@@ -14,6 +14,8 @@ import taxgen
 
 MAPCAP = 16   # bracken.hip: BR_MAPCAP
 CHUNK = 512   # bracken.hip: BR_CHUNK
+GRID_LANES = 256 * 40 * 64   # bracken.hip: br_run_batch caps the window kernel's grid at 256 * 40 blocks of BR_BLOCK = 64 lanes
+MIN_MAP_LOG2 = 10            # bracken.hip: the smallest (source, dest) map SLK_BRACKEN_MAP_LOG2 gives
 
 
 def deficits(orc, p, index, piece, read_len, qt):

@@ -12,9 +12,10 @@ pytestmark = pytest.mark.gpu
 slacken_amd = pytest.importorskip("slacken_amd")
 
 
-def device_index(p, keys, taxa, parents, spaces, canonical):
+def device_index(p, keys, taxa, parents, spaces, canonical, xor_mask=None):
+    mask = {} if xor_mask is None else dict(xor_mask=xor_mask)
     ix = slacken_amd.Index(k=p.k, m=p.m, spaces=spaces, canonical=canonical, expected_records=len(keys) + 1000,
-                           max_taxon=len(parents) - 1)
+                           max_taxon=len(parents) - 1, **mask)
     ix.append(keys, taxa)
     ix.set_taxonomy(parents)
     ix.finalize()
