@@ -131,7 +131,13 @@ int32_t slk_host_free(void *ptr);
 int32_t slk_index_create(const slk_params *params, const slk_table_config *cfg, int32_t device, slk_index **out);
 /* Append records (id1: int64 left-aligned minimizer, taxon: int32) -- the rows of the Parquet table, in any order
  * and any chunking (one call per bucket file is the intended use).  Keys are unique (guaranteed by makeRecords'
- * groupBy, KeyValueIndex.scala:85-93).  Records with taxon == NONE are skipped (indistinguishable from a miss). */
+ * groupBy, KeyValueIndex.scala:85-93).  Records with taxon == NONE are skipped (indistinguishable from a miss).
+ * A table that runs out of reach for a record grows (twice the buckets) and the call goes on.  If the growth fails, one of two
+ * things holds.  While both tables fit the device, and whenever the failure comes before the old table is touched (no larger
+ * geometry, no memory for the pieces), the index keeps its old table intact and only this call fails.  When the records had to
+ * wait in host memory -- the old table is freed before the new one can be allocated -- they are lost with the failure: the
+ * index is SPENT, every later call that takes it except slk_index_destroy returns SLK_E_STATE, and the load must be repeated
+ * (with a larger slk_table_config.expected_records).  The same holds for the other calls that add records. */
 int32_t slk_index_append(slk_index *ix, const int64_t *keys, const int32_t *taxa, uint64_t n);
 int32_t slk_index_append_device(slk_index *ix, const int64_t *d_keys, const int32_t *d_taxa, uint64_t n);
 /* Table-sharded libraries (a table beyond one GPU's memory; BASELINE.json configs[3], the exchange that replaces the shuffle of
@@ -224,6 +230,9 @@ int32_t slk_spans_batch_wide(slk_index *ix, slk_stream *st, const uint8_t *bases
  *     out_hit_offsets without out_hits: the number of spans per read only (offsets[r+1] - offsets[r]); the lists are then
  *     neither built nor copied, and the call takes the kernels that do not keep span order (the fastest route).
  * The caller's buffers may be any host memory: the copies go through pinned staging buffers of the stream.
+ * Synchronous, also when it fails: on every return, with an error too, nothing is queued any more that reads the caller's
+ * input or writes its output, so the buffers may be freed (the same holds for slk_classify_batch_packed, slk_classify_hits
+ * and slk_spans_batch[_wide]).
  * Sample-id regex, titles, duplicate-title merging and text formatting stay on the host. */
 int32_t slk_classify_batch(slk_index *ix, slk_stream *st, const uint8_t *bases, const uint64_t *offsets,
                            const uint8_t *mate_bases, const uint64_t *mate_offsets, uint64_t R,

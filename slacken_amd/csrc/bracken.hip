@@ -445,23 +445,23 @@ int32_t slk_bracken_create(slk_index *ix, int32_t read_len, uint64_t max_fragmen
     return fail(SLK_E_INVALID, "max_fragment must lie in [read_len, 2^31)");
   int32_t rc = set_device(ix);
   if (rc) return rc;
-  slk_bracken *b = new slk_bracken();
+  std::unique_ptr<slk_bracken> b(new slk_bracken());   // (released into *out on success only)
   b->ix = ix;
   b->read_len = read_len;
   b->W = read_len - ix->params.k + 1;   // kmersInRead (:263)
   b->max_fragment = max_fragment;
-  if (const char *e = getenv("SLK_BRACKEN_BATCH_MB")) b->batch_bytes = std::max<uint64_t>(1, strtoull(e, nullptr, 10)) << 20;
+  b->batch_bytes = (uint64_t)std::max(1L, env_long("SLK_BRACKEN_BATCH_MB", 1L << 10)) << 20;
   b->batch_bytes = std::max<uint64_t>(b->batch_bytes, max_fragment);
   b->h_offsets.assign(1, 0);
   hipError_t e = b->status.ensure(8);
   if (e == hipSuccess) e = hipMemset(b->status.p, 0, 8);
-  if (e != hipSuccess) { delete b; (void)hipGetLastError(); return fail(SLK_E_HIP, "bracken: %s", hipGetErrorString(e)); }
-  int map_log2 = 22;   // 4 M pairs (64 MiB): a standard library has a few hundred thousand
-  if (const char *v = getenv("SLK_BRACKEN_MAP_LOG2")) map_log2 = std::min(32, std::max(10, atoi(v)));
-  rc = br_grow_map(b, nullptr, 1ULL << map_log2);
+  if (e != hipSuccess) { (void)hipGetLastError(); return fail(SLK_E_HIP, "bracken: %s", hipGetErrorString(e)); }
+  // 2^22 = 4 M pairs (64 MiB): a standard library has a few hundred thousand
+  const int map_log2 = (int)std::min(32L, std::max(10L, env_long("SLK_BRACKEN_MAP_LOG2", 22)));
+  rc = br_grow_map(b.get(), nullptr, 1ULL << map_log2);
   if (rc == SLK_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(SLK_E_HIP, "bracken: map setup failed");
-  if (rc) { slk_bracken_destroy(b); return rc; }
-  *out = b;
+  if (rc) return rc;
+  *out = b.release();
   return SLK_OK;
 }
 
@@ -535,10 +535,6 @@ int32_t slk_bracken_result(slk_bracken *b, uint64_t *n, int32_t *dest, int32_t *
 void slk_bracken_destroy(slk_bracken *b) {
   if (!b) return;
   (void)hipSetDevice(b->ix->device);
-  for (DevBuf *d : {&b->map_keys, &b->map_counts, &b->status, &b->bases, &b->offsets, &b->span_keys, &b->span_meta, &b->span_taxon,
-                    &b->span_count, &b->ktax, &b->kflag, &b->qtax, &b->qend, &b->chunk0, &b->source, &b->chunk_piece, &b->deficit,
-                    &b->overflow, &b->n_overflow, &b->scratch})
-    d->release();
   delete b;
 }
 

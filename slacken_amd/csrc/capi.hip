@@ -4,7 +4,7 @@
 #include "hostside.h"
 #include "../host/pack.hpp"
 
-extern "C" {
+// (The slk_* functions below have C linkage from their declarations in include/slacken_amd.h; everything else is internal.)
 
 const char *slk_last_error(void) { return g_err.c_str(); }
 const char *slk_version(void) { return "slacken_amd 0.1 (gfx950)"; }
@@ -13,7 +13,7 @@ const char *slk_version(void) { return "slacken_amd 0.1 (gfx950)"; }
 int32_t slk_host_alloc(size_t bytes, void **out) {
   if (!out) return fail(SLK_E_INVALID, "null argument");
   *out = nullptr;
-  void *p = nullptr;
+  void *p = nullptr;   // (the caller's from here on: slk_host_free)
   HIPCHK(hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault));
   pinned().add(p, bytes ? bytes : 1, true);
   *out = p;
@@ -57,7 +57,7 @@ static TableShape shape_of(uint64_t nb, int tb) {
   sh.q = ceil_log2_u64(sh.nb);
   const bool pow2 = sh.nb == (1ULL << sh.q);
   const int avail = 64 - tb - (64 - sh.q + (pow2 ? 0 : 1));
-  static const bool no_flag = getenv("SLK_NO_BUCKET_FLAG") != nullptr && getenv("SLK_NO_BUCKET_FLAG")[0] == '1';   // (A/B switch)
+  static const bool no_flag = env_on("SLK_NO_BUCKET_FLAG");   // (A/B switch)
   sh.flag = avail - 1 >= DISP_MIN && !no_flag;
   sh.disp = std::min(8, avail - (sh.flag ? 1 : 0));
   return sh;
@@ -74,6 +74,18 @@ static TableShape settle_shape(uint64_t nb, uint64_t records, int tb, bool *ok) 
   while (sh.nb < (1ULL << 32) && sh.disp < std::max(DISP_MIN, need_disp_bits((double)records / ((double)sh.nb * CELLS)))) sh = shape_of(grow_buckets(sh.nb), tb);
   *ok = !(sh.nb > (1ULL << 32) || sh.disp < DISP_MIN);
   return sh;
+}
+
+// the build stream and the build counters of a new index, and its table (either kind) zeroed
+static int32_t start_build_state(slk_index *ix, void *table, size_t table_bytes) {
+  HIPCHK(hipStreamCreate(ix->build_stream.put()));
+  HIPCHK(hipMemsetAsync(table, 0, table_bytes, ix->build_stream));
+  HIPCHK(hipMalloc((void **)ix->d_max_disp.put(), sizeof(int32_t)));
+  HIPCHK(hipMalloc((void **)ix->d_counters.put(), 3 * sizeof(unsigned long long)));
+  HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), ix->build_stream));
+  HIPCHK(hipMemsetAsync(ix->d_counters, 0, 3 * sizeof(unsigned long long), ix->build_stream));
+  HIPCHK(hipStreamSynchronize(ix->build_stream));
+  return SLK_OK;
 }
 
 int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32_t device, slk_index **out) {
@@ -98,7 +110,7 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
     return fail(SLK_E_NO_GPU, "device %d is %s; this library holds gfx950 (MI355X) code objects only", device,
                 prop.gcnArchName);
 
-  slk_index *ix = new slk_index();
+  std::unique_ptr<slk_index> ix(new slk_index());   // (released into *out on success only)
   ix->device = device;
   ix->params = *p;
   ScanParams &sp = ix->sp;
@@ -132,23 +144,18 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
     uint64_t cap = 1ULL << ceil_log2_u64(std::max<uint64_t>(cfg->expected_records, 8) * 2);
     ix->wt.mask = cap - 1;
     ix->taxon_bits = 31;
-    hipError_t e1 = hipMalloc((void **)&ix->wt.keys, cap * W * 8);
-    hipError_t e2 = e1 == hipSuccess ? hipMalloc((void **)&ix->wt.taxa, cap * 4) : e1;
+    hipError_t e1 = hipMalloc((void **)ix->wide_keys.put(), cap * W * 8);
+    hipError_t e2 = e1 == hipSuccess ? hipMalloc((void **)ix->wide_taxa.put(), cap * 4) : e1;
     if (e2 != hipSuccess) {
       (void)hipGetLastError();
-      if (ix->wt.keys) (void)hipFree(ix->wt.keys);
-      delete ix;
       return fail(SLK_E_HIP, "hipMalloc of the %llu-slot table failed: %s", (unsigned long long)cap, hipGetErrorString(e2));
     }
-    HIPCHK(hipStreamCreate(&ix->build_stream));
-    HIPCHK(hipMemsetAsync(ix->wt.taxa, 0, cap * 4, ix->build_stream));
-    HIPCHK(hipMalloc((void **)&ix->d_max_disp, sizeof(int32_t)));
-    HIPCHK(hipMalloc((void **)&ix->d_counters, 3 * sizeof(unsigned long long)));
-    HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), ix->build_stream));
-    HIPCHK(hipMemsetAsync(ix->d_counters, 0, 3 * sizeof(unsigned long long), ix->build_stream));
-    HIPCHK(hipStreamSynchronize(ix->build_stream));
+    ix->wt.keys = ix->wide_keys;
+    ix->wt.taxa = ix->wide_taxa;
     ix->nbuckets = cap;
-    *out = ix;
+    int32_t rc = start_build_state(ix.get(), ix->wt.taxa, cap * 4);
+    if (rc) return rc;
+    *out = ix.release();
     return SLK_OK;
   }
   int32_t max_taxon = cfg->max_taxon > 0 ? cfg->max_taxon : ((1 << 22) - 1);
@@ -178,7 +185,7 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
   const uint64_t cells_needed = (uint64_t)((double)expected / lf) + CELLS;
   bool shape_ok = false;
   const TableShape sh = settle_shape((cells_needed + CELLS - 1) / CELLS, expected, tb, &shape_ok);
-  if (!shape_ok) { delete ix; return fail(SLK_E_CAPACITY, "a table of %llu buckets is too large", (unsigned long long)sh.nb); }
+  if (!shape_ok) { return fail(SLK_E_CAPACITY, "a table of %llu buckets is too large", (unsigned long long)sh.nb); }
   ix->load_target = (float)lf;
   ix->bucket_bits = sh.q;
   ix->taxon_bits = tb;
@@ -186,19 +193,14 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
   ix->bucket_flag = sh.flag;
   ix->nbuckets = sh.nb;
   size_t bytes = (size_t)ix->nbuckets * CELLS * 8;
-  hipError_t e = hipMalloc((void **)&ix->cells, bytes);
+  hipError_t e = hipMalloc((void **)ix->cells.put(), bytes);
   if (e != hipSuccess) {
-    delete ix;
+    (void)hipGetLastError();
     return fail(SLK_E_HIP, "hipMalloc of %zu table bytes failed: %s", bytes, hipGetErrorString(e));
   }
-  HIPCHK(hipStreamCreate(&ix->build_stream));
-  HIPCHK(hipMemsetAsync(ix->cells, 0, bytes, ix->build_stream));
-  HIPCHK(hipMalloc((void **)&ix->d_max_disp, sizeof(int32_t)));
-  HIPCHK(hipMalloc((void **)&ix->d_counters, 3 * sizeof(unsigned long long)));
-  HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), ix->build_stream));
-  HIPCHK(hipMemsetAsync(ix->d_counters, 0, 3 * sizeof(unsigned long long), ix->build_stream));
-  HIPCHK(hipStreamSynchronize(ix->build_stream));
-  *out = ix;
+  int32_t rc = start_build_state(ix.get(), ix->cells, bytes);
+  if (rc) return rc;
+  *out = ix.release();
   return SLK_OK;
 }
 
@@ -237,6 +239,21 @@ static TableBuild build_view(slk_index *ix) {
 // through a bounded staging buffer -- on the device while both tables fit its memory, through host memory otherwise --, and the
 // insert that hit the limit runs again (records it had placed are found again as duplicates of themselves: the caller corrects
 // the count).  Replaces KeyValueIndex.loadRecords' "it is a table scan: any size works" (S/slacken/KeyValueIndex.scala:150-159).
+//
+// When this fails.  Before the old table is touched -- no larger geometry, no memory for the pieces -- and on the device route
+// throughout, the index keeps its old table, intact, and the call that needed the room fails alone.  The host route has to free the
+// old table before it can allocate the new one: from there on a failure loses the records, the index is marked spent, and every
+// later entry that takes it (set_device) says that the load must be repeated.
+// buckets [b0, b1) of a table as records in dk / dt (room for `cap`), *n of them; complete on return
+static int32_t export_piece(slk_index *ix, const TableView &from, uint64_t b0, uint64_t b1, DevBuf &dk, DevBuf &dt, DevBuf &dc, uint64_t cap,
+                            unsigned long long *n) {
+  HIPCHK(hipMemsetAsync(dc.p, 0, 8, ix->build_stream));
+  launch_export_range(from, b0, b1, dk.as<int64_t>(), dt.as<int32_t>(), cap, dc.as<unsigned long long>(), ix->build_stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(n, dc.p, 8, hipMemcpyDeviceToHost, ix->build_stream));
+  HIPCHK(hipStreamSynchronize(ix->build_stream));
+  return SLK_OK;
+}
 static int32_t grow_table(slk_index *ix) {
   bool ok = false;
   const TableShape sh = settle_shape(grow_buckets(ix->nbuckets), std::max<uint64_t>(ix->records, 1), ix->taxon_bits, &ok);
@@ -245,61 +262,48 @@ static int32_t grow_table(slk_index *ix) {
   const uint64_t CH = (uint64_t)1 << 24;   // buckets per piece (at most 2^27 records: 1.5 GB of staging)
   DevBuf dk, dt, dc;
   HIPCHK(dc.ensure(8));
-  uint64_t *new_cells = nullptr;
+  DevPtr<uint64_t> new_cells;
   // (SLK_GROW_VIA_HOST=1: take the host route although both tables would fit the device -- how the tests reach it)
-  const char *via_host = getenv("SLK_GROW_VIA_HOST");
-  const bool on_device = !(via_host && via_host[0] == '1') && hipMalloc((void **)&new_cells, new_bytes) == hipSuccess;
+  const bool on_device = !env_on("SLK_GROW_VIA_HOST") && hipMalloc((void **)new_cells.put(), new_bytes) == hipSuccess;
   if (!on_device) (void)hipGetLastError();
   const uint64_t cap = std::min<uint64_t>(CH, ix->nbuckets) * CELLS;
   HIPCHK(dk.ensure(cap * 8));
   HIPCHK(dt.ensure(cap * 4));
-  // scratch counters for the move (the index's own keep counting the caller's records); the new maximum displacement is the move's
-  unsigned long long *d_scratch = nullptr;
-  HIPCHK(hipMalloc((void **)&d_scratch, 3 * sizeof(unsigned long long)));
-  HIPCHK(hipMemsetAsync(d_scratch, 0, 3 * sizeof(unsigned long long), ix->build_stream));
-  std::vector<int64_t> h_keys;
-  std::vector<int32_t> h_taxa;
+  // scratch state of the move: inserted, duplicate, unplaced (the index's own counters keep counting the caller's records) and, in a
+  // fourth word, the new table's maximum displacement (the index keeps the old table's until the new one is adopted)
+  DevPtr<unsigned long long> d_scratch;
+  HIPCHK(hipMalloc((void **)d_scratch.put(), 4 * sizeof(unsigned long long)));
+  HIPCHK(hipMemsetAsync(d_scratch, 0, 4 * sizeof(unsigned long long), ix->build_stream));
   const TableView old_view = [&] { TableView v = ix->view(); v.to_orig = nullptr; return v; }();
   const uint64_t old_nb = ix->nbuckets;
-  uint64_t *old_cells = ix->cells;
-  auto adopt = [&](uint64_t *cells) {
-    ix->cells = cells; ix->nbuckets = sh.nb; ix->bucket_bits = sh.q; ix->disp_bits = sh.disp; ix->bucket_flag = sh.flag;
-  };
+  TableBuild nb = build_view(ix);   // the new table
+  nb.g = slk_index::geom_of(sh.nb, sh.q, sh.flag, ix->taxon_bits, sh.disp);
+  nb.disp_limit = (1 << sh.disp) - 1;
+  nb.shard = 0; nb.n_shards = 0;   // (what is in the table is this shard's already)
+  nb.max_disp = (int32_t *)(d_scratch + 3);
+  nb.n_inserted = d_scratch; nb.n_duplicate = d_scratch + 1; nb.n_overflow = d_scratch + 2;
   auto insert_piece = [&](const int64_t *k, const int32_t *t, uint64_t n) -> int32_t {
-    TableBuild nb = build_view(ix);
-    nb.shard = 0; nb.n_shards = 0;   // (what is in the table is this shard's already)
-    nb.n_inserted = d_scratch; nb.n_duplicate = d_scratch + 1; nb.n_overflow = d_scratch + 2;
+    nb.cells = new_cells;
     launch_table_insert(nb, k, t, n, ix->build_stream);
     HIPCHK(hipGetLastError());
     return SLK_OK;
   };
   if (on_device) {
     HIPCHK(hipMemsetAsync(new_cells, 0, new_bytes, ix->build_stream));
-    HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), ix->build_stream));
-    adopt(new_cells);
     for (uint64_t b0 = 0; b0 < old_nb; b0 += CH) {
-      const uint64_t b1 = std::min(old_nb, b0 + CH);
       unsigned long long n = 0;
-      HIPCHK(hipMemsetAsync(dc.p, 0, 8, ix->build_stream));
-      launch_export_range(old_view, b0, b1, dk.as<int64_t>(), dt.as<int32_t>(), cap, dc.as<unsigned long long>(), ix->build_stream);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&n, dc.p, 8, hipMemcpyDeviceToHost, ix->build_stream));
-      HIPCHK(hipStreamSynchronize(ix->build_stream));
-      int32_t rc = insert_piece(dk.as<int64_t>(), dt.as<int32_t>(), n);
+      int32_t rc = export_piece(ix, old_view, b0, std::min(old_nb, b0 + CH), dk, dt, dc, cap, &n);
+      if (!rc) rc = insert_piece(dk.as<int64_t>(), dt.as<int32_t>(), n);
       if (rc) return rc;
     }
-    HIPCHK(hipStreamSynchronize(ix->build_stream));
-    HIPCHK(hipFree(old_cells));
   } else {
     // both tables do not fit the device: the records wait in host memory (12 bytes each) while the old table makes room
+    std::vector<int64_t> h_keys;
+    std::vector<int32_t> h_taxa;
     for (uint64_t b0 = 0; b0 < old_nb; b0 += CH) {
-      const uint64_t b1 = std::min(old_nb, b0 + CH);
       unsigned long long n = 0;
-      HIPCHK(hipMemsetAsync(dc.p, 0, 8, ix->build_stream));
-      launch_export_range(old_view, b0, b1, dk.as<int64_t>(), dt.as<int32_t>(), cap, dc.as<unsigned long long>(), ix->build_stream);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&n, dc.p, 8, hipMemcpyDeviceToHost, ix->build_stream));
-      HIPCHK(hipStreamSynchronize(ix->build_stream));
+      int32_t rc = export_piece(ix, old_view, b0, std::min(old_nb, b0 + CH), dk, dt, dc, cap, &n);
+      if (rc) return rc;
       const size_t at = h_keys.size();
       h_keys.resize(at + n); h_taxa.resize(at + n);
       if (n) {
@@ -307,17 +311,14 @@ static int32_t grow_table(slk_index *ix) {
         HIPCHK(hipMemcpy(h_taxa.data() + at, dt.p, n * 4, hipMemcpyDeviceToHost));
       }
     }
-    HIPCHK(hipFree(old_cells));
-    ix->cells = nullptr;
-    if (hipMalloc((void **)&new_cells, new_bytes) != hipSuccess) {
+    ix->spent = true;   // (until the new table is adopted, below: the records are in h_keys / h_taxa only)
+    ix->cells.reset();
+    if (hipMalloc((void **)new_cells.put(), new_bytes) != hipSuccess) {
       (void)hipGetLastError();
-      (void)hipFree(d_scratch);
       return fail(SLK_E_HIP, "hipMalloc of %zu table bytes failed while the table was growing (the records are lost: load the library again "
                   "with a larger slk_table_config.expected_records)", new_bytes);
     }
     HIPCHK(hipMemsetAsync(new_cells, 0, new_bytes, ix->build_stream));
-    HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), ix->build_stream));
-    adopt(new_cells);
     for (uint64_t o = 0; o < h_keys.size(); o += cap) {
       const uint64_t n = std::min<uint64_t>(cap, h_keys.size() - o);
       HIPCHK(hipMemcpyAsync(dk.p, h_keys.data() + o, n * 8, hipMemcpyHostToDevice, ix->build_stream));
@@ -328,10 +329,13 @@ static int32_t grow_table(slk_index *ix) {
     }
   }
   unsigned long long c[3] = {0, 0, 0};
+  HIPCHK(hipStreamSynchronize(ix->build_stream));
   HIPCHK(hipMemcpy(c, d_scratch, sizeof(c), hipMemcpyDeviceToHost));
-  (void)hipFree(d_scratch);
-  dk.release(); dt.release(); dc.release();
   if (c[2] != 0 || c[1] != 0) return fail(SLK_E_HIP, "moving the table to a larger one lost records (%llu unplaced, %llu collided)", c[2], c[1]);
+  HIPCHK(hipMemcpy(ix->d_max_disp, d_scratch + 3, sizeof(int32_t), hipMemcpyDeviceToDevice));
+  ix->cells = std::move(new_cells);   // (the old table, if it is still there, is freed here)
+  ix->nbuckets = sh.nb; ix->bucket_bits = sh.q; ix->disp_bits = sh.disp; ix->bucket_flag = sh.flag;
+  ix->spent = false;
   ix->grown++;
   static const bool verbose = getenv("SLK_DEBUG_GROW") != nullptr;
   if (verbose) fprintf(stderr, "[slk] table grown to %llu buckets (%d displacement bits), %llu records moved %s\n", (unsigned long long)sh.nb, sh.disp,
@@ -381,6 +385,7 @@ static int32_t insert_growing(slk_index *ix, bool counts_dups, const std::functi
 // so that every rank can be handed the same record stream or the same genomes.  Before the first record.
 int32_t slk_index_set_shard(slk_index *ix, uint32_t shard, uint32_t n_shards) {
   if (!ix) return fail(SLK_E_INVALID, "null argument");
+  if (ix->spent) return check_spent(ix);
   if (n_shards < 1 || n_shards > 64 || shard >= n_shards) return fail(SLK_E_INVALID, "shard %u of %u", shard, n_shards);
   if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "the sharded entry points support minimizers of up to 32 nt (one id column)");
   if (ix->finalized || ix->records != 0) return fail(SLK_E_STATE, "slk_index_set_shard must precede the first record");
@@ -456,8 +461,8 @@ int32_t slk_index_append(slk_index *ix, const int64_t *keys, const int32_t *taxa
 // of b" (Taxonomy.hasAncestor, Taxonomy.scala:236-244) is tin[a] <= tin[b] <= tout[a] -- two compares on values that are loaded
 // once per taxon of a read's map -- instead of a walk of b's root path: NCBI lineages are 25-40 nodes deep, and resolveTree
 // (LowestCommonAncestor.scala:101-146) asks it for every pair of map taxa and again at every step of the confidence walk.
-static int32_t build_tax_nodes(const int32_t *parents, int32_t n, int32_t max_n, uint4 **out) {
-  *out = nullptr;
+static int32_t build_tax_nodes(const int32_t *parents, int32_t n, int32_t max_n, DevPtr<uint4> &out) {
+  out.reset();
   if (n < 2 || n > max_n) return SLK_OK;
   std::vector<uint32_t> first((size_t)n + 1, 0), kids;   // children of p: kids[first[p] .. first[p + 1]), in increasing id order
   for (int32_t t = 1; t < n; t++) if (parents[t] != 0) first[(size_t)parents[t] + 1]++;
@@ -487,14 +492,9 @@ static int32_t build_tax_nodes(const int32_t *parents, int32_t n, int32_t max_n,
       }
     }
   }
-  HIPCHK(hipMalloc((void **)out, (size_t)n * sizeof(uint4)));
-  HIPCHK(hipMemcpy(*out, nodes.data(), (size_t)n * sizeof(uint4), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc((void **)out.put(), (size_t)n * sizeof(uint4)));
+  HIPCHK(hipMemcpy(out, nodes.data(), (size_t)n * sizeof(uint4), hipMemcpyHostToDevice));
   return SLK_OK;
-}
-static void free_tax_nodes(slk_index *ix) {
-  if (ix->d_nodes_orig && ix->d_nodes_orig != ix->d_nodes) (void)hipFree(ix->d_nodes_orig);
-  if (ix->d_nodes) (void)hipFree(ix->d_nodes);
-  ix->d_nodes = ix->d_nodes_orig = nullptr;
 }
 
 int32_t slk_index_set_taxonomy(slk_index *ix, const int32_t *parents, int32_t T) {
@@ -519,18 +519,17 @@ int32_t slk_index_set_taxonomy(slk_index *ix, const int32_t *parents, int32_t T)
     }
   }
   if (ix->D) return fail(SLK_E_STATE, "this finalized index stores dense taxon ids derived from its taxonomy: the taxonomy cannot be replaced");
-  if (ix->d_parents) { HIPCHK(hipFree(ix->d_parents)); ix->d_parents = nullptr; }
-  HIPCHK(hipMalloc((void **)&ix->d_parents, (size_t)T * sizeof(int32_t)));
+  HIPCHK(hipMalloc((void **)ix->d_parents.put(), (size_t)T * sizeof(int32_t)));
   HIPCHK(hipMemcpy(ix->d_parents, parents, (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice));
   ix->T = T;
   ix->h_parents.assign(parents, parents + T);
   // Euler tours: for the fused kernels (ids of at most 22 bits take the lane kernel; wider ones are renumbered at finalize, which
   // builds that tour then) and, in the caller's ids, for the staged classify kernel (up to 2^26 ids: 1 GiB of node records)
-  free_tax_nodes(ix);
-  int32_t rcn = build_tax_nodes(parents, T, (1 << 22) + 1, &ix->d_nodes);
-  if (rcn) return rcn;
-  if (ix->d_nodes) { ix->d_nodes_orig = ix->d_nodes; return SLK_OK; }
-  return build_tax_nodes(parents, T, 1 << 26, &ix->d_nodes_orig);
+  ix->d_nodes = nullptr;
+  rc = build_tax_nodes(parents, T, 1 << 26, ix->d_nodes_orig);
+  if (rc) return rc;
+  if (T <= (1 << 22) + 1) ix->d_nodes = ix->d_nodes_orig;   // (one tour serves both)
+  return SLK_OK;
 }
 
 // Library construction with several id columns (minimizers of 33..128 nt): the staged kernels of wide.hip.  Groups of about 64 MiB
@@ -591,7 +590,6 @@ static int32_t add_sequences_wide(slk_index *ix, const uint8_t *bases, const uin
   }
   int32_t rc = flush();
   if (rc) return rc;
-  d_bases.release(); d_off.release(); d_tax.release(); d_keys.release(); d_meta.release(); d_count.release();
   return read_build_counters(ix);
 }
 
@@ -662,7 +660,6 @@ static int32_t add_sequences(slk_index *ix, const uint8_t *bases, const uint64_t
     }
     i = j;
   }
-  d_bases.release(); d_start.release(); d_len.release(); d_tax.release();
   return read_build_counters(ix);
 }
 
@@ -678,7 +675,8 @@ int32_t slk_index_add_sequences_device(slk_index *ix, const uint8_t *d_bases, co
 
 int32_t slk_index_export(const slk_index *ix, int64_t *keys, int32_t *taxa, uint64_t capacity, uint64_t *n_records) {
   if (!ix || !n_records || (capacity && (!keys || !taxa))) return fail(SLK_E_INVALID, "null argument");
-  (void)hipSetDevice(ix->device);
+  int32_t rc = set_device(ix);
+  if (rc) return rc;
   DevBuf dk, dt, dc;
   HIPCHK(dk.ensure(std::max<uint64_t>(capacity, 1) * 8 * ix->W));
   HIPCHK(dt.ensure(std::max<uint64_t>(capacity, 1) * 4));
@@ -699,7 +697,6 @@ int32_t slk_index_export(const slk_index *ix, int64_t *keys, int32_t *taxa, uint
     HIPCHK(hipMemcpy(keys, dk.p, got * 8 * ix->W, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(taxa, dt.p, got * 4, hipMemcpyDeviceToHost));
   }
-  dk.release(); dt.release(); dc.release();
   if (n > capacity && capacity) return fail(SLK_E_CAPACITY, "%llu records, capacity %llu", n, (unsigned long long)capacity);
   return SLK_OK;
 }
@@ -721,32 +718,30 @@ static int32_t make_dense_taxa(slk_index *ix) {
   if (D < 1 || D >= (1 << 22)) return SLK_OK;
   std::vector<int32_t> pd((size_t)D + 1, 0);
   for (int32_t d = 1; d <= D; d++) pd[d] = to_dense[ix->h_parents[to_orig[d]]];  // (parent of ROOT is NONE = 0)
-  int32_t *d_td = nullptr, *d_to = nullptr, *d_pd = nullptr;
-  unsigned long long *d_bad = nullptr, bad = 0;
-  HIPCHK(hipMalloc((void **)&d_td, (size_t)T * 4));
-  HIPCHK(hipMalloc((void **)&d_bad, 8));
+  DevPtr<int32_t> d_td, d_to, d_pd;
+  DevPtr<unsigned long long> d_bad;
+  unsigned long long bad = 0;
+  HIPCHK(hipMalloc((void **)d_td.put(), (size_t)T * 4));
+  HIPCHK(hipMalloc((void **)d_bad.put(), 8));
   HIPCHK(hipMemcpy(d_td, to_dense.data(), (size_t)T * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemset(d_bad, 0, 8));
   launch_remap_cells(ix->cells, ix->nbuckets * CELLS, ix->taxon_bits, d_td, T, d_bad, false, ix->build_stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ix->build_stream));
   HIPCHK(hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost));
-  if (bad != 0) {  // records whose taxon is not a node of this taxonomy: keep the ids as they are
-    (void)hipFree(d_td); (void)hipFree(d_bad);
-    return SLK_OK;
-  }
+  if (bad != 0) return SLK_OK;  // records whose taxon is not a node of this taxonomy: keep the ids as they are
   launch_remap_cells(ix->cells, ix->nbuckets * CELLS, ix->taxon_bits, d_td, T, d_bad, true, ix->build_stream);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(ix->build_stream));
-  (void)hipFree(d_bad);
-  HIPCHK(hipMalloc((void **)&d_to, ((size_t)D + 1) * 4));
-  HIPCHK(hipMalloc((void **)&d_pd, ((size_t)D + 1) * 4));
+  HIPCHK(hipMalloc((void **)d_to.put(), ((size_t)D + 1) * 4));
+  HIPCHK(hipMalloc((void **)d_pd.put(), ((size_t)D + 1) * 4));
   HIPCHK(hipMemcpy(d_to, to_orig.data(), ((size_t)D + 1) * 4, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_pd, pd.data(), ((size_t)D + 1) * 4, hipMemcpyHostToDevice));
-  ix->d_to_dense = d_td; ix->d_to_orig = d_to; ix->d_parents_dense = d_pd; ix->D = D;
-  if (ix->d_nodes && ix->d_nodes != ix->d_nodes_orig) (void)hipFree(ix->d_nodes);
-  if (ix->d_nodes == ix->d_nodes_orig) ix->d_nodes = nullptr;   // (the tour of the ids as given stays with the staged kernel)
-  return build_tax_nodes(pd.data(), D + 1, (1 << 22) + 1, &ix->d_nodes);
+  ix->d_to_dense = std::move(d_td); ix->d_to_orig = std::move(d_to); ix->d_parents_dense = std::move(d_pd); ix->D = D;
+  ix->d_nodes = nullptr;   // (the tour of the ids as given stays with the staged kernel)
+  const int32_t rc = build_tax_nodes(pd.data(), D + 1, (1 << 22) + 1, ix->d_nodes_dense);
+  ix->d_nodes = ix->d_nodes_dense;
+  return rc;
 }
 
 int32_t slk_index_finalize(slk_index *ix) {
@@ -769,6 +764,7 @@ int32_t slk_index_finalize(slk_index *ix) {
 int32_t slk_index_get_info(const slk_index *ix, slk_index_info *out) {
   if (!ix || !out) return fail(SLK_E_INVALID, "null argument");
   memset(out, 0, sizeof(*out));
+  if (ix->spent) return check_spent(ix);
   out->records = ix->records;
   out->buckets = ix->nbuckets;
   out->table_bytes = ix->W > 1 ? ix->nbuckets * (8 * ix->W + 4) : ix->nbuckets * CELLS * 8;
@@ -800,28 +796,12 @@ int32_t slk_index_lookup(const slk_index *ix, const int64_t *keys, uint64_t n, i
   else launch_table_lookup(ix->view(), k.as<int64_t>(), n, o.as<int32_t>(), nullptr);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpy(out_taxa, o.p, n * 4, hipMemcpyDeviceToHost));
-  k.release();
-  o.release();
   return SLK_OK;
 }
 
 void slk_index_destroy(slk_index *ix) {
   if (!ix) return;
   (void)hipSetDevice(ix->device);
-  if (ix->cells) (void)hipFree(ix->cells);
-  if (ix->wt.keys) (void)hipFree(ix->wt.keys);
-  if (ix->wt.taxa) (void)hipFree(ix->wt.taxa);
-  if (ix->d_max_disp) (void)hipFree(ix->d_max_disp);
-  if (ix->d_counters) (void)hipFree(ix->d_counters);
-  if (ix->d_parents) (void)hipFree(ix->d_parents);
-  if (ix->d_parents_dense) (void)hipFree(ix->d_parents_dense);
-  free_tax_nodes(ix);
-  if (ix->d_to_orig) (void)hipFree(ix->d_to_orig);
-  if (ix->d_to_dense) (void)hipFree(ix->d_to_dense);
-  ix->stage_keys.release();
-  ix->stage_taxa.release();
-  ix->staging.release();
-  if (ix->build_stream) (void)hipStreamDestroy(ix->build_stream);
   delete ix;
 }
 
@@ -830,16 +810,16 @@ int32_t slk_stream_create(slk_index *ix, slk_stream **out) {
   *out = nullptr;
   int32_t rc = set_device(ix);
   if (rc) return rc;
-  slk_stream *st = new slk_stream();
+  std::unique_ptr<slk_stream> st(new slk_stream());   // (released into *out on success only)
   st->ix = ix;
   st->device = ix->device;
-  HIPCHK(hipStreamCreate(&st->s));
-  for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(&st->ev[i]));
-  HIPCHK(hipMalloc((void **)&st->d_status, sizeof(int32_t)));
+  HIPCHK(hipStreamCreate(st->s.put()));
+  for (int i = 0; i < 4; i++) HIPCHK(hipEventCreate(st->ev[i].put()));
+  HIPCHK(hipMalloc((void **)st->d_status.put(), sizeof(int32_t)));
   HIPCHK(hipMemset(st->d_status, 0, sizeof(int32_t)));
-  HIPCHK(hipHostMalloc((void **)&st->h_status, sizeof(int32_t), hipHostMallocDefault));
+  HIPCHK(hipHostMalloc((void **)st->h_status.put(), sizeof(int32_t), hipHostMallocDefault));
   *st->h_status = 0;
-  *out = st;
+  *out = st.release();
   return SLK_OK;
 }
 
@@ -861,35 +841,17 @@ void *slk_stream_hip_stream(slk_stream *st) { return st ? (void *)st->s : nullpt
 void slk_stream_destroy(slk_stream *st) {
   if (!st) return;
   (void)hipSetDevice(st->device);
-  (void)hipStreamSynchronize(st->s);
-  DevBuf *bufs[] = {&st->span_keys, &st->span_meta, &st->span_taxon, &st->span_count, &st->bases, &st->offsets,
-                    &st->mate_bases, &st->mate_offsets, &st->out_taxon, &st->out_cls, &st->out_nd, &st->out_tk,
-                    &st->out_nh, &st->out_offsets, &st->out_items, &st->defer_list, &st->scan_tmp, &st->pk_codes, &st->pk_valid, &st->pk_mate_codes,
-                    &st->pk_mate_valid};
-  for (DevBuf *b : bufs) b->release();
-  if (st->d_status) (void)hipFree(st->d_status);
-  if (st->h_status) (void)hipHostFree(st->h_status);
-  st->staging.release();
-  st->staging_c.release();
-  for (hipEvent_t e : st->up_ev) (void)hipEventDestroy(e);
-  for (hipEvent_t e : st->dn_ev) (void)hipEventDestroy(e);
-  if (st->cs) (void)hipStreamDestroy(st->cs);
-  if (st->ds) { (void)hipStreamSynchronize(st->ds); (void)hipStreamDestroy(st->ds); }
-  if (st->s2) { (void)hipStreamSynchronize(st->s2); (void)hipStreamDestroy(st->s2); }
-  if (st->ev_unpack) (void)hipEventDestroy(st->ev_unpack);
-  if (st->ev_fork) (void)hipEventDestroy(st->ev_fork);
-  if (st->ev_join) (void)hipEventDestroy(st->ev_join);
-  for (int i = 0; i < 4; i++) if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
-  if (st->s) (void)hipStreamDestroy(st->s);
+  for (hipStream_t s : {st->s.get(), st->ds.get(), st->s2.get()})
+    if (s) (void)hipStreamSynchronize(s);
   delete st;
 }
 
 // span slots needed by a batch (see span_region in engine.h)
-uint64_t span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired) {
+uint64_t slk::span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired) {
   return total_bases + (paired ? total_mate_bases + R : 0) + 1;
 }
 
-int32_t ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R) {
+int32_t slk::ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R) {
   HIPCHK(st->span_keys.ensure(slots * 8 * st->ix->W));
   HIPCHK(st->span_meta.ensure(slots * 4));
   HIPCHK(st->span_taxon.ensure(slots * 4));
@@ -897,7 +859,7 @@ int32_t ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R) {
   return SLK_OK;
 }
 
-int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax) {
+int32_t slk::check_ready(const slk_index *ix, const slk_stream *st, bool need_tax) {
   if (!ix || !st) return fail(SLK_E_INVALID, "null handle");
   if (st->ix != ix) return fail(SLK_E_INVALID, "stream belongs to a different index");
   if (!ix->finalized) return fail(SLK_E_STATE, "index is not finalized");
@@ -908,12 +870,12 @@ int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax) {
 // The fused wave-per-read kernels (fused.hip) cover windows of up to 32 m-mers; wider windows (and SLK_FORCE_V1=1, an
 // A/B switch for tests) run the three separate lane-per-read kernels of kernels.hip.  Both are HIP: no CPU path.
 static bool use_fused(const slk_index *ix) {
-  static const bool force_v1 = getenv("SLK_FORCE_V1") != nullptr && getenv("SLK_FORCE_V1")[0] == '1';
+  static const bool force_v1 = env_on("SLK_FORCE_V1");
   return !force_v1 && ix->W == 1 && ix->sp.w <= 32;
 }
 
 static bool force_wave() {  // SLK_FORCE_WAVE=1: A/B switch, classify with the wave-per-read kernel only
-  static const bool v = getenv("SLK_FORCE_WAVE") != nullptr && getenv("SLK_FORCE_WAVE")[0] == '1';
+  static const bool v = env_on("SLK_FORCE_WAVE");
   return v;
 }
 
@@ -922,25 +884,24 @@ static bool force_wave() {  // SLK_FORCE_WAVE=1: A/B switch, classify with the w
 // distinct taxa than that (long reads across conserved regions can) raises status bit 1; the batch is then classified again
 // by the staged kernels, whose per-fragment map lives in HBM scratch and is unbounded -- the same three kernels that serve
 // windows wider than 32 m-mers.  Slower (HBM intermediates), rare, and bit-identical for every other fragment.
-static int32_t run_unbounded(slk_stream *st, const slk_stream::LastCall &L) {
+static int32_t run_unbounded(slk_stream *st, const ClassifyCall &c) {
   slk_index *ix = st->ix;
-  const bool paired = L.mate_bases != nullptr;
-  int32_t rc = ensure_scratch(st, span_slots(L.total, L.mate_total, L.R, paired) + L.span_shift, L.R);
+  const Reads &in = c.in;
+  int32_t rc = ensure_scratch(st, span_slots(in.total, in.mate_total, in.R, in.paired()) + c.span_shift, in.R);
   if (rc) return rc;
-  uint64_t *const keys = st->span_keys.as<uint64_t>() + L.span_shift;   // (fused path only: one key word per span)
-  int32_t *const meta = st->span_meta.as<int32_t>() + L.span_shift, *const taxa = st->span_taxon.as<int32_t>() + L.span_shift;
-  launch_scan(ix->sp, L.bases, L.offsets, L.mate_bases, L.mate_offsets, L.R, keys, meta, st->span_count.as<int32_t>(), st->s);
-  launch_probe(ix->view(), L.offsets, L.mate_offsets, L.R, keys, meta, st->span_count.as<int32_t>(), taxa, st->s);
-  launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, L.offsets, L.mate_offsets, L.R, meta, taxa, st->span_count.as<int32_t>(), keys,
-                  L.min_hit_groups, L.thr, L.C, L.out_stride, L.out_taxon, L.out_cls, L.out_nd, L.out_tk, L.out_nh, L.out_np, st->s);
+  uint64_t *const keys = st->span_keys.as<uint64_t>() + c.span_shift;   // (fused path only: one key word per span)
+  int32_t *const meta = st->span_meta.as<int32_t>() + c.span_shift, *const taxa = st->span_taxon.as<int32_t>() + c.span_shift;
+  launch_scan(ix->sp, in.bases, in.offsets, in.mate_bases, in.mate_offsets, in.R, keys, meta, st->span_count.as<int32_t>(), st->s);
+  launch_probe(ix->view(), in.offsets, in.mate_offsets, in.R, keys, meta, st->span_count.as<int32_t>(), taxa, st->s);
+  launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, c, meta, taxa, st->span_count.as<int32_t>(), keys, st->s);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st->s));
   return SLK_OK;
 }
 
-int32_t check_status(slk_stream *st) {  // call after the stream has been synchronised
+int32_t slk::check_status(slk_stream *st) {
   int32_t v = *st->h_status;
-  std::vector<slk_stream::LastCall> queued;
+  std::vector<slk_stream::Queued> queued;
   queued.swap(st->queued);
   if (v != 0) {
     *st->h_status = 0;
@@ -949,9 +910,9 @@ int32_t check_status(slk_stream *st) {  // call after the stream has been synchr
       // Some queued batch held a fragment with more distinct taxa than the LDS maps take.  The status word does not say
       // which, so every batch queued since the last synchronisation is classified again by the unbounded kernels, in
       // order (callers that reuse their output buffers from call to call end up with the last call's results, as before).
-      for (const slk_stream::LastCall &L : queued) {
-        if (!L.valid) return fail(SLK_E_CAPACITY, "a fragment hit more than %d distinct taxa; the per-read taxon map overflowed", 128);
-        int32_t rc = run_unbounded(st, L);
+      for (const slk_stream::Queued &q : queued) {
+        if (!q.valid) return fail(SLK_E_CAPACITY, "a fragment hit more than %d distinct taxa; the per-read taxon map overflowed", 128);
+        int32_t rc = run_unbounded(st, q.call);
         if (rc) return rc;
       }
       st->reran = true;
@@ -964,61 +925,62 @@ int32_t check_status(slk_stream *st) {  // call after the stream has been synchr
   return SLK_OK;
 }
 
-bool lane_path_ok(const slk_index *ix) {
+bool slk::lane_path_ok(const slk_index *ix) {
   return use_fused(ix) && ix->sp.w <= 32 && ix->internal_taxon_bits() <= 22 && ix->d_nodes != nullptr;
 }
 
-static int32_t run_classify(slk_index *ix, slk_stream *st, const uint8_t *d_bases, const uint64_t *d_offsets,
-                            const uint8_t *d_mate_bases, const uint64_t *d_mate_offsets, uint64_t R,
-                            uint64_t total_bases, uint64_t total_mate_bases, int32_t min_hit_groups,
-                            const double *thresholds, int32_t C, int32_t *d_out_taxon, uint8_t *d_out_classified,
-                            int32_t *d_out_num_distinct, int32_t *d_out_total_kmers, int32_t *d_out_num_hits,
-                            int32_t *d_out_num_probes, bool want_hits, uint64_t out_stride = 0, uint64_t span_shift = 0) {
-  // span_shift (a sub-batch of a larger host call, hit lists wanted): its fragments' span regions are addressed by their ABSOLUTE
-  // offsets but by the fragment's number INSIDE the sub-batch (span_region: offsets[r] + mate_offsets[r] + r for pairs), so the
-  // arrays are handed over moved by the sub-batch's first fragment number -- the regions then are the ones the whole batch has,
-  // and sub-batches do not overlap.  The caller has sized the scratch for the whole batch.
-  if (out_stride == 0) out_stride = R;
-  bool paired = d_mate_bases != nullptr;
+// the second stream of a classify call or a sharded step, and the two events that fork it from s and join it again
+static int32_t fork_ready(slk_stream *st) {
+  if (st->ev_join) return SLK_OK;
+  HIPCHK(hipStreamCreateWithFlags(st->s2.put(), hipStreamNonBlocking));
+  HIPCHK(hipEventCreateWithFlags(st->ev_fork.put(), hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(st->ev_join.put(), hipEventDisableTiming));
+  return SLK_OK;
+}
+
+// the part of FusedArgs every job shares: the splitter, the table, the taxonomy in the table's ids, the reads, the status word
+static FusedArgs fused_args(const slk_index *ix, const slk_stream *st, const Reads &in) {
+  FusedArgs A{};
+  A.P = ix->sp; A.T = ix->view(); A.parents = ix->kernel_parents(); A.ntax = ix->kernel_ntax(); A.nodes = ix->kernel_nodes();
+  A.bases = in.bases; A.offsets = in.offsets; A.mate_bases = in.mate_bases; A.mate_offsets = in.mate_offsets; A.R = in.R;
+  A.status = st->d_status;
+  return A;
+}
+static Thresholds thresholds_of(const double *v, int32_t C) {
+  Thresholds thr{};
+  memcpy(thr.v, v, C * sizeof(double));
+  return thr;
+}
+
+static int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call) {
+  ClassifyCall c = call;
+  if (c.out.stride == 0) c.out.stride = c.in.R;
+  const Reads &in = c.in;
+  const uint64_t R = in.R, span_shift = c.span_shift, all_bases = in.total + in.mate_total;
+  const bool paired = in.paired(), want_hits = c.want_hits;
   bool fused = use_fused(ix);
   int32_t rc;
   st->last_used_lane = false;
   if (!fused || want_hits) {
-    rc = ensure_scratch(st, span_slots(total_bases, total_mate_bases, R, paired) + span_shift, R);
+    rc = ensure_scratch(st, span_slots(in.total, in.mate_total, R, paired) + span_shift, R);
     if (rc) return rc;
   }
-  Thresholds thr{};
-  memcpy(thr.v, thresholds, C * sizeof(double));
   HIPCHK(hipEventRecord(st->ev[0], st->s));
-  {
-    if (st->queued.size() >= 4096) {  // (a caller that never synchronises: settle what is queued before taking more)
-      HIPCHK(hipStreamSynchronize(st->s));
-      rc = check_status(st);
-      if (rc) return rc;
-    }
-    st->queued.emplace_back();
-    slk_stream::LastCall &L = st->queued.back();
-    L.valid = fused; L.want_hits = want_hits; L.thr = thr;
-    L.bases = d_bases; L.offsets = d_offsets; L.mate_bases = d_mate_bases; L.mate_offsets = d_mate_offsets;
-    L.R = R; L.total = total_bases; L.mate_total = total_mate_bases; L.min_hit_groups = min_hit_groups; L.C = C;
-    L.out_stride = out_stride; L.span_shift = span_shift;
-    L.out_taxon = d_out_taxon; L.out_cls = d_out_classified; L.out_nd = d_out_num_distinct; L.out_tk = d_out_total_kmers;
-    L.out_nh = d_out_num_hits; L.out_np = d_out_num_probes;
+  if (st->queued.size() >= 4096) {  // (a caller that never synchronises: settle what is queued before taking more)
+    HIPCHK(hipStreamSynchronize(st->s));
+    rc = check_status(st);
+    if (rc) return rc;
   }
+  st->queued.push_back({c, fused});
   if (fused) {
-    FusedArgs A{};
-    A.P = ix->sp; A.T = ix->view(); A.parents = ix->kernel_parents(); A.ntax = ix->kernel_ntax(); A.nodes = ix->kernel_nodes();
-    A.bases = d_bases; A.offsets = d_offsets; A.mate_bases = d_mate_bases; A.mate_offsets = d_mate_offsets; A.R = R;
-    A.out_stride = out_stride;
-    A.min_hit_groups = min_hit_groups; A.thr = thr; A.C = C;
-    A.out_taxon = d_out_taxon; A.out_classified = d_out_classified;
-    A.out_nd = d_out_num_distinct; A.out_tk = d_out_total_kmers; A.out_nh = d_out_num_hits; A.out_np = d_out_num_probes;
-    A.span_keys = nullptr;
+    FusedArgs A = fused_args(ix, st, in);
+    A.out_stride = c.out.stride;
+    A.min_hit_groups = c.min_hit_groups; A.thr = c.thr; A.C = c.C;
+    A.out_taxon = c.out.taxon; A.out_classified = c.out.classified;
+    A.out_nd = c.out.nd; A.out_tk = c.out.tk; A.out_nh = c.out.nh; A.out_np = c.out.np;
     A.span_meta = want_hits ? st->span_meta.as<int32_t>() + span_shift : nullptr;
     A.span_taxon = want_hits ? st->span_taxon.as<int32_t>() + span_shift : nullptr;
     A.span_count = want_hits ? st->span_count.as<int32_t>() : nullptr;
-    A.status = st->d_status;
-    A.work_list = nullptr; A.work_count = nullptr; A.work_draw = nullptr;
     if (lane_path_ok(ix) && !force_wave() && R < 0xFFFFFFFFull) {  // (window of at most 32 m-mers, taxon ids of at most 22 bits)
       st->last_used_lane = true;
       // Hot path: one lane per fragment.  What that kernel does not take -- fragments over 1000 bases, taxon maps that overflow --
@@ -1026,14 +988,13 @@ static int32_t run_classify(slk_index *ix, slk_stream *st, const uint8_t *d_base
       // variant (1001 .. 4999 bases), the lane-per-segment kernel (unpaired, w = 5, the fragments that are long for their batch), the
       // wave-per-fragment kernel (the rest, and what the long variant hands on in turn).
       const size_t hdr_bytes = HandOn::WORDS * sizeof(uint64_t);
-      const uint64_t long_cap = std::min<uint64_t>(R, (total_bases + total_mate_bases) / 1001 + 1);
+      const uint64_t long_cap = std::min<uint64_t>(R, all_bases / 1001 + 1);
       // SLK_LANE_LONG_MAX moves the long variant's limit (at most 8191: queue entries carry 13-bit k-mer counts; 0: no such pass)
-      const char *long_env = getenv("SLK_LANE_LONG_MAX");
-      const int long_max = std::min(long_env ? atoi(long_env) : 4999, 8191);
+      const int long_max = (int)std::min(env_long("SLK_LANE_LONG_MAX", 4999), 8191L);
       // A batch whose fragments average more than 1000 bases gets a routing kernel instead of a first pass (engine.h:
       // FusedArgs.hand_short; SLK_ROUTE_FIRST=0 / 1 says so either way)
       const char *route_env = getenv("SLK_ROUTE_FIRST");
-      const bool route_first = long_max > 1000 && (route_env ? route_env[0] == '1' : (total_bases + total_mate_bases) / 1000 > R);
+      const bool route_first = long_max > 1000 && (route_env ? route_env[0] == '1' : all_bases / 1000 > R);
       HIPCHK(st->defer_list.ensure(hdr_bytes + HandOn::entries(R, long_cap, route_first) * sizeof(uint32_t)));
       HIPCHK(hipMemsetAsync(st->defer_list.p, 0, hdr_bytes, st->s));
       A.hand_hdr = (unsigned long long *)st->defer_list.p;
@@ -1051,15 +1012,12 @@ static int32_t run_classify(slk_index *ix, slk_stream *st, const uint8_t *d_base
       // that its lanes have too little each) and always from 250 000; and the wave kernel starts its long fragments longest first
       // (engine.h: hand_hdr).  Nanopore-like mix, 200 .. 50 000 bases, 1 Gbp: 90-94 Gbp/s with the threshold at 12-16 000, 93-99 at
       // 30 000, 97-101 at 64 000 (none on the segment kernel).
-      const char *seg_env = getenv("SLK_SEG_MIN_LEN");
-      const uint64_t seg_auto = std::min<uint64_t>(250000, std::max<uint64_t>(16000, (total_bases + total_mate_bases) >> 14));
-      const int seg_min = seg_env ? atoi(seg_env) : (int)seg_auto;
+      const uint64_t seg_auto = std::min<uint64_t>(250000, std::max<uint64_t>(16000, all_bases >> 14));
+      const int seg_min = (int)env_long("SLK_SEG_MIN_LEN", (long)seg_auto);
       // (hit lists: the segment kernel can put them together -- SLK_SEG_HITS=1 --, but the queues that take its spans to memory
       //  in order cost it half its resident waves, and it measured 51-53 Gbp/s against the wave kernel's 68-79 on the same reads:
       //  profiles/r03_long_hits_*.json; so per-read lines of long reads keep the wave kernel unless asked otherwise)
-      const char *seg_hits_env = getenv("SLK_SEG_HITS");
-      const bool seg_hits = seg_hits_env != nullptr && seg_hits_env[0] == '1';
-      const bool seg_on = (!want_hits || seg_hits) && !paired && ix->sp.w == 5 && seg_min > 0;
+      const bool seg_on = (!want_hits || env_on("SLK_SEG_HITS")) && !paired && ix->sp.w == 5 && seg_min > 0;
       A.long_max = long_max > 1000 ? (uint32_t)long_max : 0;
       if (A.long_max) {  // class borders: a geometric ladder from 1000 to the limit (a tile's lanes then differ by at most ~1.5x)
         const double ratio = pow((double)A.long_max / 1000.0, 0.25);
@@ -1078,11 +1036,8 @@ static int32_t run_classify(slk_index *ix, slk_stream *st, const uint8_t *d_base
       // every wave slot until it is through, the other two are chains of dependent steps that share a CU well.  What the long
       // variant hands on in turn (map overflows) goes to a list of its own that a second launch of the wave kernel takes when
       // both streams are through.
-      if (!st->s2) {
-        HIPCHK(hipStreamCreateWithFlags(&st->s2, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&st->ev_fork, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&st->ev_join, hipEventDisableTiming));
-      }
+      rc = fork_ready(st);
+      if (rc) return rc;
       HIPCHK(hipEventRecord(st->ev_fork, st->s));
       if (A.long_max) launch_lane_long(A, A.long_max, st->s);   // (first: its chain of steps is the longest, whoever comes first gets the CUs)
       HIPCHK(hipStreamWaitEvent(st->s2, st->ev_fork, 0));
@@ -1110,25 +1065,20 @@ static int32_t run_classify(slk_index *ix, slk_stream *st, const uint8_t *d_base
     HIPCHK(hipEventRecord(st->ev[1], st->s));
     HIPCHK(hipEventRecord(st->ev[2], st->s));
   } else {
+    uint64_t *const keys = st->span_keys.as<uint64_t>();
+    int32_t *const meta = st->span_meta.as<int32_t>(), *const taxa = st->span_taxon.as<int32_t>(), *const count = st->span_count.as<int32_t>();
     if (ix->W > 1) {
-      launch_wide_scan(ix->wp, d_bases, d_offsets, d_mate_bases, d_mate_offsets, R, st->span_keys.as<uint64_t>(),
-                       st->span_meta.as<int32_t>(), st->span_count.as<int32_t>(), st->s);
+      launch_wide_scan(ix->wp, in.bases, in.offsets, in.mate_bases, in.mate_offsets, R, keys, meta, count, st->s);
       HIPCHK(hipEventRecord(st->ev[1], st->s));
-      launch_wide_probe(ix->wt, ix->W, d_offsets, d_mate_offsets, R, st->span_keys.as<uint64_t>(), st->span_meta.as<int32_t>(),
-                        st->span_count.as<int32_t>(), st->span_taxon.as<int32_t>(), st->s);
+      launch_wide_probe(ix->wt, ix->W, in.offsets, in.mate_offsets, R, keys, meta, count, taxa, st->s);
     } else {
-      launch_scan(ix->sp, d_bases, d_offsets, d_mate_bases, d_mate_offsets, R, st->span_keys.as<uint64_t>(),
-                  st->span_meta.as<int32_t>(), st->span_count.as<int32_t>(), st->s);
+      launch_scan(ix->sp, in.bases, in.offsets, in.mate_bases, in.mate_offsets, R, keys, meta, count, st->s);
       HIPCHK(hipEventRecord(st->ev[1], st->s));
-      launch_probe(ix->view(), d_offsets, d_mate_offsets, R, st->span_keys.as<uint64_t>(), st->span_meta.as<int32_t>(),
-                   st->span_count.as<int32_t>(), st->span_taxon.as<int32_t>(), st->s);
+      launch_probe(ix->view(), in.offsets, in.mate_offsets, R, keys, meta, count, taxa, st->s);
     }
     HIPCHK(hipEventRecord(st->ev[2], st->s));
     // the key slots are dead after the probe: the per-read taxon->count map reuses them
-    launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, d_offsets, d_mate_offsets, R, st->span_meta.as<int32_t>(),
-                    st->span_taxon.as<int32_t>(), st->span_count.as<int32_t>(), st->span_keys.as<uint64_t>(),
-                    min_hit_groups, thr, C, out_stride, d_out_taxon, d_out_classified, d_out_num_distinct,
-                    d_out_total_kmers, d_out_num_hits, d_out_num_probes, st->s);
+    launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, c, meta, taxa, count, keys, st->s);
   }
   HIPCHK(hipEventRecord(st->ev[3], st->s));
   HIPCHK(hipMemcpyAsync(st->h_status, st->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, st->s));
@@ -1152,9 +1102,11 @@ int32_t slk_classify_batch_device(slk_index *ix, slk_stream *st, const uint8_t *
     return fail(SLK_E_INVALID, "mate_bases and mate_offsets must be given together");
   rc = set_device(ix);
   if (rc) return rc;
-  return run_classify(ix, st, d_bases, d_offsets, d_mate_bases, d_mate_offsets, R, total_bases, total_mate_bases,
-                      min_hit_groups, thresholds, C, d_out_taxon, d_out_classified, d_out_num_distinct,
-                      d_out_total_kmers, d_out_num_hits, d_out_num_probes, false);
+  ClassifyCall c;
+  c.in = {d_bases, d_offsets, d_mate_bases, d_mate_offsets, R, total_bases, total_mate_bases};
+  c.out = {d_out_taxon, d_out_classified, d_out_num_distinct, d_out_total_kmers, d_out_num_hits, d_out_num_probes, R};
+  c.thr = thresholds_of(thresholds, C); c.C = C; c.min_hit_groups = min_hit_groups;
+  return run_classify(ix, st, c);
 }
 
 int32_t slk_scan_device(slk_index *ix, slk_stream *st, const uint8_t *d_bases, const uint64_t *d_offsets,
@@ -1169,9 +1121,8 @@ int32_t slk_scan_device(slk_index *ix, slk_stream *st, const uint8_t *d_bases, c
   rc = set_device(ix);
   if (rc) return rc;
   if (use_fused(ix)) {
-    FusedArgs A{};
-    A.P = ix->sp; A.bases = d_bases; A.offsets = d_offsets; A.mate_bases = d_mate_bases; A.mate_offsets = d_mate_offsets;
-    A.R = R; A.span_keys = d_span_keys; A.span_meta = d_span_meta; A.span_count = d_span_count; A.status = st->d_status;
+    FusedArgs A = fused_args(ix, st, {d_bases, d_offsets, d_mate_bases, d_mate_offsets, R});
+    A.span_keys = d_span_keys; A.span_meta = d_span_meta; A.span_count = d_span_count;
     launch_fused(MODE_SPANS, A, st->s);
   } else {
     launch_scan(ix->sp, d_bases, d_offsets, d_mate_bases, d_mate_offsets, R, d_span_keys, d_span_meta, d_span_count, st->s);
@@ -1232,10 +1183,8 @@ uint32_t slk_shard_chunk(uint32_t n_shards) {
 
 // FusedArgs / ShardIO of a batch's EMIT job from its lists
 static void fill_emit(const slk_index *ix, slk_stream *st, const slk_shard_lists &E, FusedArgs &A, ShardIO &S) {
-  A.P = ix->sp; A.T = ix->view();
-  A.bases = E.d_bases; A.offsets = E.d_offsets; A.mate_bases = E.d_mate_bases; A.mate_offsets = E.d_mate_offsets; A.R = E.R;
+  A = fused_args(ix, st, {E.d_bases, E.d_offsets, E.d_mate_bases, E.d_mate_offsets, E.R});
   A.span_meta = E.d_span_meta; A.span_taxon = E.d_span_taxon; A.span_count = E.d_span_count;
-  A.status = st->d_status;
   S.n_shards = (int32_t)E.n_shards; S.chunk = slk_shard_chunk(E.n_shards); S.cap = E.capacity_per_owner;
   S.send_keys = E.d_send_keys; S.cursors = (unsigned long long *)E.d_cursors; S.send_meta = E.d_send_meta;
   S.batch_log = (uint4 *)E.d_batch_log; S.tile_rows = (uint2 *)E.d_tile_rows; S.read_info = (int2 *)E.d_read_info;
@@ -1302,11 +1251,8 @@ int32_t slk_shard_step_device(slk_index *ix, slk_stream *st, const slk_shard_lis
       //  for two dependent loads per row, the lookups for the table; on one stream they took 2.1 + 9.6 ms, side by side ~10)
       const bool beside = scans || (apply && apply_lists->R != 0);
       if (beside) {
-        if (!st->s2) {
-          HIPCHK(hipStreamCreateWithFlags(&st->s2, hipStreamNonBlocking));
-          HIPCHK(hipEventCreateWithFlags(&st->ev_fork, hipEventDisableTiming));
-          HIPCHK(hipEventCreateWithFlags(&st->ev_join, hipEventDisableTiming));
-        }
+        rc = fork_ready(st);
+        if (rc) return rc;
         HIPCHK(hipEventRecord(st->ev_fork, st->s));
         HIPCHK(hipStreamWaitEvent(st->s2, st->ev_fork, 0));
       }
@@ -1318,8 +1264,7 @@ int32_t slk_shard_step_device(slk_index *ix, slk_stream *st, const slk_shard_lis
   ApplyJob J{};
   const bool applies = apply && apply_lists->R != 0;
   if (applies) {
-    Thresholds thr{};
-    memcpy(thr.v, apply->thresholds, apply->C * sizeof(double));
+    const Thresholds thr = thresholds_of(apply->thresholds, apply->C);
     FusedArgs &B = J.A;
     B.P = ix->sp; B.T = ix->view(); B.parents = ix->kernel_parents(); B.ntax = ix->kernel_ntax(); B.nodes = ix->kernel_nodes();
     B.offsets = apply_lists->d_offsets; B.mate_offsets = apply_lists->d_mate_offsets; B.R = apply_lists->R; B.out_stride = apply_lists->R;
@@ -1365,11 +1310,11 @@ int32_t slk_classify_hits_device(slk_index *ix, slk_stream *st, const uint64_t *
     return fail(SLK_E_INVALID, "null argument");
   rc = set_device(ix);
   if (rc) return rc;
-  Thresholds thr{};
-  memcpy(thr.v, thresholds, C * sizeof(double));
-  launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, d_offsets, d_mate_offsets, R, d_span_meta, d_span_taxon, d_span_count, d_scratch,
-                  min_hit_groups, thr, C, R, d_out_taxon, d_out_classified, d_out_num_distinct,
-                  d_out_total_kmers, d_out_num_hits, nullptr, st->s);
+  ClassifyCall c;
+  c.in.offsets = d_offsets; c.in.mate_offsets = d_mate_offsets; c.in.R = R;
+  c.out = {d_out_taxon, d_out_classified, d_out_num_distinct, d_out_total_kmers, d_out_num_hits, nullptr, R};
+  c.thr = thresholds_of(thresholds, C); c.C = C; c.min_hit_groups = min_hit_groups;
+  launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, c, d_span_meta, d_span_taxon, d_span_count, d_scratch, st->s);
   HIPCHK(hipGetLastError());
   return SLK_OK;
 }
@@ -1414,17 +1359,18 @@ int32_t slk_classify_hits(slk_index *ix, slk_stream *st, uint64_t R, const uint6
   HIPCHK(st->out_cls.ensure((size_t)C * R));
   HIPCHK(st->out_nd.ensure(R * 4));
   HIPCHK(st->out_tk.ensure(R * 4));
+  DrainOnExit drain(st);
   rc = copy_in(st, st->offsets.p, offs.data(), (R + 1) * 8);
   if (!rc) rc = copy_in(st, st->span_meta.p, meta.data(), (n + 1) * 4);
   if (!rc) rc = copy_in(st, st->span_taxon.p, taxon.data(), (n + 1) * 4);
   if (!rc) rc = copy_in(st, st->span_count.p, count.data(), R * 4);
   if (rc) return rc;
-  Thresholds thr{};
-  memcpy(thr.v, thresholds, C * sizeof(double));
-  launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, st->offsets.as<uint64_t>(), nullptr, R, st->span_meta.as<int32_t>(),
-                  st->span_taxon.as<int32_t>(), st->span_count.as<int32_t>(), st->span_keys.as<uint64_t>(), min_hit_groups,
-                  thr, C, R, st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(),
-                  st->out_tk.as<int32_t>(), nullptr, nullptr, st->s);
+  ClassifyCall c;
+  c.in.offsets = st->offsets.as<uint64_t>(); c.in.R = R;
+  c.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(), nullptr, nullptr, R};
+  c.thr = thresholds_of(thresholds, C); c.C = C; c.min_hit_groups = min_hit_groups;
+  launch_classify(ix->d_parents, ix->d_nodes_orig, ix->T, c, st->span_meta.as<int32_t>(), st->span_taxon.as<int32_t>(),
+                  st->span_count.as<int32_t>(), st->span_keys.as<uint64_t>(), st->s);
   HIPCHK(hipGetLastError());
   rc = copy_out(st, out_taxon, st->out_taxon.p, (size_t)C * R * 4);
   if (!rc) rc = copy_out(st, out_classified, st->out_cls.p, (size_t)C * R);
@@ -1475,8 +1421,8 @@ static int32_t validate_reads(const uint64_t *offsets, const uint64_t *mate_offs
   return SLK_OK;
 }
 
-int32_t upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
-                            const uint64_t *mate_offsets, uint64_t R, uint64_t *total, uint64_t *mate_total) {
+int32_t slk::upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
+                          const uint64_t *mate_offsets, uint64_t R, uint64_t *total, uint64_t *mate_total) {
   int32_t rc = validate_reads(offsets, mate_offsets, R);
   if (rc) return rc;
   *total = offsets[R];
@@ -1497,10 +1443,10 @@ int32_t upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offse
 }
 
 // counts (device, int32[R]) -> out_offsets (host, u64[R+1]); uploads the offsets for a gather kernel
-int32_t counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets,
-                                 uint64_t capacity) {
+int32_t slk::counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets, uint64_t capacity) {
   out_offsets[0] = 0;
   if (R == 0) return SLK_OK;
+  DrainOnExit drain(st);
   HIPCHK(st->out_offsets.ensure((R + 1) * 8));
   HIPCHK(st->scan_tmp.ensure((R / 2048 + 2) * 8));
   launch_counts_to_offsets(d_counts, R, st->out_offsets.as<uint64_t>(), st->scan_tmp.as<uint64_t>(), st->s);   // (kernels.hip)
@@ -1528,6 +1474,7 @@ static int32_t spans_batch(slk_index *ix, slk_stream *st, const uint8_t *bases, 
   out_span_offsets[0] = 0;
   if (R == 0) return SLK_OK;
   uint64_t total, mate_total;
+  DrainOnExit drain(st);
   rc = upload_reads(st, bases, offsets, mate_bases, mate_offsets, R, &total, &mate_total);
   if (rc) return rc;
   bool paired = mate_offsets != nullptr;
@@ -1535,18 +1482,17 @@ static int32_t spans_batch(slk_index *ix, slk_stream *st, const uint8_t *bases, 
   if (rc) return rc;
   const uint64_t *d_off = st->offsets.as<uint64_t>();
   const uint64_t *d_moff = paired ? st->mate_offsets.as<uint64_t>() : nullptr;
+  const uint8_t *d_mate = paired ? st->mate_bases.as<uint8_t>() : nullptr;
   if (ix->W > 1) {
-    launch_wide_scan(ix->wp, st->bases.as<uint8_t>(), d_off, paired ? st->mate_bases.as<uint8_t>() : nullptr, d_moff, R,
+    launch_wide_scan(ix->wp, st->bases.as<uint8_t>(), d_off, d_mate, d_moff, R,
                      st->span_keys.as<uint64_t>(), st->span_meta.as<int32_t>(), st->span_count.as<int32_t>(), st->s);
   } else if (use_fused(ix)) {
-    FusedArgs A{};
-    A.P = ix->sp; A.bases = st->bases.as<uint8_t>(); A.offsets = d_off;
-    A.mate_bases = paired ? st->mate_bases.as<uint8_t>() : nullptr; A.mate_offsets = d_moff; A.R = R;
+    FusedArgs A = fused_args(ix, st, {st->bases.as<uint8_t>(), d_off, d_mate, d_moff, R});
     A.span_keys = st->span_keys.as<uint64_t>(); A.span_meta = st->span_meta.as<int32_t>();
-    A.span_count = st->span_count.as<int32_t>(); A.status = st->d_status;
+    A.span_count = st->span_count.as<int32_t>();
     launch_fused(MODE_SPANS, A, st->s);
   } else {
-    launch_scan(ix->sp, st->bases.as<uint8_t>(), d_off, paired ? st->mate_bases.as<uint8_t>() : nullptr, d_moff, R,
+    launch_scan(ix->sp, st->bases.as<uint8_t>(), d_off, d_mate, d_moff, R,
                 st->span_keys.as<uint64_t>(), st->span_meta.as<int32_t>(), st->span_count.as<int32_t>(), st->s);
   }
   HIPCHK(hipGetLastError());
@@ -1618,6 +1564,23 @@ static int32_t upload_range(slk_stream *st, Staging *g, hipStream_t up, hipStrea
   return SLK_OK;
 }
 
+// Fragments [r0, r1) of a host call as a call of their own (h_offsets / h_mate_offsets: the caller's arrays).  The offsets stay
+// ABSOLUTE, so "total bases" is where the sub-batch ENDS: it sizes the span scratch of the unbounded re-run, whose regions are
+// addressed by those offsets.  Hit lists: the fragments' span regions are addressed by their absolute offsets but by the fragment's
+// number INSIDE the sub-batch (span_region: offsets[r] + mate_offsets[r] + r for pairs), so the span arrays are handed over moved by
+// the sub-batch's first fragment number -- the regions then are the ones the whole batch has, and sub-batches do not overlap.  The
+// caller has sized the scratch for the whole batch; the result rows keep the whole batch's stride.
+static ClassifyCall sub_call(const ClassifyCall &whole, uint64_t r0, uint64_t r1, const uint64_t *h_offsets, const uint64_t *h_mate_offsets) {
+  ClassifyCall c = whole;
+  const bool paired = whole.in.paired();
+  c.in.offsets += r0;
+  if (paired) c.in.mate_offsets += r0;
+  c.in.R = r1 - r0; c.in.total = h_offsets[r1]; c.in.mate_total = paired ? h_mate_offsets[r1] : 0;
+  c.out.taxon += r0; c.out.classified += r0; c.out.nd += r0; c.out.tk += r0; c.out.nh += r0;
+  c.span_shift = whole.want_hits && paired ? r0 : 0;
+  return c;
+}
+
 static int32_t classify_batch_host(slk_index *ix, slk_stream *st, const ReadSource &src, const uint64_t *offsets, const uint64_t *mate_offsets,
                                    uint64_t R, int32_t min_hit_groups, const double *thresholds, int32_t C, int32_t *out_taxon,
                                    uint8_t *out_classified, int32_t *out_num_distinct, int32_t *out_total_kmers, uint64_t *out_hit_offsets,
@@ -1664,34 +1627,36 @@ static int32_t classify_batch_host(slk_index *ix, slk_stream *st, const ReadSour
       HIPCHK(st->pk_mate_codes.ensure((mate_total + 15) / 16 * 4 + 4));
       HIPCHK(st->pk_mate_valid.ensure((mate_total + 15) / 16 * 2 + 2));
     }
-    if (!st->ev_unpack) HIPCHK(hipEventCreateWithFlags(&st->ev_unpack, hipEventDisableTiming));
+    if (!st->ev_unpack) HIPCHK(hipEventCreateWithFlags(st->ev_unpack.put(), hipEventDisableTiming));
   }
   // A large call is cut into sub-batches: the reads of sub-batch i+1 go up (on a second stream) while the kernels of
   // sub-batch i run, so the call costs its upload plus ONE sub-batch of kernel time.  With hit lists too: the sub-batches leave
-  // their spans in the batch's span arrays (run_classify: span_shift) and the lists are put together for the whole batch at the end.
-  const char *sub_env = getenv("SLK_HOST_SUBBATCH");  // (read per call, so that tests can move it)
+  // their spans in the batch's span arrays (sub_call: span_shift) and the lists are put together for the whole batch at the end.
   // (2^19 reads: measured from pinned memory, 4 M reads of 150 bp -- packed 353 / 576 / 643 / 623 / 403 M reads/s at 2^17 .. 2^21, text
   //  313 / 324 / 327 / 315 / 246: smaller pieces pay per copy -- a sub-batch is five to nine DMAs --, larger ones leave the last
-  //  piece's kernels exposed; profiles/r04_packed_entry.json)
-  const uint64_t SUB = sub_env ? (uint64_t)std::max(1L, atol(sub_env)) : (uint64_t)1 << 19;
+  //  piece's kernels exposed; profiles/r04_packed_entry.json.  Read per call, so that tests can move it.)
+  const uint64_t SUB = (uint64_t)std::max(1L, env_long("SLK_HOST_SUBBATCH", 1L << 19));
+  ClassifyCall whole;   // (every buffer it names has its size for this call by now)
+  whole.in = {st->bases.as<uint8_t>(), st->offsets.as<uint64_t>(), paired ? st->mate_bases.as<uint8_t>() : nullptr,
+              paired ? st->mate_offsets.as<uint64_t>() : nullptr, R, total, mate_total};
+  whole.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
+               st->out_nh.as<int32_t>(), nullptr, R};
+  whole.thr = thresholds_of(thresholds, C); whole.C = C; whole.min_hit_groups = min_hit_groups; whole.want_hits = want_hits;
+  DrainOnExit drain(st);   // (from the first copy queued below, no return leaves work behind that touches the caller's memory)
   if (use_fused(ix) && R >= 2 * SUB) {
     if (want_hits) {   // (once, for the whole batch: a sub-batch must not move the arrays under the kernels of the one before)
       rc = ensure_scratch(st, span_slots(total, mate_total, R, paired), R);
       if (rc) return rc;
     }
-    if (!st->cs) HIPCHK(hipStreamCreateWithFlags(&st->cs, hipStreamNonBlocking));
-    if (!st->ds) HIPCHK(hipStreamCreateWithFlags(&st->ds, hipStreamNonBlocking));
+    if (!st->cs) HIPCHK(hipStreamCreateWithFlags(st->cs.put(), hipStreamNonBlocking));
+    if (!st->ds) HIPCHK(hipStreamCreateWithFlags(st->ds.put(), hipStreamNonBlocking));
     const uint64_t nsub = (R + SUB - 1) / SUB;
-    while (st->up_ev.size() < nsub) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      st->up_ev.push_back(e);
-    }
-    while (st->dn_ev.size() < nsub) {
-      hipEvent_t e;
-      HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      st->dn_ev.push_back(e);
-    }
+    for (std::vector<Event> *evs : {&st->up_ev, &st->dn_ev})
+      while (evs->size() < nsub) {
+        Event e;
+        HIPCHK(hipEventCreateWithFlags(e.put(), hipEventDisableTiming));
+        evs->push_back(std::move(e));
+      }
     // Result buffers the library can DMA into take their rows sub-batch by sub-batch, beside the next sub-batch's kernels (the link
     // is full duplex: the rows come down while the reads go up); pageable ones are filled at the end, through the staging buffers.
     early_down = pinned().covers(out_taxon, (size_t)C * R * 4) && pinned().covers(out_classified, (size_t)C * R) &&
@@ -1712,13 +1677,7 @@ static int32_t classify_batch_host(slk_index *ix, slk_stream *st, const ReadSour
       if (rc) return rc;
       HIPCHK(hipEventRecord(st->up_ev[i], st->cs));
       HIPCHK(hipStreamWaitEvent(st->s, st->up_ev[i], 0));
-      rc = run_classify(ix, st, st->bases.as<uint8_t>(), st->offsets.as<uint64_t>() + r0, paired ? st->mate_bases.as<uint8_t>() : nullptr,
-                        // (the offsets stay absolute, so "total bases" is where this sub-batch ENDS: it sizes the span scratch of
-                        //  the unbounded re-run, whose regions are addressed by those offsets)
-                        paired ? st->mate_offsets.as<uint64_t>() + r0 : nullptr, n, offsets[r1],
-                        paired ? mate_offsets[r1] : 0, min_hit_groups, thresholds, C, st->out_taxon.as<int32_t>() + r0,
-                        st->out_cls.as<uint8_t>() + r0, st->out_nd.as<int32_t>() + r0, st->out_tk.as<int32_t>() + r0,
-                        st->out_nh.as<int32_t>() + r0, nullptr, want_hits, R, want_hits && paired ? r0 : 0);
+      rc = run_classify(ix, st, sub_call(whole, r0, r1, offsets, mate_offsets));
       if (rc) return rc;
       if (early_down) {
         HIPCHK(hipEventRecord(st->dn_ev[i], st->s));
@@ -1744,10 +1703,7 @@ static int32_t classify_batch_host(slk_index *ix, slk_stream *st, const ReadSour
     }
     if (rc) return rc;
     if (call_timing) { (void)hipStreamSynchronize(st->s); tp[1] = now(); }
-    rc = run_classify(ix, st, st->bases.as<uint8_t>(), st->offsets.as<uint64_t>(), paired ? st->mate_bases.as<uint8_t>() : nullptr,
-                      paired ? st->mate_offsets.as<uint64_t>() : nullptr, R, total, mate_total, min_hit_groups, thresholds, C,
-                      st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
-                      st->out_nh.as<int32_t>(), nullptr, want_hits);
+    rc = run_classify(ix, st, whole);
     if (rc) return rc;
   }
   const uint64_t *d_off = st->offsets.as<uint64_t>();
@@ -1842,5 +1798,3 @@ int32_t slk_pack_bases(const uint8_t *bases, uint64_t n, uint32_t *codes, uint16
   });
   return SLK_OK;
 }
-
-}  // extern "C"

@@ -360,11 +360,32 @@ void launch_scan(const ScanParams &P, const uint8_t *bases, const uint64_t *offs
 void launch_probe(const TableView &T, const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R,
                   const uint64_t *span_keys, const int32_t *span_meta, const int32_t *span_count, int32_t *span_taxon,
                   hipStream_t s);
-void launch_classify(const int32_t *parents, const uint4 *nodes, int32_t T, const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R,
-                     const int32_t *span_meta, const int32_t *span_taxon, const int32_t *span_count,
-                     uint64_t *map_scratch, int32_t min_hit_groups, const Thresholds &thr, int32_t C, uint64_t out_stride,
-                     int32_t *out_taxon, uint8_t *out_classified, int32_t *out_num_distinct, int32_t *out_total_kmers,
-                     int32_t *out_num_hits, int32_t *out_num_probes, hipStream_t s);
+// One record of a batch, for the host side only (no kernel reads these; the launchers take them apart):
+struct Reads {        // the fragments, on the device
+  const uint8_t *bases = nullptr;
+  const uint64_t *offsets = nullptr;
+  const uint8_t *mate_bases = nullptr;     // the second mates' two arrays, or both null
+  const uint64_t *mate_offsets = nullptr;
+  uint64_t R = 0, total = 0, mate_total = 0;
+  bool paired() const { return mate_offsets != nullptr; }
+};
+struct ResultRows {   // where the results go, on the device (nullable from nd on)
+  int32_t *taxon = nullptr;      // [C][stride]
+  uint8_t *classified = nullptr; // [C][stride]
+  int32_t *nd = nullptr, *tk = nullptr, *nh = nullptr, *np = nullptr;
+  uint64_t stride = 0;           // = R unless the call is a sub-batch of a larger one
+};
+struct ClassifyCall {
+  Reads in;
+  ResultRows out;
+  Thresholds thr{};
+  int32_t C = 0, min_hit_groups = 0;
+  bool want_hits = false;
+  uint64_t span_shift = 0;   // slots the span arrays are moved by for this call (capi.hip: sub_call)
+};
+// the staged classify kernel over the spans of c.in (map_scratch: their key slots, dead after the probe)
+void launch_classify(const int32_t *parents, const uint4 *nodes, int32_t T, const ClassifyCall &c, const int32_t *span_meta,
+                     const int32_t *span_taxon, const int32_t *span_count, uint64_t *map_scratch, hipStream_t s);
 void launch_gather_spans(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R, const uint64_t *span_keys,
                          const int32_t *span_meta, const uint64_t *out_offsets, void *out, hipStream_t s);
 // out[i] = counts[0] + .. + counts[i - 1] for i = 0 .. n (n + 1 values); tmp holds n / 2048 + 2 words

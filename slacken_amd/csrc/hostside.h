@@ -15,6 +15,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -46,9 +47,44 @@ inline int32_t fail(int32_t code, const char *fmt, ...) {
   } while (0)
 
 
-struct DevBuf {
+// ---- owners -------------------------------------------------------------------------------------------------------------------
+// Whatever the host side allocates on or for a device is held by one of these: released when the owner dies, movable, not copyable.
+// Two rules follow from the destructors.  No owner has static storage duration (the HIP runtime is gone by the time statics die),
+// and whoever deletes a handle selects its device first.
+template <class H, hipError_t (*Free)(H)>
+class Owner {
+  H h_{};
+
+ public:
+  Owner() = default;
+  Owner(Owner &&o) noexcept : h_(o.h_) { o.h_ = H{}; }
+  Owner &operator=(Owner &&o) noexcept {
+    if (this != &o) { reset(o.h_); o.h_ = H{}; }
+    return *this;
+  }
+  ~Owner() { reset(); }
+  H get() const { return h_; }
+  operator H() const { return h_; }
+  void reset(H h = H{}) { if (h_) (void)Free(h_); h_ = h; }
+  H *put() { reset(); return &h_; }   // for the call that makes one: hipStreamCreate(s.put()), hipMalloc((void **)p.put(), n)
+};
+template <class T> hipError_t free_device(T *p) { return hipFree((void *)p); }
+template <class T> hipError_t free_pinned(T *p) { return hipHostFree((void *)p); }
+template <class T> using DevPtr = Owner<T *, free_device<T>>;
+template <class T> using PinnedPtr = Owner<T *, free_pinned<T>>;
+using Stream = Owner<hipStream_t, hipStreamDestroy>;
+using Event = Owner<hipEvent_t, hipEventDestroy>;
+
+struct DevBuf {   // device scratch that grows on demand
   void *p = nullptr;
   size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    return *this;
+  }
+  ~DevBuf() { release(); }
   hipError_t ensure(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
     if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
@@ -60,6 +96,11 @@ struct DevBuf {
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T *as() const { return (T *)p; }
 };
+
+// SLK_* switches of the environment.  Which of them are read once per process (a `static const` at the place of use) and which
+// per call (tests move those) is the caller's business.
+inline bool env_on(const char *name) { const char *e = getenv(name); return e != nullptr && e[0] == '1'; }
+inline long env_long(const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; }
 
 // ---- host side of the copies ----------------------------------------------------------------------------------------------
 // A few threads that move bytes between the caller's (pageable) memory and the pinned staging buffers: one thread copies
@@ -123,8 +164,7 @@ class HostPool {
 };
 inline HostPool &host_pool() {
   static HostPool *pool = [] {
-    const char *e = getenv("SLK_COPY_THREADS");
-    long n = e ? atol(e) : 6;
+    long n = env_long("SLK_COPY_THREADS", 6);
     unsigned hc = std::thread::hardware_concurrency();
     if (hc && n > (long)hc) n = hc;
     return new HostPool((size_t)std::max<long>(1, n));  // (never destroyed: worker threads must not be joined at process exit)
@@ -171,16 +211,12 @@ inline PinnedRanges &pinned() { static PinnedRanges *r = new PinnedRanges(); ret
 // threads was mapping and unmapping memory around it.  Memory from slk_host_alloc / slk_host_register skips them.
 constexpr int N_STAGE = 3;
 struct Staging {
-  void *buf[N_STAGE] = {};
-  hipEvent_t ev[N_STAGE] = {};
+  PinnedPtr<void> buf[N_STAGE];
+  Event ev[N_STAGE];
   bool busy[N_STAGE] = {};
   int next = 0;
   void release() {
-    for (int i = 0; i < N_STAGE; i++) {
-      if (buf[i]) (void)hipHostFree(buf[i]);
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-      buf[i] = nullptr; ev[i] = nullptr; busy[i] = false;
-    }
+    for (int i = 0; i < N_STAGE; i++) { buf[i].reset(); ev[i].reset(); busy[i] = false; }
   }
 };
 
@@ -188,20 +224,23 @@ struct slk_index {
   int32_t device = 0;
   slk_params params{};
   ScanParams sp{};
-  uint64_t *cells = nullptr;
+  DevPtr<uint64_t> cells;
   uint64_t nbuckets = 0;
   int32_t bucket_bits = 0, taxon_bits = 0, disp_bits = 0;   // bucket_bits = ceil(log2(nbuckets)): the hash bits that choose the bucket
   bool bucket_flag = false;        // the cells keep their top bit for the buckets' "a record went past" flag (engine.h: TableGeom.flag)
   uint32_t shard = 0, n_shards = 0;  // slk_index_set_shard: keep only the records of this shard
-  int32_t *d_max_disp = nullptr;
-  unsigned long long *d_counters = nullptr;  // inserted, duplicate, overflow
-  int32_t *d_parents = nullptr;   // the taxonomy as given (ids of the caller)
+  DevPtr<int32_t> d_max_disp;
+  DevPtr<unsigned long long> d_counters;  // inserted, duplicate, overflow
+  DevPtr<int32_t> d_parents;      // the taxonomy as given (ids of the caller)
   int32_t T = 0;
   std::vector<int32_t> h_parents;  // host copy, for the dense renumbering at finalize
   // dense taxon ids (engine.h: TableView.to_orig): set up by slk_index_finalize when the caller's ids need more than 22 bits
-  int32_t *d_parents_dense = nullptr, *d_to_orig = nullptr, *d_to_dense = nullptr;
-  uint4 *d_nodes = nullptr;        // kernel_parents() with an Euler tour (engine.h: FusedArgs.nodes); null: more than 2^22 ids, no lane kernel
-  uint4 *d_nodes_orig = nullptr;   // the same for the taxonomy as given (the staged classify kernel works in the caller's ids); may BE d_nodes
+  DevPtr<int32_t> d_parents_dense, d_to_orig, d_to_dense;
+  // Euler tours (capi.hip: build_tax_nodes).  The two owners: of the taxonomy as given (the staged classify kernel works in the
+  // caller's ids; null: more than 2^26 ids) and of the dense renumbering.  d_nodes is a VIEW of one of them: kernel_parents() with
+  // its tour (engine.h: FusedArgs.nodes); null: more than 2^22 ids, no lane kernel.
+  DevPtr<uint4> d_nodes_orig, d_nodes_dense;
+  const uint4 *d_nodes = nullptr;
   int32_t D = 0;                   // nodes of the taxonomy = largest dense id (0: ids are stored as given)
   bool finalized = false;
   int32_t max_disp = 0;
@@ -209,14 +248,17 @@ struct slk_index {
   uint64_t unplaced = 0;           // records of the last insert that found no cell within reach of the displacement field (capi.hip: insert_growing)
   uint32_t grown = 0;              // times the table was moved to a larger one because of that
   float load_target = 0;           // the load factor the table was sized for (given, or chosen by the free memory: slk_index_create)
-  hipStream_t build_stream = nullptr;
+  bool spent = false;              // the table was lost while it was growing (capi.hip: grow_table): only slk_index_destroy takes the index
+  Stream build_stream;
   DevBuf stage_keys, stage_taxa;
   Staging staging;    // host -> HBM copies of the build calls
   int W = 1;          // id columns; > 1: the wide path (wide.hip) with its own table
   WideParams wp{};
-  WideTable wt{};
+  WideTable wt{};    // (a view: the two arrays are owned by wide_keys / wide_taxa)
+  DevPtr<uint64_t> wide_keys;
+  DevPtr<int32_t> wide_taxa;
 
-  TableGeom geom() const {
+  static TableGeom geom_of(uint64_t nbuckets, int32_t bucket_bits, bool bucket_flag, int32_t taxon_bits, int32_t disp_bits) {
     TableGeom g{};
     g.nbuckets = nbuckets;
     g.q = bucket_bits;
@@ -226,6 +268,7 @@ struct slk_index {
     g.disp_bits = disp_bits;
     return g;
   }
+  TableGeom geom() const { return geom_of(nbuckets, bucket_bits, bucket_flag, taxon_bits, disp_bits); }
   TableView view() const {
     TableView v;
     v.cells = cells;
@@ -249,55 +292,46 @@ struct slk_index {
 struct slk_stream {
   slk_index *ix = nullptr;
   int32_t device = 0;  // copy: the stream may be destroyed after its index
-  hipStream_t s = nullptr;
+  Stream s;
   DevBuf span_keys, span_meta, span_taxon, span_count;  // per-batch scratch (sparse per-read regions)
   DevBuf bases, offsets, mate_bases, mate_offsets;      // staging for the host-pointer entry points
   DevBuf out_taxon, out_cls, out_nd, out_tk, out_nh, out_offsets, out_items, defer_list, scan_tmp;
   bool merged_hits = false;                 // slk_stream_set_merged_hits: hit lists as TaxonCounts.fromHits merges them
   DevBuf pk_codes, pk_valid, pk_mate_codes, pk_mate_valid;   // slk_classify_batch_packed: the reads as they arrive (3 bits per base)
-  hipEvent_t ev_unpack = nullptr;
-  hipStream_t s2 = nullptr;                 // the segment pass and the wave pass run here, beside the long-lane pass on s
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int32_t *d_status = nullptr;     // device error bits of the fused kernels
-  int32_t *h_status = nullptr;     // pinned copy, refreshed after every classify launch
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev_unpack;
+  Stream s2;                                // the segment pass and the wave pass run here, beside the long-lane pass on s
+  Event ev_fork, ev_join;
+  DevPtr<int32_t> d_status;        // device error bits of the fused kernels
+  PinnedPtr<int32_t> h_status;     // pinned copy, refreshed after every classify launch
+  Event ev[4];
   Staging staging;
   // large host-pointer calls: the reads go up on a second stream, sub-batch by sub-batch, while the kernels of the
   // sub-batches before run on s (slk_classify_batch)
-  hipStream_t cs = nullptr;
+  Stream cs;
   Staging staging_c;
-  std::vector<hipEvent_t> up_ev;
+  std::vector<Event> up_ev;
   // ... and the results of sub-batch i come down on a third stream while sub-batch i + 1 runs (pinned result buffers only)
-  hipStream_t ds = nullptr;
-  std::vector<hipEvent_t> dn_ev;
+  Stream ds;
+  std::vector<Event> dn_ev;
   bool reran = false;           // check_status classified queued calls again (a taxon map had overflowed): results on the host are stale
   bool timed = false;
   bool last_used_lane = false;  // the last classify call ran the lane kernel (defer_list[0] is its deferral count)
   // The arguments of every classify call queued since the stream was last synchronised, for the unbounded re-run
   // (check_status): a taxon-map overflow is only seen at the next synchronisation, and by then several calls may have gone by.
-  struct LastCall {
-    bool valid = false, want_hits = false;
-    Thresholds thr{};
-    const uint8_t *bases = nullptr, *mate_bases = nullptr;
-    const uint64_t *offsets = nullptr, *mate_offsets = nullptr;
-    uint64_t R = 0, total = 0, mate_total = 0, out_stride = 0;
-    uint64_t span_shift = 0;   // slots the span arrays are moved by for this call (a sub-batch of a larger host call: run_classify)
-    int32_t min_hit_groups = 0, C = 0;
-    int32_t *out_taxon = nullptr, *out_nd = nullptr, *out_tk = nullptr, *out_nh = nullptr, *out_np = nullptr;
-    uint8_t *out_cls = nullptr;
+  struct Queued {
+    ClassifyCall call;
+    bool valid = false;   // the call can be run again (it was a fused classify call)
   };
-  std::vector<LastCall> queued;
+  std::vector<Queued> queued;
 };
-
-extern "C" __attribute__((visibility("hidden"))) int32_t check_status(slk_stream *st);
 
 constexpr size_t STAGE_BYTES = (size_t)8 << 20;
 
 inline int32_t stage_ready(Staging *g) {
-  if (g->buf[0]) return SLK_OK;
+  if (g->ev[N_STAGE - 1]) return SLK_OK;
   for (int i = 0; i < N_STAGE; i++) {
-    HIPCHK(hipHostMalloc(&g->buf[i], STAGE_BYTES, hipHostMallocDefault));
-    HIPCHK(hipEventCreateWithFlags(&g->ev[i], hipEventDisableTiming));
+    HIPCHK(hipHostMalloc(g->buf[i].put(), STAGE_BYTES, hipHostMallocDefault));
+    HIPCHK(hipEventCreateWithFlags(g->ev[i].put(), hipEventDisableTiming));
   }
   return SLK_OK;
 }
@@ -361,22 +395,43 @@ inline int32_t copy_out(Staging *g, hipStream_t s, void *h_dst, const void *d_sr
 inline int32_t copy_in(slk_stream *st, void *d_dst, const void *h_src, size_t n) { return copy_in(&st->staging, st->s, d_dst, h_src, n); }
 inline int32_t copy_out(slk_stream *st, void *h_dst, const void *d_src, size_t n) { return copy_out(&st->staging, st->s, h_dst, d_src, n); }
 
-// Every entry point that launches kernels starts here: select the index's device and drop whatever error code an earlier,
+// Every entry point that takes an index starts here: select the index's device and drop whatever error code an earlier,
 // unrelated HIP call of this thread (this library's or the application's) left behind, so that the hipGetLastError()
-// after a launch reports that launch.
+// after a launch reports that launch.  An index that lost its table (capi.hip: grow_table) is refused.
+inline int32_t check_spent(const slk_index *ix) {
+  if (ix->spent)
+    return fail(SLK_E_STATE, "this index lost its records when its table could not grow: destroy it and repeat the load (with a larger "
+                             "slk_table_config.expected_records)");
+  return SLK_OK;
+}
 inline int32_t set_device(const slk_index *ix) {
+  int32_t rc = check_spent(ix);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ix->device));
   (void)hipGetLastError();
   return SLK_OK;
 }
 
+// A synchronous host entry leaves with nothing queued that reads or writes the caller's memory: from the first copy it queues, every
+// return -- the failing ones too, after which the caller may free its buffers -- passes through this.
+struct DrainOnExit {
+  slk_stream *st;
+  explicit DrainOnExit(slk_stream *st_) : st(st_) {}
+  DrainOnExit(const DrainOnExit &) = delete;
+  ~DrainOnExit() {
+    for (hipStream_t s : {st->cs.get(), st->s.get(), st->ds.get()})
+      if (s && hipStreamSynchronize(s) != hipSuccess) (void)hipGetLastError();
+  }
+};
 
-// defined in capi.hip (inside its extern "C" block), used by shardset.hip too; not exported
-#define SLK_INTERNAL extern "C" __attribute__((visibility("hidden")))
-SLK_INTERNAL uint64_t span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired);
-SLK_INTERNAL int32_t ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R);
-SLK_INTERNAL int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax);
-SLK_INTERNAL bool lane_path_ok(const slk_index *ix);
-SLK_INTERNAL int32_t upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
-                                  const uint64_t *mate_offsets, uint64_t R, uint64_t *total, uint64_t *mate_total);
-SLK_INTERNAL int32_t counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets, uint64_t capacity);
+// defined in capi.hip, used by shardset.hip and bracken.hip too; not exported (the library exports its extern "C" names only)
+namespace slk {
+int32_t check_status(slk_stream *st);   // call after the stream has been synchronised
+uint64_t span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired);
+int32_t ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R);
+int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax);
+bool lane_path_ok(const slk_index *ix);
+int32_t upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
+                     const uint64_t *mate_offsets, uint64_t R, uint64_t *total, uint64_t *mate_total);
+int32_t counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets, uint64_t capacity);
+}  // namespace slk

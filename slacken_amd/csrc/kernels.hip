@@ -622,17 +622,15 @@ void launch_probe(const TableView &T, const uint64_t *offsets, const uint64_t *m
   hipLaunchKernelGGL(probe_kernel, dim3((unsigned)blocks), dim3(256), 0, s, T, offsets, mate_offsets, R, span_keys,
                      span_meta, span_count, span_taxon);
 }
-void launch_classify(const int32_t *parents, const uint4 *nodes, int32_t T, const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R,
-                     const int32_t *span_meta, const int32_t *span_taxon, const int32_t *span_count,
-                     uint64_t *map_scratch, int32_t min_hit_groups, const Thresholds &thr, int32_t C, uint64_t out_stride,
-                     int32_t *out_taxon, uint8_t *out_classified, int32_t *out_num_distinct, int32_t *out_total_kmers,
-                     int32_t *out_num_hits, int32_t *out_num_probes, hipStream_t s) {
+void launch_classify(const int32_t *parents, const uint4 *nodes, int32_t T, const ClassifyCall &c, const int32_t *span_meta,
+                     const int32_t *span_taxon, const int32_t *span_count, uint64_t *map_scratch, hipStream_t s) {
+  const uint64_t R = c.in.R;
   if (R == 0) return;
   Tax tx{parents, nodes, T};
   uint64_t blocks = (R + 255) / 256;
-  hipLaunchKernelGGL(classify_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tx, offsets, mate_offsets, R, span_meta,
-                     span_taxon, span_count, map_scratch, min_hit_groups, thr, C, out_stride, out_taxon, out_classified,
-                     out_num_distinct, out_total_kmers, out_num_hits, out_num_probes);
+  hipLaunchKernelGGL(classify_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tx, c.in.offsets, c.in.mate_offsets, R, span_meta,
+                     span_taxon, span_count, map_scratch, c.min_hit_groups, c.thr, c.C, c.out.stride, c.out.taxon, c.out.classified,
+                     c.out.nd, c.out.tk, c.out.nh, c.out.np);
 }
 void launch_gather_spans(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R, const uint64_t *span_keys,
                          const int32_t *span_meta, const uint64_t *out_offsets, void *out, hipStream_t s) {

@@ -23,8 +23,6 @@
 
 #include <dlfcn.h>
 
-#include <memory>
-
 namespace {
 
 // ---- the few RCCL entry points, resolved at run time (no link-time dependency; PyTorch processes carry their own copy) ----
@@ -110,57 +108,34 @@ struct Slot {   // what a round leaves on a member between its EMIT and its APPL
   DevBuf send_meta, cursors, log, tile_rows, read_info, defer, taxa;     // engine.h: ShardIO / ApplyJob
   DevBuf span_meta, span_taxon, span_count, out_offsets, out_items;      // hit lists
   DevBuf out_taxon, out_cls, out_nd, out_tk, out_nh;                     // results (host-pointer rounds)
-  uint64_t *h_cursors = nullptr;                                          // pinned [n + 3]
-  hipEvent_t ev_up = nullptr, ev_keys = nullptr, ev_taxa = nullptr;       // reads uploaded; the round's keys arrived HERE; its taxa came back
+  PinnedPtr<uint64_t> h_cursors;                                          // pinned [n + 3]
+  Event ev_up, ev_keys, ev_taxa;                                          // reads uploaded; the round's keys arrived HERE; its taxa came back
   slk_shard_lists lists{};
   uint64_t total = 0, mate_total = 0;
   bool failed = false;                                                    // a send region overflowed: the whole batch takes the staged route
-  void release() {
-    for (DevBuf *b : {&bases, &offsets, &mate_bases, &mate_offsets, &send_meta, &cursors, &log, &tile_rows, &read_info, &defer, &taxa, &span_meta,
-                      &span_taxon, &span_count, &out_offsets, &out_items, &out_taxon, &out_cls, &out_nd, &out_tk, &out_nh})
-      b->release();
-    if (h_cursors) (void)hipHostFree(h_cursors);
-    for (hipEvent_t *e : {&ev_up, &ev_keys, &ev_taxa}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-    h_cursors = nullptr;
-  }
 };
 struct Big {    // send_keys: EMIT(t) .. exchange after step t; recv_keys / found: exchange .. LOOKUP(t + 2) .. exchange after step t + 2
   DevBuf send_keys, recv_keys, found;
-  void release() { send_keys.release(); recv_keys.release(); found.release(); }
 };
 
 struct Member {
   slk_index *ix = nullptr;
   int32_t device = 0;           // copy: the set may be destroyed after its members' indices
   slk_stream *st = nullptr;     // this set's compute stream on the member (HIP stream, staging buffers, scratch of the staged round)
-  hipStream_t xs = nullptr;     // the exchanges
-  hipStream_t us = nullptr;     // reads up (host-pointer rounds)
-  hipStream_t ds = nullptr;     // results down
+  Stream xs;                    // the exchanges
+  Stream us;                    // reads up (host-pointer rounds)
+  Stream ds;                    // results down
   Staging staging_u, staging_d;
   ncclComm_t comm = nullptr;
   Slot slot[NSLOT];
   Big big[NBIG];
-  hipEvent_t ev_step[NSLOT] = {};   // step t's kernel (and the copy of its cursors) has finished
+  Event ev_step[NSLOT];             // step t's kernel (and the copy of its cursors) has finished
   // the staged round's buffers
   DevBuf counts, starts, out_keys, slots, recv_keys, found, taxa;
-  uint64_t *h_counts = nullptr;     // pinned [n]: keys per owner
-  hipEvent_t ev_sent = nullptr, ev_found = nullptr, ev_bounce = nullptr;
-  void *h_bounce = nullptr;         // pinned: copies to devices that cannot reach this one's memory
+  PinnedPtr<uint64_t> h_counts;     // pinned [n]: keys per owner
+  Event ev_sent, ev_found, ev_bounce;
+  PinnedPtr<void> h_bounce;         // pinned: copies to devices that cannot reach this one's memory
   size_t bounce_cap = 0;
-  void release() {
-    for (Slot &s : slot) s.release();
-    for (Big &b : big) b.release();
-    for (DevBuf *b : {&counts, &starts, &out_keys, &slots, &recv_keys, &found, &taxa}) b->release();
-    staging_u.release(); staging_d.release();
-    if (h_counts) (void)hipHostFree(h_counts);
-    if (h_bounce) (void)hipHostFree(h_bounce);
-    for (hipEvent_t &e : ev_step) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    if (ev_sent) (void)hipEventDestroy(ev_sent);
-    if (ev_found) (void)hipEventDestroy(ev_found);
-    if (ev_bounce) (void)hipEventDestroy(ev_bounce);
-    for (hipStream_t *s : {&xs, &us, &ds}) { if (*s) { (void)hipStreamSynchronize(*s); (void)hipStreamDestroy(*s); } *s = nullptr; }
-    h_counts = nullptr; h_bounce = nullptr; bounce_cap = 0; ev_sent = ev_found = ev_bounce = nullptr;
-  }
 };
 
 }  // namespace
@@ -234,18 +209,17 @@ int32_t exchange(slk_shardset *set, const std::vector<const void *> &src, const 
         for (int d = 0; d < W; d++) { if (d == b) off = row; row += n[a][d]; }
         if (row * esz > ma.bounce_cap) {
           HIPCHK(hipStreamSynchronize(str[a]));   // (the copies still using the old buffer)
-          if (ma.h_bounce) HIPCHK(hipHostFree(ma.h_bounce));
-          ma.h_bounce = nullptr; ma.bounce_cap = 0;
-          HIPCHK(hipHostMalloc(&ma.h_bounce, row * esz + row * esz / 4 + 4096, hipHostMallocPortable));
+          ma.bounce_cap = 0;
+          HIPCHK(hipHostMalloc(ma.h_bounce.put(), row * esz + row * esz / 4 + 4096, hipHostMallocPortable));
           ma.bounce_cap = row * esz + row * esz / 4 + 4096;
         }
         HIPCHK(hipStreamWaitEvent(str[a], ev[a], 0));
-        HIPCHK(hipMemcpyAsync((char *)ma.h_bounce + off * esz, from, bytes, hipMemcpyDeviceToHost, str[a]));
+        HIPCHK(hipMemcpyAsync((char *)ma.h_bounce.get() + off * esz, from, bytes, hipMemcpyDeviceToHost, str[a]));
         HIPCHK(hipEventRecord(ma.ev_bounce, str[a]));
         rc = use(set->m[b]);
         if (rc) return rc;
         HIPCHK(hipStreamWaitEvent(str[b], ma.ev_bounce, 0));
-        HIPCHK(hipMemcpyAsync(to, (const char *)ma.h_bounce + off * esz, bytes, hipMemcpyHostToDevice, str[b]));
+        HIPCHK(hipMemcpyAsync(to, (const char *)ma.h_bounce.get() + off * esz, bytes, hipMemcpyHostToDevice, str[b]));
       }
     }
   }
@@ -441,10 +415,13 @@ int32_t staged_round(slk_shardset *set, const RoundArgs &A) {
       HIPCHK(hipGetLastError());
     }
     // the key slots are dead after the exchange: the unbounded per-fragment taxon map of the classify kernel reuses them
-    launch_classify(mb.ix->d_parents, mb.ix->d_nodes_orig, mb.ix->T, st->offsets.as<uint64_t>(), paired ? st->mate_offsets.as<uint64_t>() : nullptr,
-                    B.R, st->span_meta.as<int32_t>(), st->span_taxon.as<int32_t>(), st->span_count.as<int32_t>(), st->span_keys.as<uint64_t>(),
-                    A.min_hit_groups, thr, A.C, B.R, st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(),
-                    st->out_tk.as<int32_t>(), st->out_nh.as<int32_t>(), nullptr, st->s);
+    ClassifyCall c;
+    c.in.offsets = st->offsets.as<uint64_t>(); c.in.mate_offsets = paired ? st->mate_offsets.as<uint64_t>() : nullptr; c.in.R = B.R;
+    c.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
+             st->out_nh.as<int32_t>(), nullptr, B.R};
+    c.thr = thr; c.C = A.C; c.min_hit_groups = A.min_hit_groups;
+    launch_classify(mb.ix->d_parents, mb.ix->d_nodes_orig, mb.ix->T, c, st->span_meta.as<int32_t>(), st->span_taxon.as<int32_t>(),
+                    st->span_count.as<int32_t>(), st->span_keys.as<uint64_t>(), st->s);
     HIPCHK(hipGetLastError());
   }
   rc = sync_all(set);
@@ -1022,34 +999,27 @@ int32_t slk_shardset_create(slk_index *const *members, int32_t n_members, int32_
   set->m.resize(n_members);
   set->cnt.assign(n_members, std::vector<uint64_t>(n_members, 0));
   set->peer.assign(n_members, std::vector<char>(n_members, 1));
-  auto cleanup = [&]() {
-    for (Member &mb : set->m) {
-      if (mb.ix) (void)hipSetDevice(mb.device);
-      if (mb.comm) (void)rccl().CommDestroy(mb.comm);
-      if (mb.st) slk_stream_destroy(mb.st);
-      mb.release();
-    }
-  };
+  auto cleanup = [&]() { slk_shardset_destroy(set.release()); };
   for (int g = 0; g < n_members; g++) {
     Member &mb = set->m[g];
     mb.ix = members[g];
     mb.device = members[g]->device;
     int32_t rc = slk_stream_create(mb.ix, &mb.st);
     if (rc) { cleanup(); return rc; }
-    bool ok = hipHostMalloc((void **)&mb.h_counts, ((size_t)n_members + 3) * 8, hipHostMallocDefault) == hipSuccess &&
-              hipEventCreateWithFlags(&mb.ev_sent, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&mb.ev_found, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&mb.ev_bounce, hipEventDisableTiming) == hipSuccess &&
-              hipStreamCreateWithFlags(&mb.xs, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&mb.us, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&mb.ds, hipStreamNonBlocking) == hipSuccess;
+    bool ok = hipHostMalloc((void **)mb.h_counts.put(), ((size_t)n_members + 3) * 8, hipHostMallocDefault) == hipSuccess &&
+              hipEventCreateWithFlags(mb.ev_sent.put(), hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(mb.ev_found.put(), hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(mb.ev_bounce.put(), hipEventDisableTiming) == hipSuccess &&
+              hipStreamCreateWithFlags(mb.xs.put(), hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(mb.us.put(), hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(mb.ds.put(), hipStreamNonBlocking) == hipSuccess;
     for (int i = 0; ok && i < NSLOT; i++) {
       Slot &sl = mb.slot[i];
-      ok = hipEventCreateWithFlags(&mb.ev_step[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&sl.ev_up, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&sl.ev_keys, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&sl.ev_taxa, hipEventDisableTiming) == hipSuccess &&
-           hipHostMalloc((void **)&sl.h_cursors, ((size_t)n_members + 3) * 8, hipHostMallocDefault) == hipSuccess;
+      ok = hipEventCreateWithFlags(mb.ev_step[i].put(), hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(sl.ev_up.put(), hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(sl.ev_keys.put(), hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(sl.ev_taxa.put(), hipEventDisableTiming) == hipSuccess &&
+           hipHostMalloc((void **)sl.h_cursors.put(), ((size_t)n_members + 3) * 8, hipHostMallocDefault) == hipSuccess;
     }
     if (!ok) {
       (void)hipGetLastError();
@@ -1111,7 +1081,9 @@ void slk_shardset_destroy(slk_shardset *set) {
     if (mb.st) (void)hipStreamSynchronize(mb.st->s);
     if (mb.comm) (void)rccl().CommDestroy(mb.comm);
     if (mb.st) slk_stream_destroy(mb.st);
-    mb.release();
+    for (hipStream_t s : {mb.xs.get(), mb.us.get(), mb.ds.get()})
+      if (s) (void)hipStreamSynchronize(s);
+    mb = Member();   // (its buffers, streams and events go here, with its device selected)
   }
   delete set;
 }
