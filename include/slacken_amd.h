@@ -442,6 +442,43 @@ int32_t slk_bracken_add(slk_bracken *b, slk_stream *st, const uint8_t *bases, co
 int32_t slk_bracken_result(slk_bracken *b, uint64_t *n, int32_t *dest, int32_t *source, uint64_t *count, uint64_t cap);
 void slk_bracken_destroy(slk_bracken *b);
 
+/* ---- Minimizer migration: replaces MinimizerMigration.taxaDistances (S/slacken/analysis/MinimizerMigration.scala:38-66), the
+ * arithmetic of `compareIndex` (Slacken.scala:332-341) -- the records of a SUBJECT library joined on the minimizer with those of a
+ * REFERENCE library (joinWith, :47) and counted by (t1 = the subject's taxon, t2 = the reference's).  The reference's table is the
+ * index; the subject's records are streamed through it, no second table is built.
+ *   slk_migration_create      reference: finalized (SLK_E_STATE otherwise), taxonomy not needed; one id column and not a shard of
+ *                             a table-sharded library (slk_index_set_shard), SLK_E_UNSUPPORTED otherwise.  depths[T] (copied):
+ *                             Taxonomy.depth (Taxonomy.scala:222-228) of the REFERENCE's taxonomy (bcTax, :42) for every id -- the
+ *                             rank depth of the nearest ranked ancestor-or-self, -1 for undefined ids; the caller computes it, the
+ *                             engine knows parents, not ranks.  An id outside [0, T) has depth -1 (the reference would throw an
+ *                             ArrayIndexOutOfBoundsException).  depths NULL with T 0: steps is written as 0, only the pairs mean
+ *                             something.
+ *   slk_migration_add         n records of the subject in host memory (left-aligned minimizer, taxon), any chunking, any order;
+ *                             n = 0 is allowed.  Records with taxon NONE are skipped (as slk_index_append skips them); a record
+ *                             whose minimizer the reference lacks leaves the join (:47) and is counted in `unmatched`, the others
+ *                             add 1 to their (t1, t2).  Both taxa are the caller's ids, also when slk_index_finalize renumbered
+ *                             the reference's; t1 is never looked at (any int32 but 0 is counted).  Synchronous on st, also on
+ *                             failure.
+ *   slk_migration_add_device  the same with pointers on the reference's GPU, asynchronous on st; a failure of the queued work
+ *                             shows at the next call on the handle.
+ *   slk_migration_result      synchronises the device; the triples so far sorted by t1 then t2, steps per distinct pair (:51-64):
+ *                             -100 when depth(t1) == -1, else -200 when depth(t2) == -1, else depth(t1) - depth(t2).
+ *                             *n_triples = their number; cap 0 queries only that, 0 < cap < *n_triples gives SLK_E_CAPACITY.
+ *                             matched / unmatched (nullable): records counted / records that left the join (an addition: the
+ *                             reference does not report them).  May be called repeatedly and between adds.
+ * The pair map starts at 2^SLK_MIGRATION_MAP_LOG2 slots (default 20, at least 10) and doubles between calls (and between the 4 M
+ * record pieces of a host call) while it is more than half full, so only a call (piece) that by itself brings more new pairs than
+ * the map has free slots can fill it: that call returns SLK_E_CAPACITY.  After SLK_E_CAPACITY or SLK_E_HIP the handle has counted an
+ * unknown part of its records and is spent: slk_migration_add* and slk_migration_result return SLK_E_STATE, slk_migration_destroy
+ * is what remains.  A call refused with SLK_E_INVALID counted nothing and leaves the handle usable. */
+typedef struct slk_migration slk_migration;
+int32_t slk_migration_create(slk_index *reference, const int32_t *depths, int32_t T, slk_migration **out);
+int32_t slk_migration_add(slk_migration *m, slk_stream *st, const int64_t *keys, const int32_t *taxa, uint64_t n);
+int32_t slk_migration_add_device(slk_migration *m, slk_stream *st, const int64_t *d_keys, const int32_t *d_taxa, uint64_t n);
+int32_t slk_migration_result(slk_migration *m, uint64_t *n_triples, int32_t *t1, int32_t *t2, int32_t *steps, uint64_t *count,
+                             uint64_t cap, uint64_t *matched, uint64_t *unmatched);
+void slk_migration_destroy(slk_migration *m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,7 +79,8 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
            "slk_shard_of", "slk_stream_set_merged_hits", "slk_classify_hits_device", "slk_shard_batch_rows", "slk_shard_chunk", "slk_shard_step_device",
            "slk_stream_last_deferred", "slk_table_slot", "slk_table_hash_of",
-           "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy"]
+           "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy",
+           "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy"]
 
 
 def lib_path():
@@ -164,6 +165,13 @@ def lib():
     L.slk_bracken_result.argtypes = [vp, C.POINTER(C.c_uint64), i32p, i32p, u64p, C.c_uint64]
     L.slk_bracken_destroy.argtypes = [vp]
     L.slk_bracken_destroy.restype = None
+    L.slk_migration_create.argtypes = [vp, i32p, C.c_int32, C.POINTER(vp)]
+    L.slk_migration_add.argtypes = [vp, vp, i64p, i32p, C.c_uint64]
+    L.slk_migration_add_device.argtypes = [vp, vp, i64p, i32p, C.c_uint64]
+    L.slk_migration_result.argtypes = [vp, C.POINTER(C.c_uint64), i32p, i32p, i32p, u64p, C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]
+    L.slk_migration_destroy.argtypes = [vp]
+    L.slk_migration_destroy.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -340,6 +348,50 @@ class BrackenWeights:
     def close(self):
         if getattr(self, "h", None):
             lib().slk_bracken_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MinimizerMigration:
+    """Minimizer migration of a subject library against a reference index (slk_migration_*: MinimizerMigration.taxaDistances,
+    S/slacken/analysis/MinimizerMigration.scala:38-66).  depths[t] = Taxonomy.depth(t) of the reference's taxonomy (None: steps
+    are 0).  add() takes the subject's records; result() gives (t1, t2, steps, count, matched, unmatched): numpy arrays sorted by
+    t1 then t2, and two ints."""
+
+    def __init__(self, reference_index, depths=None, stream=None):
+        self.index = reference_index
+        self.stream = stream if stream is not None else reference_index.stream()
+        h = C.c_void_p()
+        d = _np(depths, np.int32) if depths is not None else None
+        _check(lib().slk_migration_create(reference_index.h, _ptr(d), d.size if d is not None else 0, C.byref(h)))
+        self.h = h
+
+    def add(self, keys, taxa):
+        keys, taxa = _np(keys, np.int64), _np(taxa, np.int32)
+        assert keys.size == taxa.size
+        _check(lib().slk_migration_add(self.h, self.stream.h, _ptr(keys), _ptr(taxa), taxa.size))
+
+    def add_device(self, d_keys_ptr, d_taxa_ptr, n):
+        _check(lib().slk_migration_add_device(self.h, self.stream.h, d_keys_ptr, d_taxa_ptr, n))
+
+    def result(self):
+        n, matched, unmatched = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().slk_migration_result(self.h, C.byref(n), None, None, None, None, 0, C.byref(matched), C.byref(unmatched)))
+        t1, t2, steps = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        count = np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_migration_result(self.h, C.byref(n), _ptr(t1), _ptr(t2), _ptr(steps), _ptr(count), n.value,
+                                              C.byref(matched), C.byref(unmatched)))
+        return t1, t2, steps, count, matched.value, unmatched.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slk_migration_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -11,13 +11,13 @@
 // A lane whose window holds more than BR_MAPCAP taxa hands the rest of its chunk to a second launch of the same code with its map
 // in HBM (capacity W + 1: a window cannot hold more taxa than k-mers).
 #include "hostside.h"
+#include "pairmap.h"
 
 namespace {
 
 constexpr int BR_BLOCK = 64;          // window kernel: one wave per block
 constexpr int BR_MAPCAP = 16;         // taxa of one lane's window map in LDS
 constexpr uint32_t BR_CHUNK = 512;    // read starts per lane
-constexpr uint64_t BR_EMPTY = ~0ULL;  // free slot of the (source, dest) map
 constexpr uint8_t KF_START = 1, KF_IN = 2, KF_END = 4;  // k-mer flags: first / any / last k-mer of a distinct non-NONE super-mer
 
 __device__ __forceinline__ bool br_is_base(uint8_t c) {  // Supermers.nonAmbiguousRegex without whitespace (removed upstream, :311)
@@ -196,13 +196,7 @@ __device__ int32_t br_resolve(const BrArgs &A, MapRef &M) {
 __device__ __forceinline__ void br_flush(const BrArgs &A, int32_t source, int32_t dest, uint64_t reads) {
   if (reads == 0) return;
   const unsigned long long key = ((unsigned long long)(uint32_t)source << 32) | (uint32_t)dest;
-  uint64_t h = fmix64(key) & A.map_mask;
-  for (uint64_t probe = 0; probe <= A.map_mask; probe++) {
-    const unsigned long long prev = atomicCAS(&A.map_keys[h], (unsigned long long)BR_EMPTY, key);
-    if (prev == BR_EMPTY || prev == key) { atomicAdd(&A.map_counts[h], (unsigned long long)reads); return; }
-    h = (h + 1) & A.map_mask;
-  }
-  atomicOr(A.status, 2);
+  if (!pair_map_add(A.map_keys, A.map_counts, A.map_mask, key, (unsigned long long)reads, nullptr)) atomicOr(A.status, 2);
 }
 
 // Reads [p0, p1) of piece r, starting from the literal state of read p0 (true window counts, qtax short by D0).  count_first =
@@ -294,8 +288,8 @@ struct slk_bracken {
   slk_index *ix = nullptr;
   int32_t read_len = 0, W = 0;
   uint64_t max_fragment = 0;
-  uint64_t map_cap = 0;
-  DevBuf map_keys, map_counts, status;
+  PairMap map;   // (source << 32 | dest) -> reads
+  DevBuf status;
   DevBuf bases, offsets, span_keys, span_meta, span_taxon, span_count, ktax, kflag, qtax, qend, chunk0, source, chunk_piece,
       deficit, overflow, n_overflow, scratch;
   uint64_t batch_bytes = 1ULL << 30;   // bases per batch (SLK_BRACKEN_BATCH_MB): about 22 bytes of HBM each
@@ -306,30 +300,6 @@ struct slk_bracken {
   std::vector<uint32_t> h_chunk_piece;
   bool spent = false;   // a batch failed: the map holds part of it, so no count of this handle can be trusted any more
 };
-
-static int32_t br_grow_map(slk_bracken *b, hipStream_t s, uint64_t cap) {
-  HIPCHK(b->map_keys.ensure(cap * 8));
-  HIPCHK(b->map_counts.ensure(cap * 8));
-  HIPCHK(hipMemsetAsync(b->map_keys.p, 0xff, cap * 8, s));
-  HIPCHK(hipMemsetAsync(b->map_counts.p, 0, cap * 8, s));
-  b->map_cap = cap;
-  return SLK_OK;
-}
-
-// Reads the (source, dest) map back: pairs with their counts, unordered
-static int32_t br_read_map(slk_bracken *b, hipStream_t s, std::vector<uint64_t> &keys, std::vector<uint64_t> &counts) {
-  keys.resize(b->map_cap);
-  counts.resize(b->map_cap);
-  HIPCHK(hipMemcpyAsync(keys.data(), b->map_keys.p, b->map_cap * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(counts.data(), b->map_counts.p, b->map_cap * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  uint64_t w = 0;
-  for (uint64_t i = 0; i < b->map_cap; i++)
-    if (keys[i] != BR_EMPTY) { keys[w] = keys[i]; counts[w] = counts[i]; w++; }
-  keys.resize(w);
-  counts.resize(w);
-  return SLK_OK;
-}
 
 static void br_clear_batch(slk_bracken *b) {
   b->h_bases.clear();
@@ -378,7 +348,7 @@ static int32_t br_run_batch_device(slk_bracken *b, slk_stream *st) {
   A.chunk0 = b->chunk0.as<uint64_t>(); A.source = b->source.as<int32_t>(); A.chunk_piece = b->chunk_piece.as<uint32_t>();
   A.nchunks = nchunks; A.deficit = b->deficit.as<int32_t>();
   A.nodes = ix->d_nodes_orig; A.T = ix->T;
-  A.map_keys = b->map_keys.as<unsigned long long>(); A.map_counts = b->map_counts.as<unsigned long long>(); A.map_mask = b->map_cap - 1;
+  A.map_keys = b->map.k(); A.map_counts = b->map.c(); A.map_mask = b->map.cap - 1;
   A.overflow = b->overflow.as<uint4>(); A.n_overflow = b->n_overflow.as<unsigned int>(); A.status = b->status.as<int32_t>();
 
   // getSpans as slk_scan_device computes it (the fused wave-per-fragment scan where the window allows, else kernels.hip's)
@@ -411,7 +381,7 @@ static int32_t br_run_batch_device(slk_bracken *b, slk_stream *st) {
   }
   if (status & 2)
     return fail(SLK_E_CAPACITY, "bracken: more (source, dest) pairs than the map holds (%llu; SLK_BRACKEN_MAP_LOG2)",
-                (unsigned long long)b->map_cap);
+                (unsigned long long)b->map.cap);
   return SLK_OK;
 }
 
@@ -458,7 +428,7 @@ int32_t slk_bracken_create(slk_index *ix, int32_t read_len, uint64_t max_fragmen
   if (e != hipSuccess) { (void)hipGetLastError(); return fail(SLK_E_HIP, "bracken: %s", hipGetErrorString(e)); }
   // 2^22 = 4 M pairs (64 MiB): a standard library has a few hundred thousand
   const int map_log2 = (int)std::min(32L, std::max(10L, env_long("SLK_BRACKEN_MAP_LOG2", 22)));
-  rc = br_grow_map(b.get(), nullptr, 1ULL << map_log2);
+  rc = b->map.reset(nullptr, 1ULL << map_log2);
   if (rc == SLK_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(SLK_E_HIP, "bracken: map setup failed");
   if (rc) return rc;
   *out = b.release();
@@ -513,7 +483,7 @@ int32_t slk_bracken_result(slk_bracken *b, uint64_t *n, int32_t *dest, int32_t *
   rc = set_device(b->ix);
   if (rc) return rc;
   std::vector<uint64_t> keys, counts;
-  rc = br_read_map(b, nullptr, keys, counts);
+  rc = b->map.read(nullptr, keys, counts);
   if (rc) return rc;
   std::vector<size_t> order(keys.size());
   for (size_t i = 0; i < order.size(); i++) order[i] = i;

@@ -79,33 +79,6 @@ __global__ void __launch_bounds__(256) table_insert_kernel(TableBuild t, const i
   }
 }
 
-// One bucket per probe step; returns the stored taxon or 0 (NONE).
-__device__ __forceinline__ int32_t table_lookup(const TableView &t, uint64_t key) {
-  uint64_t h = fmix64(key);
-  uint32_t home;
-  uint64_t rem_hi;
-  table_slot(t.g, h, home, rem_hi);
-  uint64_t tmask = (1ULL << t.g.taxon_bits) - 1;
-  for (int d = 0; d <= t.max_disp; d++) {
-    const ulonglong2 *b = (const ulonglong2 *)(t.cells + ((uint64_t)table_bucket(t.g, home, (uint32_t)d) * CELLS));
-    uint64_t tag = rem_hi | (uint64_t)d;
-    uint64_t cells[CELLS];
-#pragma unroll
-    for (int c = 0; c < LPB; c++) { ulonglong2 v = b[c]; cells[2 * c] = v.x; cells[2 * c + 1] = v.y; }
-    bool has_empty = false;
-    int32_t found = 0;
-#pragma unroll
-    for (int c = 0; c < CELLS; c++) {
-      has_empty |= (cells[c] == 0);
-      if (cells[c] != 0 && cell_tag(t.g, cells[c]) == tag) found = (int32_t)(cells[c] & tmask);
-    }
-    if (found) return found;
-    if (has_empty) return 0;
-    if (t.g.flag && !(cells[0] & t.g.flag)) return 0;  // full, but no record ever went past it
-  }
-  return 0;
-}
-
 __global__ void __launch_bounds__(256) table_lookup_kernel(TableView t, const int64_t *__restrict__ keys, uint64_t n,
                                                            int32_t *__restrict__ out) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,0 +1,52 @@
+// pairmap.h -- the device-wide (a << 32 | b) -> uint64 count map that bracken.hip (source, dest) and migration.hip (t1, t2) add
+// into: open addressing with linear probing over a power-of-two number of slots, two parallel arrays in HBM.  Internal.
+#pragma once
+#include "hostside.h"
+
+constexpr uint64_t PAIR_EMPTY = ~0ULL;   // free slot (no pair is all ones: the low half is a taxon found in a table, > 0)
+
+// counts[slot of key] += n, claiming a slot if the key is new (then ++*n_pairs when given).  false: the map is full.
+__device__ __forceinline__ bool pair_map_add(unsigned long long *keys, unsigned long long *counts, uint64_t mask,
+                                             unsigned long long key, unsigned long long n, unsigned long long *n_pairs) {
+  uint64_t h = slk::fmix64(key) & mask;
+  for (uint64_t probe = 0; probe <= mask; probe++) {
+    const unsigned long long prev = atomicCAS(&keys[h], (unsigned long long)PAIR_EMPTY, key);
+    if (prev == PAIR_EMPTY || prev == key) {
+      atomicAdd(&counts[h], n);
+      if (n_pairs != nullptr && prev == PAIR_EMPTY) atomicAdd(n_pairs, 1ULL);
+      return true;
+    }
+    h = (h + 1) & mask;
+  }
+  return false;
+}
+
+struct PairMap {
+  DevBuf keys, counts;
+  uint64_t cap = 0;   // slots, a power of two
+  unsigned long long *k() const { return keys.as<unsigned long long>(); }
+  unsigned long long *c() const { return counts.as<unsigned long long>(); }
+  // an empty map of `slots` slots (whatever it held is gone), ordered on s
+  int32_t reset(hipStream_t s, uint64_t slots) {
+    HIPCHK(keys.ensure(slots * 8));
+    HIPCHK(counts.ensure(slots * 8));
+    HIPCHK(hipMemsetAsync(keys.p, 0xff, slots * 8, s));
+    HIPCHK(hipMemsetAsync(counts.p, 0, slots * 8, s));
+    cap = slots;
+    return SLK_OK;
+  }
+  // the pairs with their counts, unordered; synchronises s
+  int32_t read(hipStream_t s, std::vector<uint64_t> &hk, std::vector<uint64_t> &hc) const {
+    hk.resize(cap);
+    hc.resize(cap);
+    HIPCHK(hipMemcpyAsync(hk.data(), keys.p, cap * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hc.data(), counts.p, cap * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t w = 0;
+    for (uint64_t i = 0; i < cap; i++)
+      if (hk[i] != PAIR_EMPTY) { hk[w] = hk[i]; hc[w] = hc[i]; w++; }
+    hk.resize(w);
+    hc.resize(w);
+    return SLK_OK;
+  }
+};

@@ -9,6 +9,7 @@
 //   inputs           S/kmers/input/FileInputs.scala:64-85,156-221, InputReader.scala:105-131 (FASTA, FASTQ, gz, pairing)
 //   per-read output  S/slacken/Classifier.scala:41-44,124-147,184-227, S/slacken/TaxonCounts.scala:94-121
 //   report           S/slacken/KrakenReport.scala (taxonomy.hpp)
+//   compare-index    S/slacken/Slacken.scala:332-341, S/slacken/analysis/MinimizerMigration.scala:33-85 (migration.hpp)
 // Host-only subcommands (`report`, `parse`, `props`) exist so that this layer can be tested without a GPU.
 #include <atomic>
 #include <chrono>
@@ -20,6 +21,7 @@
 #include <algorithm>
 
 #include "../../include/slacken_amd.h"
+#include "migration.hpp"
 #include "output.hpp"
 #include "pack.hpp"
 #include "parquet_source.hpp"
@@ -1445,6 +1447,95 @@ static int cmd_kmer_distrib(int argc, char **argv) {
   return 0;
 }
 
+// ---- compare-index (Slacken.scala:332-341): MinimizerMigration(subject, reference).run(output) ----
+// The table on stdout, OUTPUT_taxaToRoot_report.txt beside it (MinimizerMigration.scala:68-84)
+static void write_migration_files(const Taxonomy &subject_tax, const std::vector<int32_t> &t1, const std::vector<int32_t> &t2,
+                                  const std::vector<int32_t> &steps, const std::vector<uint64_t> &count, const std::string &output) {
+  const std::string path = output + "_taxaToRoot_report.txt";
+  if (fs::path(path).has_parent_path()) fs::create_directories(fs::path(path).parent_path());
+  std::ofstream rep(path);
+  if (!rep) die("cannot write " + path);
+  write_migration(subject_tax, t1, t2, steps, count, std::cout, rep);
+  std::cout.flush();
+}
+
+// migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV OUTPUT: what compare-index writes, from "t1 \t t2 \t count"
+// lines (host only: the outputs without a GPU)
+static int cmd_migration_report(int argc, char **argv) {
+  if (argc < 4) die("usage: migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV OUTPUT");
+  const Taxonomy subject_tax = Taxonomy::load(argv[0]), reference_tax = Taxonomy::load(argv[1]);
+  std::ifstream f(argv[2]);
+  if (!f) die(std::string("cannot open ") + argv[2]);
+  std::vector<int32_t> t1, t2, steps;
+  std::vector<uint64_t> count;
+  long long a, b;
+  unsigned long long n;
+  while (f >> a >> b >> n) {
+    t1.push_back((int32_t)a); t2.push_back((int32_t)b); count.push_back(n);
+    steps.push_back(migration_steps(reference_tax, (Taxon)a, (Taxon)b));
+  }
+  write_migration_files(subject_tax, t1, t2, steps, count, argv[3]);
+  return 0;
+}
+
+static int cmd_compare_index(int argc, char **argv) {
+  std::string subject, reference, output;
+  std::vector<int> devices{0};
+  for (int i = 0; i < argc; i++) {
+    std::string a = argv[i];
+    auto next = [&]() { if (i + 1 >= argc) die("missing value for " + a); return std::string(argv[++i]); };
+    if (a == "-i" || a == "--index") subject = next();
+    else if (a == "-r" || a == "--reference") reference = next();
+    else if (a == "-o" || a == "--output") output = next();
+    else if (a == "--devices") {
+      const std::string v = next();
+      if (v == "all" || v.find(',') != std::string::npos) die("compare-index takes one device: the reference's table must fit one GPU");
+      devices = parse_device_list(v);
+    }
+    else if (a == "--shard-table")
+      die("--shard-table is not supported by compare-index: the reference's table must fit one GPU\n"
+          "usage: compare-index -i SUBJECT -r REFERENCE -o OUTPUT [--devices D]");
+    else die("unknown option " + a);
+  }
+  if (subject.empty() || reference.empty() || output.empty()) die("usage: compare-index -i SUBJECT -r REFERENCE -o OUTPUT [--devices D]");
+  // "They must use the same minimizer scheme for the comparison to be meaningful" (MinimizerMigration.scala:31): checked here
+  const IndexParams sp = read_index_params(subject), rp0 = read_index_params(reference);
+  if (sp.k != rp0.k || sp.m != rp0.m || sp.spaces != rp0.spaces || sp.xorMask != rp0.xorMask || sp.canonical != rp0.canonical)
+    die("the two libraries do not share a minimizer scheme (k, m, minimizerSpaces, XORmask, canonical of " + subject + ".properties and " +
+        reference + ".properties differ): their minimizers cannot be compared");
+  const Taxonomy subject_tax = Taxonomy::load(subject + "_taxonomy");
+  IndexParams rp;
+  Taxonomy reference_tax;
+  DeviceIndex dev;
+  dev.devices = devices;
+  load_index(reference, rp, reference_tax, dev);
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<int32_t> depths(reference_tax.size());
+  for (Taxon t = 0; t < reference_tax.size(); t++) depths[t] = reference_tax.depth(t);
+  slk_migration *mg = nullptr;
+  SLK_CALL(slk_migration_create(dev.ix, depths.data(), (int32_t)depths.size(), &mg));
+  // the subject's records stream through: one chunk in host memory, no second table
+  const int W = (sp.m + 31) / 32;
+  uint64_t n_read = 0;
+  auto add = [&](const int64_t *keys, const int32_t *taxa, uint64_t c) {
+    n_read += c;
+    SLK_CALL(slk_migration_add(mg, dev.st, keys, taxa, c));
+  };
+  if (!fs::exists(subject + ".slkrec") && parquet_available() && fs::is_directory(subject)) parquet_for_each_batch(subject, W, add);
+  else RecordFile(subject, W).for_each_chunk(true, add);
+  uint64_t n = 0, matched = 0, unmatched = 0;
+  SLK_CALL(slk_migration_result(mg, &n, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr));
+  std::vector<int32_t> t1(n), t2(n), steps(n);
+  std::vector<uint64_t> count(n);
+  if (n) SLK_CALL(slk_migration_result(mg, &n, t1.data(), t2.data(), steps.data(), count.data(), n, &matched, &unmatched));
+  else SLK_CALL(slk_migration_result(mg, &n, nullptr, nullptr, nullptr, nullptr, 0, &matched, &unmatched));
+  slk_migration_destroy(mg);
+  write_migration_files(subject_tax, t1, t2, steps, count, output);
+  std::cerr << "compare-index: " << n_read << " records read, " << matched << " matched, " << unmatched << " unmatched, " << n
+            << " distinct pairs, " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+  return 0;
+}
+
 static const char *HELP =
     "slacken-amd -- Slacken's classify path on an MI355X (libslacken_amd.so)\n"
     "  slacken-amd [--partitions N] classify  -i INDEX -o OUTPUT [options] FILES...\n"
@@ -1474,7 +1565,12 @@ static const char *HELP =
     "  slacken-amd bracken-build -i INDEX --library DIR [--read-len L (100)] [--devices LIST] (Slacken.scala:264-279): Bracken weights\n"
     "  of every genome of DIR labelled in DIR/seqid2taxid.map, written to INDEX_bracken/databaseLmers.kmer_distrib; the records are\n"
     "  shared out over the devices\n"
-    "host-only helpers: report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
+    "  slacken-amd compare-index -i SUBJECT -r REFERENCE -o OUTPUT [--devices D] (also spelled compareIndex; Slacken.scala:332-341):\n"
+    "  the records of library SUBJECT joined on the minimizer with those of library REFERENCE (normally a superset; its table goes to\n"
+    "  one GPU).  stdout: how many records moved up by how many standard ranks; OUTPUT_taxaToRoot_report.txt: a Kraken report of the\n"
+    "  taxa whose minimizers went to the root or to cellular organisms.  Both libraries must share k, m, spaces, mask and canonical\n"
+    "host-only helpers: report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
+    "  migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV (t1 t2 count) OUTPUT | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
     "environment: SLK_HOST_THREADS (formatting/decoding threads), SLK_INPUT_STREAMS (input files read side by side, default 8),\n"
     "             SLK_PARSE_THREADS (threads parsing one plain input file, default min(8, cores/2)), SLK_GZIP_LEVEL (1..9, default zlib's),\n"
     "             SLK_GZ_THREADS (threads inflating one gzip input file, default min(16, cores / files read side by side); 0: zlib),\n"
@@ -1484,7 +1580,7 @@ static const char *HELP =
 int main(int argc, char **argv) {
   int i = 1;
   while (i < argc && std::string(argv[i]) == "--partitions") i += 2;  // global Spark option of the reference: accepted, unused
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|compare-index|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1500,8 +1596,10 @@ int main(int argc, char **argv) {
     if (cmd == "taxonomy") return cmd_taxonomy(argc - i, argv + i);
     if (cmd == "bracken-build") return cmd_bracken_build(argc - i, argv + i);
     if (cmd == "kmer-distrib") return cmd_kmer_distrib(argc - i, argv + i);
+    if (cmd == "compare-index" || cmd == "compareIndex") return cmd_compare_index(argc - i, argv + i);
+    if (cmd == "migration-report") return cmd_migration_report(argc - i, argv + i);
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command " + cmd + " (this engine implements `classify`, `classify2` and `bracken-build`; the reference's other subcommands are out of scope)");
+  die("unknown command " + cmd + " (this engine implements `classify`, `classify2`, `bracken-build` and `compare-index`; the reference's other subcommands are out of scope)");
 }
