@@ -13,16 +13,23 @@ CLI := slacken_amd/bin/slacken-amd
 
 GATHER := slacken_amd/lib/libslk_gather.so
 
-all: $(LIB) $(CLI) $(GATHER) oracle
+STREAM_SUM := slacken_amd/lib/libslk_stream_sum.so
+
+all: $(LIB) $(CLI) $(GATHER) $(STREAM_SUM) oracle
 
 # measurement helper of bench.py (the part's random-request rate, measured in the bench run): not linked or loaded by the product
 $(GATHER): tools/gather_rate.hip
 	@mkdir -p slacken_amd/lib
 	$(HIPCC) -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -shared -o $@ tools/gather_rate.hip
 
-$(LIB): $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h slacken_amd/host/pack.hpp include/slacken_amd.h
+# measurement helper of tools/bench_taxon_counts.py (a coalesced read-and-sum, the yardstick of the taxon count): not product either
+$(STREAM_SUM): tools/stream_sum.hip
 	@mkdir -p slacken_amd/lib
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip -ldl
+	$(HIPCC) -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -shared -o $@ tools/stream_sum.hip
+
+$(LIB): $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h slacken_amd/host/pack.hpp include/slacken_amd.h
+	@mkdir -p slacken_amd/lib
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip -ldl
 
 # Parquet input of the CLI: the Arrow C++ libraries inside the pyarrow wheel, if there is one (no Arrow dev package here)
 PYARROW_DIR := $(shell python3 -c "import pyarrow, os; print(os.path.dirname(pyarrow.__file__))" 2>/dev/null)
@@ -37,7 +44,7 @@ slacken_amd/bin/parquet_source.o: slacken_amd/host/parquet_source.cpp slacken_am
 	@mkdir -p slacken_amd/bin
 	g++ -O2 -std=c++20 -Wall $(PQ_CXXFLAGS) -c -o $@ slacken_amd/host/parquet_source.cpp
 
-$(CLI): slacken_amd/bin/parquet_source.o slacken_amd/host/slacken_cli.cpp slacken_amd/host/taxonomy.hpp slacken_amd/host/seqio.hpp slacken_amd/host/pargz.hpp slacken_amd/host/parbz2.hpp slacken_amd/host/titles.hpp slacken_amd/host/output.hpp slacken_amd/host/migration.hpp slacken_amd/host/pack.hpp include/slacken_amd.h $(LIB)
+$(CLI): slacken_amd/bin/parquet_source.o slacken_amd/host/slacken_cli.cpp slacken_amd/host/taxonomy.hpp slacken_amd/host/seqio.hpp slacken_amd/host/pargz.hpp slacken_amd/host/parbz2.hpp slacken_amd/host/titles.hpp slacken_amd/host/output.hpp slacken_amd/host/migration.hpp slacken_amd/host/stats.hpp slacken_amd/host/pack.hpp include/slacken_amd.h $(LIB)
 	@mkdir -p slacken_amd/bin
 	g++ -O2 -std=c++17 -Wall -o $@ slacken_amd/host/slacken_cli.cpp slacken_amd/bin/parquet_source.o $(PQ_LDFLAGS) -Lslacken_amd/lib -lslacken_amd -lz -ldl -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
 
@@ -45,7 +52,7 @@ oracle:
 	$(MAKE) -C oracle
 
 clean:
-	rm -f $(LIB) $(GATHER)
+	rm -f $(LIB) $(GATHER) $(STREAM_SUM)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle clean

@@ -174,6 +174,18 @@ int32_t slk_index_finalize(slk_index *ix);
  * keys: id_longs words per record, row-major.  The order is unspecified (a set).  *n_records receives the number of records; if it exceeds capacity only the first
  * `capacity` were written and SLK_E_CAPACITY is returned.  keys/taxa may be NULL with capacity 0 to query the count. */
 int32_t slk_index_export(const slk_index *ix, int64_t *keys, int32_t *taxa, uint64_t capacity, uint64_t *n_records);
+/* Records per taxon of the resident table: replaces records.groupBy("taxon").agg(count("*")) -- KeyValueIndex.scala:241
+ * (showIndexStats) and :278 (report); the depth histograms (:326-336) are sums of the same pairs.  One streaming pass over the
+ * table on the device (taxstats.hip); nothing but the pairs crosses to the host.  (taxa[i], counts[i]) for i < *n_taxa, ascending
+ * taxon, ids as the caller gave them (also on an index renumbered to dense ids by slk_index_finalize); *n_records (nullable) = the
+ * sum of the counts.  The capacity protocol of slk_index_export: taxa/counts may be NULL with capacity 0 to query *n_taxa; if
+ * *n_taxa exceeds a capacity > 0 the first `capacity` pairs were written and SLK_E_CAPACITY is returned.  Works before and after
+ * slk_index_finalize, after the table has grown, and on a dynamic library (slk_index_add_sequences); a shard of a table-sharded
+ * library (slk_index_set_shard) counts its own share.  The index is not changed.  One id column only (SLK_E_UNSUPPORTED
+ * otherwise, as the staged device entries); a spent index returns SLK_E_STATE.  Synchronous; not to be called while another
+ * thread adds records to the same index. */
+int32_t slk_index_taxon_counts(const slk_index *ix, int32_t *taxa, uint64_t *counts, uint64_t capacity, uint64_t *n_taxa,
+                               uint64_t *n_records);
 int32_t slk_index_get_info(const slk_index *ix, slk_index_info *out);
 /* The table's bucket choice as host arithmetic (no GPU): the range reduction of a 64-bit hash onto ANY number of buckets
  * (32 <= nbuckets <= 2^32) -- home = (top q bits of hash) * nbuckets >> q, q = ceil(log2(nbuckets)) -- with the remainder a cell

@@ -73,7 +73,7 @@ HIT_DTYPE = np.dtype([("taxon", "<i4"), ("count", "<i4")])
 # every symbol include/slacken_amd.h declares
 EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc", "slk_host_register", "slk_host_free", "slk_index_create", "slk_index_append",
            "slk_index_append_device", "slk_index_set_shard", "slk_index_set_taxonomy", "slk_index_finalize", "slk_index_get_info",
-           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
+           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_taxon_counts", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
            "slk_stream_hip_stream", "slk_stream_destroy", "slk_spans_batch", "slk_spans_batch_wide", "slk_classify_batch",
            "slk_classify_batch_packed", "slk_pack_bases",
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
@@ -127,6 +127,7 @@ def lib():
     L.slk_index_add_sequences.argtypes = [vp, u8p, u64p, i32p, C.c_uint64]
     L.slk_index_add_sequences_device.argtypes = [vp, u8p, u64p, i32p, C.c_uint64]
     L.slk_index_export.argtypes = [vp, i64p, i32p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.slk_index_taxon_counts.argtypes = [vp, i32p, u64p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.slk_index_destroy.argtypes = [vp]
     L.slk_index_destroy.restype = None
     L.slk_stream_create.argtypes = [vp, C.POINTER(vp)]
@@ -290,6 +291,16 @@ class Index:
             return rows[order], taxa[order]
         order = np.argsort(keys, kind="stable")
         return keys[order], taxa[order]
+
+    def taxon_counts(self):
+        """(taxa int32, counts uint64) of the resident table: records per taxon, ascending taxon, the caller's ids
+        (slk_index_taxon_counts: counted on the device, only the pairs come to the host)."""
+        n, total = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().slk_index_taxon_counts(self.h, None, None, 0, C.byref(n), C.byref(total)))
+        taxa, counts = np.zeros(n.value, np.int32), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_index_taxon_counts(self.h, _ptr(taxa), _ptr(counts), n.value, C.byref(n), C.byref(total)))
+        return taxa, counts
 
     def finalize(self):
         _check(lib().slk_index_finalize(self.h))

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "stats.hpp"
 #include "taxonomy.hpp"
 
 namespace slk_host {
@@ -20,27 +21,14 @@ inline int32_t migration_steps(const Taxonomy &reference, Taxon t1, Taxon t2) {
   return l1 == -1 ? -100 : l2 == -1 ? -200 : l1 - l2;
 }
 
-// groupBy("steps").agg(count("steps")).sort("steps").show() (:70-72): right-aligned cells as wide as the column's widest entry (at
-// least 3), rules above the header, below it and after the last row, and the empty line show()'s println leaves.  At most 19 step
+// groupBy("steps").agg(count("steps")).sort("steps").show() (:70-72) in show()'s layout (stats.hpp: show_table).  At most 19 step
 // values exist, so show()'s cut at 20 rows never applies.
 inline std::string steps_histogram_text(const std::vector<int32_t> &steps, const std::vector<uint64_t> &count) {
   std::map<int32_t, uint64_t> hist;
   for (size_t i = 0; i < steps.size(); i++) hist[steps[i]] += count[i];
-  const std::string head[2] = {"steps", "count(steps)"};
-  std::vector<std::string> cells[2];
-  size_t width[2] = {std::max<size_t>(3, head[0].size()), std::max<size_t>(3, head[1].size())};
-  for (auto &e : hist) {
-    cells[0].push_back(std::to_string(e.first));
-    cells[1].push_back(std::to_string(e.second));
-    for (int c = 0; c < 2; c++) width[c] = std::max(width[c], cells[c].back().size());
-  }
-  const std::string rule = "+" + std::string(width[0], '-') + "+" + std::string(width[1], '-') + "+\n";
-  auto row = [&](const std::string &a, const std::string &b) {
-    return "|" + std::string(width[0] - a.size(), ' ') + a + "|" + std::string(width[1] - b.size(), ' ') + b + "|\n";
-  };
-  std::string out = rule + row(head[0], head[1]) + rule;
-  for (size_t i = 0; i < cells[0].size(); i++) out += row(cells[0][i], cells[1][i]);
-  return out + rule + "\n";
+  std::vector<std::vector<std::string>> rows;
+  for (auto &e : hist) rows.push_back({std::to_string(e.first), std::to_string(e.second)});
+  return show_table({"steps", "count(steps)"}, rows);
 }
 
 // t1 -> records of the pairs that moved into {ROOT, cellular organisms} from outside it (:77-79)

@@ -10,6 +10,7 @@
 //   per-read output  S/slacken/Classifier.scala:41-44,124-147,184-227, S/slacken/TaxonCounts.scala:94-121
 //   report           S/slacken/KrakenReport.scala (taxonomy.hpp)
 //   compare-index    S/slacken/Slacken.scala:332-341, S/slacken/analysis/MinimizerMigration.scala:33-85 (migration.hpp)
+//   stats, inspect   S/slacken/Slacken.scala:281-330, S/slacken/KeyValueIndex.scala:240-306,326-336 (stats.hpp), without --library
 // Host-only subcommands (`report`, `parse`, `props`) exist so that this layer can be tested without a GPU.
 #include <atomic>
 #include <chrono>
@@ -26,6 +27,7 @@
 #include "pack.hpp"
 #include "parquet_source.hpp"
 #include "seqio.hpp"
+#include "stats.hpp"
 #include "taxonomy.hpp"
 
 using namespace slk_host;
@@ -1536,6 +1538,161 @@ static int cmd_compare_index(int argc, char **argv) {
   return 0;
 }
 
+// ---- stats (Slacken.scala:281-315) and inspect (:317-330) without --library: functions of the records per taxon ----
+static const char *STATS_USAGE = "usage: stats -i INDEX [--histogram] [--devices D]";
+static const char *INSPECT_USAGE = "usage: inspect -i INDEX -o OUTPUT [--labels FILE] [--devices D]";
+
+// OUTPUT_min_report.txt, OUTPUT_genome_report.txt and, with a label file, OUTPUT_missing_report.txt (KeyValueIndex.scala:274-306)
+static void write_inspect_files(const Taxonomy &tax, const TaxonCounts &counts, const std::string &output, const std::string &labels) {
+  auto open = [&](const char *suffix, std::ofstream &f) {
+    const std::string path = output + suffix;
+    if (fs::path(path).has_parent_path()) fs::create_directories(fs::path(path).parent_path());
+    f.open(path);
+    if (!f) die("cannot write " + path);
+  };
+  std::set<Taxon> label_taxa;
+  if (!labels.empty()) {
+    std::ifstream lf(labels);
+    if (!lf) die("cannot open " + labels);
+    label_taxa = read_label_taxa(lf);
+  }
+  std::ofstream f1, f2, f3;
+  open("_min_report.txt", f1);
+  write_min_report(tax, counts, f1);
+  open("_genome_report.txt", f2);
+  write_genome_report(tax, counts, f2);
+  if (!labels.empty()) {
+    open("_missing_report.txt", f3);
+    write_missing_report(tax, counts, label_taxa, f3);
+  }
+}
+
+// stats-report TAXONOMY_DIR COUNTS_TSV M [--histogram] [-o OUTPUT [--labels FILE]]: what `stats` prints after the splitter lines,
+// or with -o what `inspect` writes, from "taxon \t count" lines (host only: the outputs without a GPU)
+static int cmd_stats_report(int argc, char **argv) {
+  const char *usage = "usage: stats-report TAXONOMY_DIR COUNTS_TSV M [--histogram] [-o OUTPUT [--labels FILE]]";
+  std::vector<std::string> pos;
+  std::string output, labels;
+  bool histogram = false;
+  for (int i = 0; i < argc; i++) {
+    std::string a = argv[i];
+    auto next = [&]() { if (i + 1 >= argc) die("missing value for " + a); return std::string(argv[++i]); };
+    if (a == "--histogram") histogram = true;
+    else if (a == "-o" || a == "--output") output = next();
+    else if (a == "--labels") labels = next();
+    else if (a.size() > 1 && a[0] == '-') die("unknown option " + a + "\n" + usage);
+    else pos.push_back(a);
+  }
+  if (pos.size() != 3 || (!labels.empty() && output.empty())) die(usage);
+  const Taxonomy tax = Taxonomy::load(pos[0]);
+  std::ifstream f(pos[1]);
+  if (!f) die("cannot open " + pos[1]);
+  std::map<Taxon, uint64_t> sum;   // (any order, a taxon may repeat)
+  long long t;
+  unsigned long long c;
+  while (f >> t >> c) sum[(Taxon)t] += c;
+  const TaxonCounts counts(sum.begin(), sum.end());
+  if (output.empty()) std::cout << stats_text(tax, counts, std::stoi(pos[2]), histogram);
+  else write_inspect_files(tax, counts, output, labels);
+  return 0;
+}
+
+// the options stats and inspect share; what neither supports is refused on the command line alone, before any library is read
+struct StatsOptions {
+  std::string index, output, labels;
+  bool histogram = false;
+  std::vector<int> devices{0};
+};
+static StatsOptions parse_stats_options(const char *cmd, const char *usage, bool inspect, int argc, char **argv) {
+  StatsOptions o;
+  for (int i = 0; i < argc; i++) {
+    std::string a = argv[i];
+    auto next = [&]() { if (i + 1 >= argc) die("missing value for " + a); return std::string(argv[++i]); };
+    if (a == "-i" || a == "--index") o.index = next();
+    else if (inspect && (a == "-o" || a == "--output")) o.output = next();
+    else if (inspect && a == "--labels") o.labels = next();
+    else if (!inspect && a == "--histogram") o.histogram = true;
+    else if (a == "-l" || a == "--library")
+      die(std::string("--library is not supported by ") + cmd + ": genome coverage (IndexStatistics) is not part of this engine\n" + usage);
+    else if (a == "--devices") {
+      const std::string v = next();
+      if (v == "all" || v.find(',') != std::string::npos) die(std::string(cmd) + " takes one device: the library's table must fit one GPU");
+      o.devices = parse_device_list(v);
+    }
+    else if (a == "--shard-table")
+      die(std::string("--shard-table is not supported by ") + cmd + ": the library's table must fit one GPU\n" + usage);
+    else die("unknown option " + a + "\n" + usage);
+  }
+  if (o.index.empty() || (inspect && o.output.empty())) die(usage);
+  return o;
+}
+
+// the (taxon, records) pairs of the resident table, counted on the device
+static TaxonCounts device_taxon_counts(const slk_index *ix) {
+  uint64_t n = 0, records = 0;
+  SLK_CALL(slk_index_taxon_counts(ix, nullptr, nullptr, 0, &n, &records));
+  std::vector<int32_t> taxa(n);
+  std::vector<uint64_t> counts(n);
+  if (n) SLK_CALL(slk_index_taxon_counts(ix, taxa.data(), counts.data(), n, &n, &records));
+  TaxonCounts out(n);
+  for (uint64_t i = 0; i < n; i++) out[i] = {taxa[i], counts[i]};
+  return out;
+}
+
+static std::string java_binary_string(uint64_t x) {   // java.lang.Long.toBinaryString: no leading zeros
+  std::string s;
+  for (; x; x >>= 1) s.insert(s.begin(), (char)('0' + (x & 1)));
+  return s.empty() ? "0" : s;
+}
+
+// The splitter lines of Slacken.scala:291-302.  The masks are one word (m <= 32, which the count needs anyway): SpacedSeed.spaceMask
+// (MinimizerPriorities.scala:287-300) and RandomXOR.mask (:146-160), both left aligned.  The reference's third line is the toString
+// of a Scala object; this one names the parameters in the engine's words.
+static void print_splitter_lines(const IndexParams &ip) {
+  if (ip.spaces > 0) {
+    const int r = ip.m % 32;
+    uint64_t sm = r == 0 ? ~0ULL : ~0ULL << ((32 - r) * 2);
+    const uint64_t final_bits = 3ULL << ((64 - r * 2) & 63);
+    for (int i = 0; i < ip.spaces; i++) sm = (sm << 4) | final_bits;
+    std::cout << "Spaced mask (left aligned) " << java_binary_string(sm) << "\n";
+    std::cout << "Toggle mask (left aligned) " << java_binary_string(r == 0 ? ip.xorMask : ip.xorMask << (64 - r * 2)) << "\n";
+    std::cout << "Inner splitter randomXOR m=" << ip.m << " XORmask=" << (int64_t)ip.xorMask << " canonical=" << (ip.canonical ? "true" : "false") << "\n";
+  } else {
+    std::cout << "Splitter randomXOR k=" << ip.k << " m=" << ip.m << " XORmask=" << (int64_t)ip.xorMask << " canonical="
+              << (ip.canonical ? "true" : "false") << "\n";
+  }
+}
+
+static void refuse_wide(const char *cmd, const IndexParams &ip) {
+  if (ip.m > 32) die(std::string(cmd) + " supports minimizers of up to 32 nt (this library has m=" + std::to_string(ip.m) + ")");
+}
+
+static int cmd_stats(int argc, char **argv) {
+  const StatsOptions o = parse_stats_options("stats", STATS_USAGE, false, argc, argv);
+  refuse_wide("stats", read_index_params(o.index));
+  IndexParams ip;
+  Taxonomy tax;
+  DeviceIndex dev;
+  dev.devices = o.devices;
+  load_index(o.index, ip, tax, dev);
+  print_splitter_lines(ip);
+  std::cout << stats_text(tax, device_taxon_counts(dev.ix), ip.m, o.histogram);
+  std::cout.flush();
+  return 0;
+}
+
+static int cmd_inspect(int argc, char **argv) {
+  const StatsOptions o = parse_stats_options("inspect", INSPECT_USAGE, true, argc, argv);
+  refuse_wide("inspect", read_index_params(o.index));
+  IndexParams ip;
+  Taxonomy tax;
+  DeviceIndex dev;
+  dev.devices = o.devices;
+  load_index(o.index, ip, tax, dev);
+  write_inspect_files(tax, device_taxon_counts(dev.ix), o.output, o.labels);
+  return 0;
+}
+
 static const char *HELP =
     "slacken-amd -- Slacken's classify path on an MI355X (libslacken_amd.so)\n"
     "  slacken-amd [--partitions N] classify  -i INDEX -o OUTPUT [options] FILES...\n"
@@ -1569,7 +1726,14 @@ static const char *HELP =
     "  the records of library SUBJECT joined on the minimizer with those of library REFERENCE (normally a superset; its table goes to\n"
     "  one GPU).  stdout: how many records moved up by how many standard ranks; OUTPUT_taxaToRoot_report.txt: a Kraken report of the\n"
     "  taxa whose minimizers went to the root or to cellular organisms.  Both libraries must share k, m, spaces, mask and canonical\n"
+    "  slacken-amd stats -i INDEX [--histogram] [--devices D] (Slacken.scala:281-315): the splitter's masks, then how many taxa the\n"
+    "  library stores, how many of them are leaves and how many records lie on leaves; with --histogram the records and the stored\n"
+    "  taxa by rank depth instead.  Counted on the GPU from the resident table (--library, the genome coverage check, is not supported)\n"
+    "  slacken-amd inspect -i INDEX -o OUTPUT [--labels FILE] [--devices D] (Slacken.scala:317-330): Kraken-style reports of the\n"
+    "  library's contents, OUTPUT_min_report.txt (records per taxon) and OUTPUT_genome_report.txt (one per stored taxon); with\n"
+    "  --labels (seqid TAB taxon lines) OUTPUT_missing_report.txt of the labelled taxa the library does not store\n"
     "host-only helpers: report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
+    "  stats-report TAXONOMY_DIR COUNTS_TSV (taxon count) M [--histogram] [-o OUTPUT [--labels FILE]] |\n"
     "  migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV (t1 t2 count) OUTPUT | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
     "environment: SLK_HOST_THREADS (formatting/decoding threads), SLK_INPUT_STREAMS (input files read side by side, default 8),\n"
     "             SLK_PARSE_THREADS (threads parsing one plain input file, default min(8, cores/2)), SLK_GZIP_LEVEL (1..9, default zlib's),\n"
@@ -1580,7 +1744,7 @@ static const char *HELP =
 int main(int argc, char **argv) {
   int i = 1;
   while (i < argc && std::string(argv[i]) == "--partitions") i += 2;  // global Spark option of the reference: accepted, unused
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|compare-index|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|compare-index|stats|inspect|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1598,8 +1762,14 @@ int main(int argc, char **argv) {
     if (cmd == "kmer-distrib") return cmd_kmer_distrib(argc - i, argv + i);
     if (cmd == "compare-index" || cmd == "compareIndex") return cmd_compare_index(argc - i, argv + i);
     if (cmd == "migration-report") return cmd_migration_report(argc - i, argv + i);
+    // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
+    //  they were commands)
+    if (cmd == "stats" && i < argc) return cmd_stats(argc - i, argv + i);
+    if (cmd == "inspect" && i < argc) return cmd_inspect(argc - i, argv + i);
+    if (cmd == "stats-report") return cmd_stats_report(argc - i, argv + i);
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command " + cmd + " (this engine implements `classify`, `classify2`, `bracken-build` and `compare-index`; the reference's other subcommands are out of scope)");
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `bracken-build`, `compare-index`, `stats -i INDEX` and "
+      "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }
