@@ -73,7 +73,10 @@ typedef struct {
 /* Sizing of the HBM-resident record table (the engine's replacement for the bucketed Parquet table scanned by the
  * join at S/slacken/Classifier.scala:84). */
 typedef struct {
-  uint64_t expected_records; /* upper bound on records that will be appended */
+  uint64_t expected_records; /* upper bound on records that will be appended.  One id column: a bound that proves too low makes
+                                the table grow.  Several id columns (m > 32): the table does NOT grow; it has as many slots as
+                                the power of two at or above 2 x expected_records (16 at least), takes records until every
+                                slot is used, and fails with SLK_E_CAPACITY beyond that (see slk_index_append) */
   int32_t max_taxon;         /* largest taxon id that will be appended (0 = derive from nothing: 2^22-1) */
   float load_factor;         /* target cells-used fraction, 0 = default: 0.55 while the table then takes at most 55 % of the device's
                                 FREE memory, more for larger libraries (0.85 at most); less for tables whose cells leave a short
@@ -86,7 +89,8 @@ typedef struct {
   uint64_t table_bytes;
   int32_t bucket_bits, taxon_bits, disp_bits; /* bucket_bits = ceil(log2(buckets)) */
   int32_t max_displacement; /* largest bucket displacement in use (0 = every record in its home bucket) */
-  uint64_t duplicate_keys;  /* appended records whose key was already present (contract violation; first kept) */
+  uint64_t duplicate_keys;  /* appended records whose key was already present (contract violation; first kept) -- tables with
+                               one and with several id columns alike; of two such records in ONE call either may be the first */
   int32_t taxonomy_size;
   int32_t device;
   int32_t dense_taxa;       /* > 0: taxon ids beyond 22 bits were renumbered internally at slk_index_finalize (the number of
@@ -95,7 +99,8 @@ typedef struct {
   float load_factor;        /* the load the table was sized for: slk_table_config.load_factor, or what the default chose from the
                                device's free memory (runs on parts with different memory are comparable by this) */
   int32_t grown;            /* times the table moved to a larger geometry because a record found no cell within reach
-                               (more records than expected_records: the load never fails for that) */
+                               (more records than expected_records: the load never fails for that).  Always 0 with several id
+                               columns: those tables do not grow */
 } slk_index_info;
 
 /* OrdinalSpan (S/slacken/package.scala:61-62) without the title; ordinal = position in the read's span list.
@@ -137,7 +142,14 @@ int32_t slk_index_create(const slk_params *params, const slk_table_config *cfg, 
  * geometry, no memory for the pieces), the index keeps its old table intact and only this call fails.  When the records had to
  * wait in host memory -- the old table is freed before the new one can be allocated -- they are lost with the failure: the
  * index is SPENT, every later call that takes it except slk_index_destroy returns SLK_E_STATE, and the load must be repeated
- * (with a larger slk_table_config.expected_records).  The same holds for the other calls that add records. */
+ * (with a larger slk_table_config.expected_records).  The same holds for the other calls that add records.
+ * Several id columns (m > 32; keys: id_longs words per record, row-major): the table does not grow.  It takes records up to its
+ * number of slots, the power of two at or above 2 x expected_records (slk_index_info: buckets x bucket_cells); a record beyond
+ * that finds no slot, the call returns SLK_E_CAPACITY -- the records that found a slot stay --, and so does every later call that
+ * adds records and slk_index_finalize: the load must be repeated with a larger expected_records.  duplicate_keys counts, and the
+ * first record of a key is kept, as with one id column.  A negative taxon is SLK_E_INVALID: slk_index_append then stores nothing
+ * of the call's chunk; slk_index_append_device, whose taxa the host never sees, skips those records on the device, stores the
+ * others and returns SLK_E_INVALID. */
 int32_t slk_index_append(slk_index *ix, const int64_t *keys, const int32_t *taxa, uint64_t n);
 int32_t slk_index_append_device(slk_index *ix, const int64_t *d_keys, const int32_t *d_taxa, uint64_t n);
 /* Table-sharded libraries (a table beyond one GPU's memory; BASELINE.json configs[3], the exchange that replaces the shuffle of

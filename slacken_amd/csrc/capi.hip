@@ -81,9 +81,9 @@ static int32_t start_build_state(slk_index *ix, void *table, size_t table_bytes)
   HIPCHK(hipStreamCreate(ix->build_stream.put()));
   HIPCHK(hipMemsetAsync(table, 0, table_bytes, ix->build_stream));
   HIPCHK(hipMalloc((void **)ix->d_max_disp.put(), sizeof(int32_t)));
-  HIPCHK(hipMalloc((void **)ix->d_counters.put(), 3 * sizeof(unsigned long long)));
+  HIPCHK(hipMalloc((void **)ix->d_counters.put(), 4 * sizeof(unsigned long long)));
   HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), ix->build_stream));
-  HIPCHK(hipMemsetAsync(ix->d_counters, 0, 3 * sizeof(unsigned long long), ix->build_stream));
+  HIPCHK(hipMemsetAsync(ix->d_counters, 0, 4 * sizeof(unsigned long long), ix->build_stream));
   HIPCHK(hipStreamSynchronize(ix->build_stream));
   return SLK_OK;
 }
@@ -216,6 +216,19 @@ static int32_t read_build_counters(slk_index *ix) {
   ix->unplaced = c[2];
   if (c[2] != 0 && ix->W > 1) return fail(SLK_E_CAPACITY, "%llu records found no free slot: raise expected_records", c[2]);
   return SLK_OK;   // (one-word table: records that found no cell within reach are the caller's to settle -- insert_growing)
+}
+
+// Several id columns: what the insert kernel leaves after a call.  Records with a negative taxon were skipped there and counted
+// (the device entry's taxa are checked nowhere else); the count belongs to this call alone and is cleared with the reading.
+static int32_t read_wide_insert(slk_index *ix) {
+  unsigned long long bad = 0;
+  HIPCHK(hipStreamSynchronize(ix->build_stream));
+  HIPCHK(hipMemcpy(&bad, ix->d_counters + 3, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad != 0) HIPCHK(hipMemset(ix->d_counters + 3, 0, sizeof(bad)));
+  const int32_t rc = read_build_counters(ix);
+  if (rc) return rc;
+  if (bad != 0) return fail(SLK_E_INVALID, "%llu records with a negative taxon were not stored", bad);
+  return SLK_OK;
 }
 
 static TableBuild build_view(slk_index *ix) {
@@ -402,7 +415,7 @@ int32_t slk_index_append_device(slk_index *ix, const int64_t *d_keys, const int3
   if (ix->W > 1) {
     launch_wide_insert(ix->wt, ix->W, d_keys, d_taxa, n, ix->d_counters, ix->build_stream);
     HIPCHK(hipGetLastError());
-    return read_build_counters(ix);
+    return read_wide_insert(ix);
   }
   return insert_growing(ix, true, [&]() -> int32_t {
     launch_table_insert(build_view(ix), d_keys, d_taxa, n, ix->build_stream);
@@ -432,7 +445,7 @@ int32_t slk_index_append(slk_index *ix, const int64_t *keys, const int32_t *taxa
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(ix->build_stream));
     }
-    return read_build_counters(ix);
+    return read_wide_insert(ix);
   }
   for (uint64_t o = 0; o < n; o += CH) {
     uint64_t c = std::min(CH, n - o);

@@ -230,7 +230,7 @@ struct slk_index {
   bool bucket_flag = false;        // the cells keep their top bit for the buckets' "a record went past" flag (engine.h: TableGeom.flag)
   uint32_t shard = 0, n_shards = 0;  // slk_index_set_shard: keep only the records of this shard
   DevPtr<int32_t> d_max_disp;
-  DevPtr<unsigned long long> d_counters;  // inserted, duplicate, overflow
+  DevPtr<unsigned long long> d_counters;  // inserted, duplicate, overflow, negative taxa skipped (several id columns)
   DevPtr<int32_t> d_parents;      // the taxonomy as given (ids of the caller)
   int32_t T = 0;
   std::vector<int32_t> h_parents;  // host copy, for the dense renumbering at finalize

@@ -177,38 +177,79 @@ __device__ __forceinline__ int32_t wide_find(const WideTable &t, const uint64_t 
   return 0;
 }
 
+// ---- the slot walk shared by the two kernels that write the table ----
+// A slot is claimed by its taxon word: 0 -> CLAIMED, key words written, then the taxon published (always > 0: no slot holds CLAIMED
+// once a kernel has ended).  A walk advances by rounds.  A lane that meets a CLAIMED slot, or loses the race for an empty one, comes
+// back to the same slot in its next round -- nobody waits inside a round, so lanes of one wave cannot hold each other up.  What
+// happens to a record whose key is there already is the policy: MERGE = the LCA of the two taxa (TaxonLCA,
+// LowestCommonAncestor.scala:152-170; library construction), otherwise the first record stays (slk_index_append: duplicate_keys).
+constexpr int32_t WIDE_CLAIMED = -1;
+enum WideStep { WIDE_AGAIN, WIDE_CREATED, WIDE_PRESENT, WIDE_FULL };
+template <int W, bool MERGE>
+__device__ __forceinline__ WideStep wide_upsert_round(const WideTable &t, const uint64_t *k, int32_t taxon, const int32_t *parents,
+                                                      int32_t ntax, uint64_t &slot, uint64_t &steps) {
+  int32_t cur = __hip_atomic_load(&t.taxa[slot], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+  if (cur == 0) {
+    if (atomicCAS((int *)&t.taxa[slot], 0, WIDE_CLAIMED) != 0) return WIDE_AGAIN;   // lost the race: look at the slot again next round
+#pragma unroll
+    for (int i = 0; i < W; i++) t.keys[slot * W + i] = k[i];
+    __hip_atomic_store(&t.taxa[slot], taxon, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    return WIDE_CREATED;
+  }
+  if (cur == WIDE_CLAIMED) return WIDE_AGAIN;
+  bool eq = true;
+#pragma unroll
+  for (int i = 0; i < W; i++) eq = eq && __hip_atomic_load(&t.keys[slot * W + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k[i];
+  if (eq) {
+    if (MERGE) {
+      for (;;) {                   // (the word holds a published taxon from here on: only LCA merges change it)
+        const int32_t merged = tax_lca(parents, ntax, cur, taxon);
+        if (merged == cur) break;
+        const int32_t prev = atomicCAS((int *)&t.taxa[slot], cur, merged);
+        if (prev == cur) break;
+        cur = prev;
+      }
+    }
+    return WIDE_PRESENT;
+  }
+  slot = (slot + 1) & t.mask;
+  return ++steps > t.mask ? WIDE_FULL : WIDE_AGAIN;
+}
+
+// slk_index_append[_device]: one lane per record, the first record of a key stays.  counters: 0 inserted, 1 key already present,
+// 2 no free slot, 3 negative taxon (skipped: the device entry's taxa reach the table unseen by the host)
 template <int W>
 __global__ void __launch_bounds__(256) wide_insert_kernel(WideTable t, const int64_t *__restrict__ keys,
                                                           const int32_t *__restrict__ taxa, uint64_t n,
                                                           unsigned long long *__restrict__ counters) {
-  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  int n_ins = 0, n_ovf = 0;
-  for (; i < n; i += stride) {
-    const int32_t taxon = taxa[i];
-    if (taxon == 0) continue;  // a record with taxon NONE is indistinguishable from a miss
+  int n_ins = 0, n_dup = 0, n_ovf = 0, n_neg = 0;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x - lane); i0 < n; i0 += stride) {   // (wave-uniform trip count)
+    const uint64_t i = i0 + lane;
+    const int32_t taxon = i < n ? taxa[i] : 0;
+    if (taxon < 0) n_neg++;
+    bool todo = taxon > 0;         // a record with taxon NONE is indistinguishable from a miss
     uint64_t k[W];
 #pragma unroll
-    for (int j = 0; j < W; j++) k[j] = (uint64_t)keys[i * W + j];
-    uint64_t slot = key_hash<W>(k) & t.mask;
-    bool done = false;
-    for (uint64_t step = 0; step <= t.mask && !done; step++) {
-      // Keys are unique (makeRecords' groupBy): claiming a slot needs no look at the keys other records are still writing.
-      if (atomicCAS((int *)&t.taxa[slot], 0, taxon) == 0) {
-#pragma unroll
-        for (int j = 0; j < W; j++) t.keys[slot * W + j] = k[j];
-        done = true;
-        n_ins++;
-      } else {
-        slot = (slot + 1) & t.mask;
+    for (int j = 0; j < W; j++) k[j] = todo ? (uint64_t)keys[i * W + j] : 0;
+    uint64_t slot = key_hash<W>(k) & t.mask, steps = 0;
+    while (__ballot(todo) != 0) {
+      if (todo) {
+        const WideStep did = wide_upsert_round<W, false>(t, k, taxon, nullptr, 0, slot, steps);
+        n_ins += did == WIDE_CREATED; n_dup += did == WIDE_PRESENT; n_ovf += did == WIDE_FULL;
+        todo = did == WIDE_AGAIN;
       }
     }
-    if (!done) n_ovf++;
   }
-  for (int o = 32; o > 0; o >>= 1) { n_ins += __shfl_xor(n_ins, o); n_ovf += __shfl_xor(n_ovf, o); }
-  if ((threadIdx.x & 63) == 0) {
+  for (int o = 32; o > 0; o >>= 1) {
+    n_ins += __shfl_xor(n_ins, o); n_dup += __shfl_xor(n_dup, o); n_ovf += __shfl_xor(n_ovf, o); n_neg += __shfl_xor(n_neg, o);
+  }
+  if (lane == 0) {
     if (n_ins) atomicAdd(&counters[0], (unsigned long long)n_ins);
+    if (n_dup) atomicAdd(&counters[1], (unsigned long long)n_dup);
     if (n_ovf) atomicAdd(&counters[2], (unsigned long long)n_ovf);
+    if (n_neg) atomicAdd(&counters[3], (unsigned long long)n_neg);
   }
 }
 
@@ -258,10 +299,7 @@ __global__ void __launch_bounds__(256) wide_probe_kernel(WideTable t, const uint
 // The SEQUENCE-flag spans of the scanned chunks are the super-mers' minimizers (SplitterMinimizers.find, Minimizers.scala:43-76:
 // library sequences are split around anything that is not a nucleotide, which is what the scan's run splitting does; runs it
 // flags as ambiguous carry no minimizer).  One lane per span inserts (key, taxon) or merges the taxon into the record that is there
-// by LCA (TaxonLCA, LowestCommonAncestor.scala:152-170).  A slot is claimed by its taxon word: 0 -> CLAIMED, key words written,
-// then the taxon published; a lane that meets a CLAIMED slot comes back to it in its next round -- nobody waits inside a round, so
-// lanes of one wave cannot hold each other up.
-constexpr int32_t WIDE_CLAIMED = -1;
+// by LCA (wide_upsert_round with the MERGE policy).
 template <int W>
 __global__ void __launch_bounds__(256) wide_build_insert_kernel(WideTable t, const int32_t *__restrict__ parents, int32_t ntax,
                                                                 const uint64_t *__restrict__ offsets, uint64_t R,
@@ -283,33 +321,9 @@ __global__ void __launch_bounds__(256) wide_build_insert_kernel(WideTable t, con
       uint64_t slot = key_hash<W>(k) & t.mask, steps = 0;
       while (__ballot(todo) != 0) {
         if (todo) {
-          int32_t cur = __hip_atomic_load(&t.taxa[slot], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-          if (cur == 0) {
-            if (atomicCAS((int *)&t.taxa[slot], 0, WIDE_CLAIMED) == 0) {
-#pragma unroll
-              for (int i = 0; i < W; i++) t.keys[slot * W + i] = k[i];
-              __hip_atomic_store(&t.taxa[slot], taxon, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-              created++;
-              todo = false;
-            }                              // (lost the race: look at the slot again next round)
-          } else if (cur != WIDE_CLAIMED) {
-            bool eq = true;
-#pragma unroll
-            for (int i = 0; i < W; i++) eq = eq && __hip_atomic_load(&t.keys[slot * W + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == k[i];
-            if (eq) {
-              for (;;) {                   // (the word holds a published taxon from here on: only LCA merges change it)
-                const int32_t merged = tax_lca(parents, ntax, cur, taxon);
-                if (merged == cur) break;
-                const int32_t prev = atomicCAS((int *)&t.taxa[slot], cur, merged);
-                if (prev == cur) break;
-                cur = prev;
-              }
-              todo = false;
-            } else {
-              slot = (slot + 1) & t.mask;
-              if (++steps > t.mask) { failed++; todo = false; }
-            }
-          }
+          const WideStep did = wide_upsert_round<W, true>(t, k, taxon, parents, ntax, slot, steps);
+          created += did == WIDE_CREATED; failed += did == WIDE_FULL;
+          todo = did == WIDE_AGAIN;
         }
       }
     }
