@@ -198,6 +198,25 @@ int32_t slk_index_export(const slk_index *ix, int64_t *keys, int32_t *taxa, uint
  * thread adds records to the same index. */
 int32_t slk_index_taxon_counts(const slk_index *ix, int32_t *taxa, uint64_t *counts, uint64_t capacity, uint64_t *n_taxa,
                                uint64_t *n_records);
+/* A library with more mask spaces from a resident one: replaces KeyValueIndex.respace (S/slacken/KeyValueIndex.scala:353-384; the loop
+ * of respaceMultiple :390-404 is the caller's) -- every record's minimizer ANDed with the space mask of `spaces` spaces and the
+ * records regrouped by minimizer with the LCA of their taxa (:370-379), without a second look at the genomes.  One pass over the
+ * source's table on the device (respace.hip): no record crosses to the host.  *out is a NEW index on the source's device: the source's
+ * slk_params with `spaces` replaced, the source's taxonomy, finalized -- ready for slk_stream_create, slk_index_export,
+ * slk_index_taxon_counts -- and independent of the source (either may be destroyed first).  The source is not changed.
+ *   cfg         NULL: the table is sized for the source's record count (an upper bound), at the default load factor.  Otherwise
+ *               expected_records (0: as NULL) and load_factor are taken; max_taxon is ignored: the taxon field is the source's.
+ *   info        records = the distinct masked minimizers; duplicate_keys = 0 (merging is the purpose); grown = how often the pass was
+ *               repeated into twice the buckets because a record found no cell within reach (the source is only read and the pass
+ *               is idempotent, so it simply runs again).  SLK_RESPACE_BUCKETS (environment) sets the buckets of the first table.
+ *   errors      SLK_E_STATE: source not finalized, without a taxonomy, or spent; SLK_E_INVALID: spaces <= the source's (the reference
+ *               throws "not meaningful") or > m / 2 (SpacedSeed's assert); SLK_E_UNSUPPORTED: several id columns, or a shard of a
+ *               table-sharded library (a key's owner is fmix64(key) mod n and the key changes: a respaced shard is no shard of the
+ *               respaced library); SLK_E_HIP: e.g. both tables do not fit the device.  On every failure *out is NULL and the source
+ *               is as it was.
+ * The reference's remark that the result equals a library built at `spaces` from the genomes is not exact: this is
+ * respace, not build.  Synchronous, on the source's build stream; not to be called while another thread adds records to the source. */
+int32_t slk_index_respace(const slk_index *src, int32_t spaces, const slk_table_config *cfg /* nullable */, slk_index **out);
 int32_t slk_index_get_info(const slk_index *ix, slk_index_info *out);
 /* The table's bucket choice as host arithmetic (no GPU): the range reduction of a 64-bit hash onto ANY number of buckets
  * (32 <= nbuckets <= 2^32) -- home = (top q bits of hash) * nbuckets >> q, q = ceil(log2(nbuckets)) -- with the remainder a cell

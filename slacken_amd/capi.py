@@ -73,7 +73,7 @@ HIT_DTYPE = np.dtype([("taxon", "<i4"), ("count", "<i4")])
 # every symbol include/slacken_amd.h declares
 EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc", "slk_host_register", "slk_host_free", "slk_index_create", "slk_index_append",
            "slk_index_append_device", "slk_index_set_shard", "slk_index_set_taxonomy", "slk_index_finalize", "slk_index_get_info",
-           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_taxon_counts", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
+           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_taxon_counts", "slk_index_respace", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
            "slk_stream_hip_stream", "slk_stream_destroy", "slk_spans_batch", "slk_spans_batch_wide", "slk_classify_batch",
            "slk_classify_batch_packed", "slk_pack_bases",
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
@@ -128,6 +128,7 @@ def lib():
     L.slk_index_add_sequences_device.argtypes = [vp, u8p, u64p, i32p, C.c_uint64]
     L.slk_index_export.argtypes = [vp, i64p, i32p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.slk_index_taxon_counts.argtypes = [vp, i32p, u64p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.slk_index_respace.argtypes = [vp, C.c_int32, C.POINTER(_TableConfig), C.POINTER(vp)]
     L.slk_index_destroy.argtypes = [vp]
     L.slk_index_destroy.restype = None
     L.slk_stream_create.argtypes = [vp, C.POINTER(vp)]
@@ -301,6 +302,16 @@ class Index:
         if n.value:
             _check(lib().slk_index_taxon_counts(self.h, _ptr(taxa), _ptr(counts), n.value, C.byref(n), C.byref(total)))
         return taxa, counts
+
+    def respace(self, spaces, expected_records=None):
+        """A new finalized Index with `spaces` (> this one's) mask spaces, derived on the device from this one's table
+        (slk_index_respace: KeyValueIndex.respace); expected_records: sizing of its table, default this index's record count."""
+        cfg = C.byref(_TableConfig(int(expected_records), 0, 0.0)) if expected_records is not None else None
+        h = C.c_void_p()
+        _check(lib().slk_index_respace(self.h, int(spaces), cfg, C.byref(h)))
+        new = Index.__new__(Index)
+        new.k, new.m, new.spaces, new.W, new.h = self.k, self.m, int(spaces), self.W, h
+        return new
 
     def finalize(self):
         _check(lib().slk_index_finalize(self.h))

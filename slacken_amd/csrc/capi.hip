@@ -88,6 +88,60 @@ static int32_t start_build_state(slk_index *ix, void *table, size_t table_bytes)
   return SLK_OK;
 }
 
+// the one-word scan and space masks of a splitter (slk_index_create; slk_index_respace recomputes them for its new `spaces`)
+static void set_scan_params(slk_index *ix, const slk_params *p, int W) {
+  ScanParams &sp = ix->sp;
+  sp.k = p->k; sp.m = p->m; sp.w = p->k - p->m + 1; sp.canonical = p->canonical ? 1 : 0;
+  sp.sh = W == 1 ? (32 - p->m) * 2 : 0;   // (the one-word fields are unused with several id columns)
+  sp.keep = (sp.sh == 0) ? ~0ULL : (~0ULL << sp.sh);
+  // RandomXOR.mask (MinimizerPriorities.scala:146-160): one word; partial word => xorMask << (64 - (m%32)*2)
+  sp.xmask = (p->m % 32 != 0) ? (p->xor_mask << (64 - (p->m % 32) * 2)) : p->xor_mask;
+  // SpacedSeed.spaceMask (:285-300): fill(-1, m), then s times { <<= 4 ; |= 3 << (64 - (m%32)*2) }
+  uint64_t sm = sp.keep;
+  uint64_t finalBits = 3ULL << ((64 - (p->m % 32) * 2) & 63);
+  for (int i = 0; i < p->spaces; i++) sm = (sm << 4) | finalBits;
+  sp.smask = sm;
+}
+
+// The geometry of a one-word table for `expected_records` records with taxon fields of tb bits: load factor, buckets, cell layout.
+static void adopt_shape(slk_index *ix, const TableShape &sh, int tb) {
+  ix->bucket_bits = sh.q;
+  ix->taxon_bits = tb;
+  ix->disp_bits = sh.disp;
+  ix->bucket_flag = sh.flag;
+  ix->nbuckets = sh.nb;
+}
+static int32_t size_table(slk_index *ix, uint64_t expected_records, float load_factor, int tb) {
+  // Load factor.  Given: as given (at most 0.95).  Default: the table takes the memory the device has.  Filled to 0.55 while that
+  // costs at most 55 % of the HBM; then fuller, up to 0.70, at that size; then 0.70 with a larger table, up to 80 % of the HBM
+  // (2.0e10 records on a 288 GB part: 229 GB); beyond that fuller again, 0.85 at most.  Measured at 1.0e10 records, 64-byte
+  // buckets (profiles/r03_bucket_geometry.txt): load 0.45 1 124 M reads/s, 0.55 1 118, 0.70 1 028 -- what a fuller table costs is
+  // second-bucket probes.
+  const bool default_lf = !(load_factor > 0);
+  const uint64_t expected = std::max<uint64_t>(expected_records, 1);
+  double lf = load_factor;
+  if (default_lf) {
+    // (the memory that is FREE now, not the part's total: several tables may share a device -- `--shard-table --devices 0,0`, a
+    //  dynamic library beside its base -- and each then takes its share of what the earlier ones left)
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) { (void)hipGetLastError(); free_b = total_b = (size_t)288 << 30; }
+    const double cell_bytes = (double)expected * 8.0, t = (double)std::min(total_b, free_b + ((size_t)2 << 30));
+    if (cell_bytes / 0.55 <= 0.55 * t) lf = 0.55;
+    else if (cell_bytes / 0.70 <= 0.55 * t) lf = cell_bytes / (0.55 * t);
+    else if (cell_bytes / 0.70 <= 0.80 * t) lf = 0.70;
+    else lf = std::min(0.85, cell_bytes / (0.80 * t));
+  }
+  if (lf > 0.95) lf = 0.95;
+  // (a record that finds no cell within reach of its displacement field all the same makes the table grow: grow_table)
+  const uint64_t cells_needed = (uint64_t)((double)expected / lf) + CELLS;
+  bool shape_ok = false;
+  const TableShape sh = settle_shape((cells_needed + CELLS - 1) / CELLS, expected, tb, &shape_ok);
+  if (!shape_ok) { return fail(SLK_E_CAPACITY, "a table of %llu buckets is too large", (unsigned long long)sh.nb); }
+  ix->load_target = (float)lf;
+  adopt_shape(ix, sh, tb);
+  return SLK_OK;
+}
+
 int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32_t device, slk_index **out) {
   if (!p || !cfg || !out) return fail(SLK_E_INVALID, "null argument");
   *out = nullptr;
@@ -113,18 +167,7 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
   std::unique_ptr<slk_index> ix(new slk_index());   // (released into *out on success only)
   ix->device = device;
   ix->params = *p;
-  ScanParams &sp = ix->sp;
-  sp.k = p->k; sp.m = p->m; sp.w = p->k - p->m + 1; sp.canonical = p->canonical ? 1 : 0;
-  sp.sh = W == 1 ? (32 - p->m) * 2 : 0;   // (the one-word fields are unused with several id columns)
-  sp.keep = (sp.sh == 0) ? ~0ULL : (~0ULL << sp.sh);
-  // RandomXOR.mask (MinimizerPriorities.scala:146-160): one word; partial word => xorMask << (64 - (m%32)*2)
-  sp.xmask = (p->m % 32 != 0) ? (p->xor_mask << (64 - (p->m % 32) * 2)) : p->xor_mask;
-  // SpacedSeed.spaceMask (:285-300): fill(-1, m), then s times { <<= 4 ; |= 3 << (64 - (m%32)*2) }
-  uint64_t sm = sp.keep;
-  uint64_t finalBits = 3ULL << ((64 - (p->m % 32) * 2) & 63);
-  for (int i = 0; i < p->spaces; i++) sm = (sm << 4) | finalBits;
-  sp.smask = sm;
-
+  set_scan_params(ix.get(), p, W);
   if (W > 1) {
     // several id columns: the staged kernels of wide.hip over an open-addressing table of (W key words, taxon) slots
     ix->W = W;
@@ -161,44 +204,15 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
   int32_t max_taxon = cfg->max_taxon > 0 ? cfg->max_taxon : ((1 << 22) - 1);
   int tb = 1;
   while (tb < 31 && (1LL << tb) <= (long long)max_taxon) tb++;
-  // Load factor.  Given: as given (at most 0.95).  Default: the table takes the memory the device has.  Filled to 0.55 while that
-  // costs at most 55 % of the HBM; then fuller, up to 0.70, at that size; then 0.70 with a larger table, up to 80 % of the HBM
-  // (2.0e10 records on a 288 GB part: 229 GB); beyond that fuller again, 0.85 at most.  Measured at 1.0e10 records, 64-byte
-  // buckets (profiles/r03_bucket_geometry.txt): load 0.45 1 124 M reads/s, 0.55 1 118, 0.70 1 028 -- what a fuller table costs is
-  // second-bucket probes.
-  const bool default_lf = !(cfg->load_factor > 0);
-  const uint64_t expected = std::max<uint64_t>(cfg->expected_records, 1);
-  double lf = cfg->load_factor;
-  if (default_lf) {
-    // (the memory that is FREE now, not the part's total: several tables may share a device -- `--shard-table --devices 0,0`, a
-    //  dynamic library beside its base -- and each then takes its share of what the earlier ones left)
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) { (void)hipGetLastError(); free_b = total_b = (size_t)288 << 30; }
-    const double cell_bytes = (double)expected * 8.0, t = (double)std::min(total_b, free_b + ((size_t)2 << 30));
-    if (cell_bytes / 0.55 <= 0.55 * t) lf = 0.55;
-    else if (cell_bytes / 0.70 <= 0.55 * t) lf = cell_bytes / (0.55 * t);
-    else if (cell_bytes / 0.70 <= 0.80 * t) lf = 0.70;
-    else lf = std::min(0.85, cell_bytes / (0.80 * t));
-  }
-  if (lf > 0.95) lf = 0.95;
-  // (a record that finds no cell within reach of its displacement field all the same makes the table grow: grow_table)
-  const uint64_t cells_needed = (uint64_t)((double)expected / lf) + CELLS;
-  bool shape_ok = false;
-  const TableShape sh = settle_shape((cells_needed + CELLS - 1) / CELLS, expected, tb, &shape_ok);
-  if (!shape_ok) { return fail(SLK_E_CAPACITY, "a table of %llu buckets is too large", (unsigned long long)sh.nb); }
-  ix->load_target = (float)lf;
-  ix->bucket_bits = sh.q;
-  ix->taxon_bits = tb;
-  ix->disp_bits = sh.disp;
-  ix->bucket_flag = sh.flag;
-  ix->nbuckets = sh.nb;
+  int32_t rc = size_table(ix.get(), cfg->expected_records, cfg->load_factor, tb);
+  if (rc) return rc;
   size_t bytes = (size_t)ix->nbuckets * CELLS * 8;
   hipError_t e = hipMalloc((void **)ix->cells.put(), bytes);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     return fail(SLK_E_HIP, "hipMalloc of %zu table bytes failed: %s", bytes, hipGetErrorString(e));
   }
-  int32_t rc = start_build_state(ix.get(), ix->cells, bytes);
+  rc = start_build_state(ix.get(), ix->cells, bytes);
   if (rc) return rc;
   *out = ix.release();
   return SLK_OK;
@@ -711,6 +725,99 @@ int32_t slk_index_export(const slk_index *ix, int64_t *keys, int32_t *taxa, uint
     HIPCHK(hipMemcpy(taxa, dt.p, got * 4, hipMemcpyDeviceToHost));
   }
   if (n > capacity && capacity) return fail(SLK_E_CAPACITY, "%llu records, capacity %llu", n, (unsigned long long)capacity);
+  return SLK_OK;
+}
+
+// ---- slk_index_respace: KeyValueIndex.respace (S/slacken/KeyValueIndex.scala:353-384) on the device (respace.hip) -----------------
+template <class T> static int32_t clone_device(DevPtr<T> &dst, const DevPtr<T> &src, size_t n, hipStream_t s) {
+  if (!src.get() || n == 0) return SLK_OK;
+  HIPCHK(hipMalloc((void **)dst.put(), n * sizeof(T)));
+  HIPCHK(hipMemcpyAsync(dst.get(), src.get(), n * sizeof(T), hipMemcpyDeviceToDevice, s));
+  return SLK_OK;
+}
+
+int32_t slk_index_respace(const slk_index *src, int32_t spaces, const slk_table_config *cfg, slk_index **out) {
+  if (!src || !out) return fail(SLK_E_INVALID, "null argument");
+  *out = nullptr;
+  int32_t rc = set_device(src);   // (a spent index: SLK_E_STATE)
+  if (rc) return rc;
+  if (!src->finalized) return fail(SLK_E_STATE, "slk_index_respace needs a finalized index");
+  if (!src->d_parents) return fail(SLK_E_STATE, "slk_index_respace needs the taxonomy (LCA merging): call slk_index_set_taxonomy first");
+  if (spaces <= src->params.spaces)   // the reference's wording (KeyValueIndex.scala:358)
+    return fail(SLK_E_INVALID, "Respacing to a smaller or identical number of spaces is not meaningful. (was %d, requested %d)",
+                src->params.spaces, spaces);
+  if (spaces > src->params.m / 2)     // SpacedSeed's assert (MinimizerPriorities.scala)
+    return fail(SLK_E_INVALID, "%d spaces in minimizers of %d nt: at most %d", spaces, src->params.m, src->params.m / 2);
+  if (src->W > 1) return fail(SLK_E_UNSUPPORTED, "slk_index_respace supports minimizers of up to 32 nt (one id column)");
+  if (src->n_shards > 1)
+    return fail(SLK_E_UNSUPPORTED, "a shard of a table-sharded library cannot be respaced: the owner of a key is fmix64(key) mod n, and the key changes");
+  hipStream_t s = src->build_stream;   // the stream the source's records were inserted on: the pass sees them all
+
+  std::unique_ptr<slk_index> ix(new slk_index());   // (released into *out on success only; the source's device is selected)
+  ix->device = src->device;
+  ix->params = src->params;
+  ix->params.spaces = spaces;
+  set_scan_params(ix.get(), &ix->params, 1);
+  // the source's taxonomy and, where it has them, its dense-id tables: the cells of the new table hold the ids the source's hold
+  ix->T = src->T;
+  ix->D = src->D;
+  ix->h_parents = src->h_parents;
+  rc = clone_device(ix->d_parents, src->d_parents, (size_t)src->T, s);
+  if (!rc) rc = clone_device(ix->d_to_dense, src->d_to_dense, (size_t)src->T, s);
+  if (!rc) rc = clone_device(ix->d_nodes_orig, src->d_nodes_orig, (size_t)src->T, s);
+  if (!rc) rc = clone_device(ix->d_parents_dense, src->d_parents_dense, (size_t)src->D + 1, s);
+  if (!rc) rc = clone_device(ix->d_to_orig, src->d_to_orig, (size_t)src->D + 1, s);
+  if (!rc) rc = clone_device(ix->d_nodes_dense, src->d_nodes_dense, (size_t)src->D + 1, s);
+  if (rc) return rc;
+  ix->d_nodes = src->d_nodes == nullptr ? nullptr : src->d_nodes == src->d_nodes_dense.get() ? ix->d_nodes_dense.get() : ix->d_nodes_orig.get();
+
+  // every record of the source could keep a key of its own: its record count bounds the new table's
+  const uint64_t expected = cfg && cfg->expected_records ? cfg->expected_records : std::max<uint64_t>(src->records, 1);
+  rc = size_table(ix.get(), expected, cfg ? cfg->load_factor : 0.0f, src->taxon_bits);
+  if (rc) return rc;
+  // SLK_RESPACE_BUCKETS: the first table has this many buckets (or the fewest its cell layout allows, if that is more) whatever the
+  // record count -- how the tests reach the repeat below
+  const long forced = env_long("SLK_RESPACE_BUCKETS", 0);
+  if (forced > 0) {
+    bool ok = false;
+    const TableShape sh = settle_shape((uint64_t)forced, 1, src->taxon_bits, &ok);
+    if (!ok) return fail(SLK_E_CAPACITY, "SLK_RESPACE_BUCKETS=%ld: no such table", forced);
+    adopt_shape(ix.get(), sh, src->taxon_bits);
+  }
+  HIPCHK(hipStreamCreate(ix->build_stream.put()));
+  HIPCHK(hipMalloc((void **)ix->d_max_disp.put(), sizeof(int32_t)));
+  HIPCHK(hipMalloc((void **)ix->d_counters.put(), 4 * sizeof(unsigned long long)));
+  for (int attempt = 0;; attempt++) {
+    const size_t bytes = (size_t)ix->nbuckets * CELLS * 8;
+    const hipError_t e = hipMalloc((void **)ix->cells.put(), bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(SLK_E_HIP, "hipMalloc of %zu table bytes beside the source's table failed: %s", bytes, hipGetErrorString(e));
+    }
+    HIPCHK(hipMemsetAsync(ix->cells, 0, bytes, s));
+    HIPCHK(hipMemsetAsync(ix->d_max_disp, 0, sizeof(int32_t), s));
+    HIPCHK(hipMemsetAsync(ix->d_counters, 0, 4 * sizeof(unsigned long long), s));
+    launch_respace(src->view(), build_view(ix.get()), ix->sp.smask, src->kernel_parents(), src->kernel_ntax(), s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    rc = read_build_counters(ix.get());
+    if (rc) return rc;
+    if (ix->unplaced == 0) break;
+    // A record found no cell within reach of the displacement field.  The source is untouched and the pass idempotent: the table is
+    // dropped and the pass repeated into twice the buckets (the taxon-count map of taxstats.hip does the same).
+    if (attempt >= 8)
+      return fail(SLK_E_CAPACITY, "%llu records could not be placed after the pass had been repeated %d times", (unsigned long long)ix->unplaced, attempt);
+    ix->cells.reset();
+    bool ok = false;
+    const TableShape sh = settle_shape(grow_buckets(ix->nbuckets), 1, src->taxon_bits, &ok);
+    if (!ok) return fail(SLK_E_CAPACITY, "the table cannot grow beyond %llu buckets", (unsigned long long)ix->nbuckets);
+    adopt_shape(ix.get(), sh, src->taxon_bits);
+    ix->grown++;
+  }
+  ix->unplaced = 0;
+  ix->dups = 0;   // (merges are the purpose here, not a contract violation)
+  ix->finalized = true;
+  *out = ix.release();
   return SLK_OK;
 }
 

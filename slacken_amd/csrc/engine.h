@@ -380,6 +380,8 @@ void launch_export(const TableView &T, uint64_t nbuckets, int64_t *keys, int32_t
                    unsigned long long *counter, hipStream_t s);
 void launch_export_range(const TableView &T, uint64_t bucket0, uint64_t bucket1, int64_t *keys, int32_t *taxa, uint64_t capacity,
                          unsigned long long *counter, hipStream_t s);
+// respace.hip: every record of `src` with its key ANDed with new_smask, inserted or LCA-merged into `dst` (taxa as the cells hold them)
+void launch_respace(const TableView &src, const TableBuild &dst, uint64_t new_smask, const int32_t *parents, int32_t ntax, hipStream_t s);
 void launch_table_lookup(const TableView &t, const int64_t *keys, uint64_t n, int32_t *out, hipStream_t s);
 void launch_scan(const ScanParams &P, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
                  const uint64_t *mate_offsets, uint64_t R, uint64_t *span_keys, int32_t *span_meta, int32_t *span_count,

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "../../include/slacken_amd.h"
+#include "library_writer.hpp"
 #include "migration.hpp"
 #include "output.hpp"
 #include "pack.hpp"
@@ -1693,6 +1694,109 @@ static int cmd_inspect(int argc, char **argv) {
   return 0;
 }
 
+// ---- respace (Slacken.scala:173-184, KeyValueIndex.respaceMultiple :390-404) and copy-records: the library writer's two users ----
+static const char *RESPACE_USAGE = "usage: respace -i INDEX -o OUTPUT --spaces S [S ...] [--format parquet|slkrec] [--devices D]";
+static const char *COPY_RECORDS_USAGE = "usage: copy-records -i INDEX -o OUTPUT [--format parquet|slkrec]";
+
+// the properties a library derived from `location` is written with (buckets: the source's; a source without the key is one bucket)
+static LibraryProperties writer_properties(const std::string &location, const IndexParams &ip) {
+  const auto p = read_properties(location + ".properties");
+  LibraryProperties lp;
+  lp.k = ip.k; lp.m = ip.m; lp.spaces = ip.spaces; lp.xorMask = ip.xorMask; lp.canonical = ip.canonical;
+  lp.buckets = p.count("buckets") ? std::stoi(p.at("buckets")) : 1;
+  return lp;
+}
+
+// copy-records -i INDEX -o OUTPUT [--format parquet|slkrec]: a library's records read with the readers and written with the
+// writer, with its properties and taxonomy (host only: the writer without a GPU)
+static int cmd_copy_records(int argc, char **argv) {
+  std::string index, output;
+  LibraryWriter::Format format = LibraryWriter::AUTO;
+  for (int i = 0; i < argc; i++) {
+    std::string a = argv[i];
+    auto next = [&]() { if (i + 1 >= argc) die("missing value for " + a); return std::string(argv[++i]); };
+    if (a == "-i" || a == "--index") index = next();
+    else if (a == "-o" || a == "--output") output = next();
+    else if (a == "--format") format = LibraryWriter::parse_format(next());
+    else die("unknown option " + a + "\n" + COPY_RECORDS_USAGE);
+  }
+  if (index.empty() || output.empty()) die(COPY_RECORDS_USAGE);
+  if (fs::weakly_canonical(index) == fs::weakly_canonical(output)) die("copy-records: OUTPUT is INDEX");
+  const IndexParams ip = read_index_params(index);
+  if (ip.m > 32) die("copy-records supports minimizers of up to 32 nt (this library has m=" + std::to_string(ip.m) + ")");
+  LibraryWriter w(output, writer_properties(index, ip), index + "_taxonomy", format);
+  auto add = [&](const int64_t *keys, const int32_t *taxa, uint64_t c) { w.add(keys, taxa, c); };
+  if (!fs::exists(index + ".slkrec") && parquet_available() && fs::is_directory(index)) parquet_for_each_batch(index, 1, add);
+  else RecordFile(index, 1).for_each_chunk(true, add);
+  w.finish();
+  std::cerr << "copy-records: " << w.records() << " records written to " << output << std::endl;
+  return 0;
+}
+
+// the first match of _s[0-9]+ in s (respaceMultiple's regex): its position and length, or false
+static bool find_spaces_tag(const std::string &s, size_t *pos, size_t *len) {
+  for (size_t at = s.find("_s"); at != std::string::npos; at = s.find("_s", at + 1)) {
+    size_t e = at + 2;
+    while (e < s.size() && s[e] >= '0' && s[e] <= '9') e++;
+    if (e > at + 2) { *pos = at; *len = e - at; return true; }
+  }
+  return false;
+}
+
+static int cmd_respace(int argc, char **argv) {
+  std::string index, output;
+  std::vector<int> spaces, devices{0};
+  LibraryWriter::Format format = LibraryWriter::AUTO;
+  for (int i = 0; i < argc; i++) {
+    std::string a = argv[i];
+    auto next = [&]() { if (i + 1 >= argc) die("missing value for " + a); return std::string(argv[++i]); };
+    if (a == "-i" || a == "--index") index = next();
+    else if (a == "-o" || a == "--output") output = next();
+    else if (a == "--format") format = LibraryWriter::parse_format(next());
+    else if (a == "-s" || a == "--spaces") {
+      while (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') spaces.push_back(std::stoi(argv[++i]));
+    }
+    else if (a == "--devices") {
+      const std::string v = next();
+      if (v == "all" || v.find(',') != std::string::npos) die("respace takes one device: both tables must fit one GPU");
+      devices = parse_device_list(v);
+    }
+    else if (a == "--shard-table")
+      die(std::string("--shard-table is not supported by respace: both tables must fit one GPU\n") + RESPACE_USAGE);
+    else die("unknown option " + a + "\n" + RESPACE_USAGE);
+  }
+  if (index.empty() || output.empty() || spaces.empty()) die(RESPACE_USAGE);
+  size_t tag_at = 0, tag_len = 0;
+  if (!find_spaces_tag(output, &tag_at, &tag_len)) die("Unable to guess the correct output location for new indexes at: " + output);
+  if (format == LibraryWriter::PARQUET && !parquet_available()) die("--format parquet: this build has no Parquet support");
+  refuse_wide("respace", read_index_params(index));
+  IndexParams ip;
+  Taxonomy tax;
+  DeviceIndex dev;
+  dev.devices = devices;
+  load_index(index, ip, tax, dev);
+  LibraryProperties lp = writer_properties(index, ip);
+  for (int s : spaces) {
+    const std::string out_loc = output.substr(0, tag_at) + "_s" + std::to_string(s) + output.substr(tag_at + tag_len);
+    Timer t("Respace to " + out_loc);
+    slk_index *nx = nullptr;
+    SLK_CALL(slk_index_respace(dev.ix, s, nullptr, &nx));   // (an s not above the library's own: the reference's wording, and the end)
+    std::unique_ptr<slk_index, void (*)(slk_index *)> owner(nx, slk_index_destroy);
+    uint64_t n = 0;
+    SLK_CALL(slk_index_export(nx, nullptr, nullptr, 0, &n));
+    std::vector<int64_t> keys(n);
+    std::vector<int32_t> taxa(n);
+    if (n) SLK_CALL(slk_index_export(nx, keys.data(), taxa.data(), n, &n));
+    lp.spaces = s;
+    LibraryWriter w(out_loc, lp, index + "_taxonomy", format);
+    for (uint64_t o = 0; o < n; o += RecordFile::CHUNK) w.add(keys.data() + o, taxa.data() + o, std::min(RecordFile::CHUNK, n - o));
+    w.finish();
+    std::cout << "Stats for " << out_loc << "\n" << index_stats_text(tax, device_taxon_counts(nx), ip.m);
+    std::cout.flush();
+  }
+  return 0;
+}
+
 static const char *HELP =
     "slacken-amd -- Slacken's classify path on an MI355X (libslacken_amd.so)\n"
     "  slacken-amd [--partitions N] classify  -i INDEX -o OUTPUT [options] FILES...\n"
@@ -1732,7 +1836,13 @@ static const char *HELP =
     "  slacken-amd inspect -i INDEX -o OUTPUT [--labels FILE] [--devices D] (Slacken.scala:317-330): Kraken-style reports of the\n"
     "  library's contents, OUTPUT_min_report.txt (records per taxon) and OUTPUT_genome_report.txt (one per stored taxon); with\n"
     "  --labels (seqid TAB taxon lines) OUTPUT_missing_report.txt of the labelled taxa the library does not store\n"
-    "host-only helpers: report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
+    "  slacken-amd respace -i INDEX -o OUTPUT --spaces S [S ...] [--format parquet|slkrec] [--devices D] (Slacken.scala:173-184): for\n"
+    "  each S above the library's own minimizerSpaces, in the order given, the library at S spaces derived on the GPU from the resident\n"
+    "  table (keys masked, records regrouped by LCA; no genome is read) and written to OUTPUT with its first _s<digits> replaced by\n"
+    "  _sS -- .properties, _taxonomy and the records as bucketed Parquet (as .slkrec with --format slkrec or without Arrow) -- followed\n"
+    "  by `Stats for <location>` and the two lines `stats` prints\n"
+    "host-only helpers: copy-records -i INDEX -o OUTPUT [--format parquet|slkrec] (a library rewritten by the library writer) |\n"
+    "  report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
     "  stats-report TAXONOMY_DIR COUNTS_TSV (taxon count) M [--histogram] [-o OUTPUT [--labels FILE]] |\n"
     "  migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV (t1 t2 count) OUTPUT | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
     "environment: SLK_HOST_THREADS (formatting/decoding threads), SLK_INPUT_STREAMS (input files read side by side, default 8),\n"
@@ -1744,7 +1854,7 @@ static const char *HELP =
 int main(int argc, char **argv) {
   int i = 1;
   while (i < argc && std::string(argv[i]) == "--partitions") i += 2;  // global Spark option of the reference: accepted, unused
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|compare-index|stats|inspect|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|compare-index|respace|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1767,9 +1877,11 @@ int main(int argc, char **argv) {
     if (cmd == "stats" && i < argc) return cmd_stats(argc - i, argv + i);
     if (cmd == "inspect" && i < argc) return cmd_inspect(argc - i, argv + i);
     if (cmd == "stats-report") return cmd_stats_report(argc - i, argv + i);
+    if (cmd == "respace") return cmd_respace(argc - i, argv + i);
+    if (cmd == "copy-records") return cmd_copy_records(argc - i, argv + i);
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `bracken-build`, `compare-index`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `bracken-build`, `compare-index`, `respace`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }
