@@ -27,9 +27,9 @@ $(STREAM_SUM): tools/stream_sum.hip
 	@mkdir -p slacken_amd/lib
 	$(HIPCC) -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -shared -o $@ tools/stream_sum.hip
 
-$(LIB): $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/respace.hip $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h slacken_amd/host/pack.hpp include/slacken_amd.h
+$(LIB): $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/index.hip $(CSRC)/classify.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/respace.hip $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h slacken_amd/host/pack.hpp include/slacken_amd.h
 	@mkdir -p slacken_amd/lib
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/respace.hip -ldl
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/index.hip $(CSRC)/classify.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/respace.hip -ldl
 
 # Parquet input of the CLI: the Arrow C++ libraries inside the pyarrow wheel, if there is one (no Arrow dev package here)
 PYARROW_DIR := $(shell python3 -c "import pyarrow, os; print(os.path.dirname(pyarrow.__file__))" 2>/dev/null)

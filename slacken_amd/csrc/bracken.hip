@@ -42,7 +42,7 @@ struct BrArgs {
   const uint32_t *chunk_piece; // [nchunks]
   uint64_t nchunks;
   int32_t *deficit;     // [nchunks]: true minus literal count of qtax at the chunk's first read start
-  const uint4 *nodes;   // {parent, tin, tout, -} of the caller's ids (capi.hip: build_tax_nodes)
+  const uint4 *nodes;   // {parent, tin, tout, -} of the caller's ids (index.hip: build_tax_nodes)
   int32_t T;
   unsigned long long *map_keys, *map_counts;  // (source << 32 | dest) -> reads; power-of-two capacity
   uint64_t map_mask;
@@ -139,16 +139,12 @@ struct MapRef {   // Int2IntArrayMap countSummary (:59): {taxon, count, tin, tou
   }
 };
 
-__device__ __forceinline__ uint4 br_node(const BrArgs &A, int32_t t) {   // an id outside the taxonomy is a tree of its own
-  return ((uint32_t)t < (uint32_t)A.T) ? A.nodes[t] : make_uint4(0u, 0x40000000u + (uint32_t)t, 0x40000000u + (uint32_t)t, 0u);
-}
-
 // countSummary.put(t, applyAsInt(t) + 1); false when the map is full
 __device__ __forceinline__ bool br_inc(const BrArgs &A, MapRef &M, int32_t t) {
   const int32_t s = M.find(t);
   if (s >= 0) { M.at(s).y++; return true; }
   if (M.n == M.cap) return false;
-  const uint4 nd = br_node(A, t);
+  const uint4 nd = tax_node(A.nodes, A.T, t);
   M.at(M.n++) = make_int4(t, 1, (int32_t)nd.y, (int32_t)nd.z);
   return true;
 }
@@ -182,10 +178,10 @@ __device__ int32_t br_resolve(const BrArgs &A, MapRef &M) {
       if (m_in <= ain && ain <= m_out) {
       } else if (ain <= m_in && m_in <= (uint32_t)ea.w) { maxTaxon = ea.x; m_in = ain; m_out = (uint32_t)ea.w; }
       else {
-        int32_t x = (int32_t)br_node(A, maxTaxon).x;
+        int32_t x = (int32_t)tax_node(A.nodes, A.T, maxTaxon).x;
         uint4 nx = make_uint4(0, 0, 0, 0);
-        while (x != 0) { nx = br_node(A, x); if (nx.y <= ain && ain <= nx.z) break; x = (int32_t)nx.x; }
-        if (x == 0) { x = 1; nx = br_node(A, 1); }
+        while (x != 0) { nx = tax_node(A.nodes, A.T, x); if (nx.y <= ain && ain <= nx.z) break; x = (int32_t)nx.x; }
+        if (x == 0) { x = 1; nx = tax_node(A.nodes, A.T, 1); }
         maxTaxon = x; m_in = nx.y; m_out = nx.z;
       }
     }

@@ -27,14 +27,6 @@ struct BuildLds {
   int32_t q_tax[BW][128];
 };
 
-__device__ __forceinline__ int code_of(uint32_t c) {  // BitRepresentation.charToTwobit :127-135; 5 = not a nucleotide
-  const uint32_t VM = (1u << 1) | (1u << 3) | (1u << 7) | (1u << 20) | (1u << 21);  // A C G T U, either case
-  bool ok = ((c & 0xC0) == 0x40) && ((VM >> (c & 31)) & 1);
-  uint32_t t = (c >> 1) & 3;
-  t ^= t >> 1;
-  return ok ? (int)t : 5;
-}
-
 __global__ void __launch_bounds__(BW * 64) build_kernel(ScanParams P, TableBuild T, const int32_t *__restrict__ parents,
                                                         int32_t ntax, const uint8_t *__restrict__ bases, uint64_t total_bases,
                                                         const uint64_t *__restrict__ chunk_start,
@@ -82,7 +74,7 @@ __global__ void __launch_bounds__(BW * 64) build_kernel(ScanParams P, TableBuild
     uint32_t ch = (uint32_t)(lo & 0xff);
     lo = (lo >> 8) | (hi << 56);
     hi >>= 8;
-    int t = (step < len) ? code_of(ch) : 5;
+    int t = (step < len) ? base_code(ch) : 5;
     bool emit = false;
     if (t >= 4) {  // InputReader.removeInvalid (InputReader.scala:60-72): sequences are split around anything else
       nvalid = 0; fwd = 0; rc = 0; head = w - 1; minage = 0; minv = ~0ULL; have_cur = false;

@@ -3,6 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdlib>
+
+// SLK_* switches of the environment (host side; the kernels' launchers read theirs too).  Which of them are read once per process
+// (a `static const` at the place of use) and which per call (tests move those) is the caller's business.
+inline bool env_on(const char *name) { const char *e = getenv(name); return e != nullptr && e[0] == '1'; }
+inline long env_long(const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; }
+
 namespace slk {
 
 // Splitter constants in the reference's left-aligned key space.
@@ -167,6 +174,32 @@ __device__ inline int32_t tax_lca(const int32_t *parents, int32_t ntax, int32_t 
   return a != 0 ? a : 1;
 }
 
+// {parent, tin, tout, -} of taxon t in an Euler-tour array (FusedArgs.nodes; index.hip: build_tax_nodes); an id outside the taxonomy is a
+// tree of its own.  A wave-uniform t makes it a scalar load.
+__device__ __forceinline__ uint4 tax_node(const uint4 *nodes, int32_t ntax, int32_t t) {
+  return ((uint32_t)t < (uint32_t)ntax) ? nodes[t] : make_uint4(0u, 0x40000000u + (uint32_t)t, 0x40000000u + (uint32_t)t, 0u);
+}
+
+// ---- device helpers the kernel files share ----------------------------------------------------------------------------------
+// BitRepresentation.charToTwobit (BitRepresentation.scala:127-135) for one character: 0..3, or 5 for anything that is not a nucleotide
+__device__ __forceinline__ int base_code(uint32_t c) {
+  const uint32_t VM = (1u << 1) | (1u << 3) | (1u << 7) | (1u << 20) | (1u << 21);  // A C G T U, either case
+  bool ok = ((c & 0xC0) == 0x40) && ((VM >> (c & 31)) & 1);
+  uint32_t t = (c >> 1) & 3;  // A,C,T/U,G -> 0,1,2,3
+  t ^= t >> 1;                // -> A=0 C=1 G=2 T=3
+  return ok ? (int)t : 5;
+}
+__device__ __forceinline__ void wave_sync() {  // order this wave's LDS traffic (lanes of one wave exchange data via LDS)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int src) {  // src wave-uniform; result wave-uniform
+  uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src), hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src);
+  return ((uint64_t)hi << 32) | lo;
+}
+__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
+
 // span_meta packing: kmers (signed) << 4 | flag << 1 | distinct
 __host__ __device__ inline int32_t pack_meta(int32_t kmers, int32_t flag, int32_t distinct) {
   return (int32_t)(((uint32_t)kmers << 4) | ((uint32_t)flag << 1) | (uint32_t)distinct);
@@ -198,6 +231,29 @@ __device__ __forceinline__ uint4 load_block16(const uint8_t *src, uint32_t room)
   return v;
 }
 __device__ __forceinline__ uint32_t clamp_room(uint64_t bytes) { return bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bytes; }
+
+// Read stream of the lane-per-fragment kernel (lane.hip: LaneLds, SBLK sub-blocks) and the lane-per-segment kernel (fused.hip: SegLds,
+// SEG_SBLK).  A lane consumes its read 16 bytes at a time; fetching those 16 bytes alone every 16 steps asks the L2 for
+// every 64-byte line about four times, and with 20 waves x 64 lanes per CU the lines do not survive in the L2 between two
+// requests (PMC: ~1.0e8 of 5.2e8 fabric reads per launch were re-fetched read bytes).  So a refill fetches SB sub-blocks
+// back to back (the L1 merges requests to a line that is already on its way), keeps the first in registers and parks the
+// others in the lane's own LDS slots (Lds::sbuf).  Measured per 10 M x 150 bp launch: 16 bytes per refill 9.28 ms, 48: 9.0, 64: 8.8,
+// 80: 8.5 (two refills per 150-base read), 96: 8.6, 112 and more: slower (the LDS they take costs resident waves).  Sub-blocks
+// starting at or beyond the end of the read are not fetched, and the block that holds the last bytes of the caller's buffer
+// is assembled from byte loads (load_block16; `room` = bytes from seq to the end of the buffer): nothing outside the buffer
+// is touched.
+template <int SB, class Lds>
+__device__ __forceinline__ uint4 stream_refill(Lds *L, int lane, const uint8_t *seq, uint32_t p, uint32_t n, uint32_t room) {
+  uint4 v[SB];
+#pragma unroll
+  for (int i = 0; i < SB; i++) {
+    v[i] = make_uint4(0, 0, 0, 0);
+    if (p + 16u * i < n) v[i] = load_block16(seq + p + 16u * i, room - (p + 16u * i));
+  }
+#pragma unroll
+  for (int i = 1; i < SB; i++) L->sbuf[(i - 1) * 64 + lane] = v[i];
+  return v[0];
+}
 
 // build-time view of the table (table_insert_kernel, build_kernel)
 struct TableBuild {
@@ -251,7 +307,7 @@ struct FusedArgs {
   const int32_t *parents;
   int32_t ntax;
   // the same forest with an Euler tour, [ntax] x {parent, tin, tout, 0}: a is an ancestor-or-self of b iff tin[a] <= tin[b] <= tout[a].
-  // The lane kernel's resolveTree asks that question of pairs of map taxa instead of walking root paths (capi.hip: build_tax_nodes)
+  // The lane kernel's resolveTree asks that question of pairs of map taxa instead of walking root paths (index.hip: build_tax_nodes)
   const uint4 *nodes;
   const uint8_t *bases;
   const uint64_t *offsets;
@@ -410,7 +466,7 @@ struct ClassifyCall {
   Thresholds thr{};
   int32_t C = 0, min_hit_groups = 0;
   bool want_hits = false;
-  uint64_t span_shift = 0;   // slots the span arrays are moved by for this call (capi.hip: sub_call)
+  uint64_t span_shift = 0;   // slots the span arrays are moved by for this call (classify.hip: sub_call)
 };
 // the staged classify kernel over the spans of c.in (map_scratch: their key slots, dead after the probe)
 void launch_classify(const int32_t *parents, const uint4 *nodes, int32_t T, const ClassifyCall &c, const int32_t *span_meta,

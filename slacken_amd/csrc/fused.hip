@@ -49,11 +49,6 @@ struct __attribute__((aligned(16))) WaveLds {
 };
 
 // ---- wave helpers ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_sync() {  // order this wave's LDS traffic (lanes of one wave exchange data via LDS)
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
   uint32_t lo = __shfl((uint32_t)v, src), hi = __shfl((uint32_t)(v >> 32), src);
   return ((uint64_t)hi << 32) | lo;
@@ -70,14 +65,6 @@ __device__ __forceinline__ uint64_t from_prev(uint64_t v) {
   uint32_t hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), 0x138, 0xF, 0xF, true);
   return ((uint64_t)hi << 32) | lo;
 }
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int src) {  // src wave-uniform; result wave-uniform
-  uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src), hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t bcast64(uint64_t v) {  // lane 0 -> all, result is wave-uniform
-  uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ int wave_sum(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -88,7 +75,6 @@ __device__ __forceinline__ int wave_max(int v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
   return v;
 }
-__device__ __forceinline__ uint64_t umin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ int lanes_below(uint64_t mask) {  // popcount(mask & lanes lower than this one)
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
@@ -285,12 +271,6 @@ __device__ int32_t lca_uniform(const int32_t *parents, int32_t ntax, int32_t a, 
   return 1;
 }
 
-// {parent, tin, tout, -} of taxon t (engine.h: FusedArgs.nodes); wave-uniform t: a scalar load.  An id outside the taxonomy is a
-// tree of its own.
-__device__ __forceinline__ uint4 tax_node(const FusedArgs &A, int32_t t) {
-  return ((uint32_t)t < (uint32_t)A.ntax) ? A.nodes[t] : make_uint4(0u, 0x40000000u + (uint32_t)t, 0x40000000u + (uint32_t)t, 0u);
-}
-
 // resolveTree over the LDS map on the taxonomy's Euler-tour intervals (lane.hip has the same for its 12-slot maps):
 // one lane per distinct taxon.  Each loads its taxon's interval once; a taxon's root-path score is the count of the entries whose
 // interval holds its tin, a candidate's clade sum that of the entries whose tin its interval holds; the confidence walk jumps to
@@ -304,7 +284,7 @@ __device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArg
   for (int b0 = 0; b0 < D; b0 += 64) {
     const int i = b0 + lane;
     if (i < D) {
-      const uint4 n = tax_node(A, dense[i].x);
+      const uint4 n = tax_node(A.nodes, A.ntax, dense[i].x);
       tin[i] = n.y; tout[i] = n.z;
     }
   }
@@ -332,14 +312,14 @@ __device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArg
         if (maxTaxon == 0 || (tin_t <= m_in && m_in <= tout_t)) {   // LowestCommonAncestor.apply :49-78 by intervals
           maxTaxon = tt; m_in = tin_t; m_out = tout_t;
         } else if (!(m_in <= tin_t && tin_t <= m_out)) {          // neither holds the other: the first node above that holds tt
-          int32_t x = (int32_t)tax_node(A, maxTaxon).x;
+          int32_t x = (int32_t)tax_node(A.nodes, A.ntax, maxTaxon).x;
           uint4 nx = make_uint4(0, 0, 0, 0);
           while (x != 0) {
-            nx = tax_node(A, x);
+            nx = tax_node(A.nodes, A.ntax, x);
             if (nx.y <= tin_t && tin_t <= nx.z) break;
             x = (int32_t)nx.x;
           }
-          if (x == 0) { x = 1; nx = tax_node(A, 1); }             // no common node: ROOT (:77)
+          if (x == 0) { x = 1; nx = tax_node(A.nodes, A.ntax, 1); }             // no common node: ROOT (:77)
           maxTaxon = x; m_in = nx.y; m_out = nx.z;
         }
       }
@@ -381,9 +361,9 @@ __device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArg
         have_cur = false;
         wave_sync();
       } else {
-        if (!have_cur) cur = tax_node(A, mt);
+        if (!have_cur) cur = tax_node(A.nodes, A.ntax, mt);
         mt = (int32_t)cur.x;                       // Taxonomy.parents
-        if (mt != 0) { cur = tax_node(A, mt); have_cur = true; cin = cur.y; cout = cur.z; }
+        if (mt != 0) { cur = tax_node(A.nodes, A.ntax, mt); have_cur = true; cin = cur.y; cout = cur.z; }
       }
     }
     const bool classified = (mt != 0) && (nd >= A.min_hit_groups);  // Classifier.scala:445
@@ -794,19 +774,6 @@ template <> struct __attribute__((aligned(16))) SegHitLds<true> {
   uint32_t flushed[64];       // entries of the lane that are in the scratch region
 };
 
-// (room: bytes from seq to the end of the caller's buffer -- the buffer's last block is assembled from byte loads)
-__device__ __forceinline__ uint4 seg_refill(SegLds *G, int lane, const uint8_t *seq, uint32_t p, uint32_t n, uint32_t room) {
-  uint4 v[SEG_SBLK];
-#pragma unroll
-  for (int i = 0; i < SEG_SBLK; i++) {
-    v[i] = make_uint4(0, 0, 0, 0);
-    if (p + 16u * i < n) v[i] = load_block16(seq + p + 16u * i, room - (p + 16u * i));
-  }
-#pragma unroll
-  for (int i = 1; i < SEG_SBLK; i++) G->sbuf[(i - 1) * 64 + lane] = v[i];
-  return v[0];
-}
-
 // A lane writes the entries of its queue that have arrived to its stretch of the scratch region (`mine`): whole groups of SEG_QG
 // consecutive entries (32 contiguous bytes) as long as the queue did not overflow in the last chunk; everything, entry by entry, when
 // it did (the surplus is in the region already) or at the end (ALL).
@@ -883,7 +850,7 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
     uint32_t cur = 0, b1 = 0, b2 = 0, b3 = 0;
     int sb = 1;
     if (!fin) {
-      uint4 v = seg_refill(G, lane, seq, 0, n, room);
+      uint4 v = stream_refill<SEG_SBLK>(G, lane, seq, 0, n, room);
       cur = v.x; b1 = v.y; b2 = v.z; b3 = v.w;
     }
     int run_class = 0;
@@ -963,7 +930,7 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
           if (refill && pos < n) {
             uint4 v;
             if (sb < SEG_SBLK) { v = G->sbuf[(sb - 1) * 64 + lane]; sb++; }
-            else { v = seg_refill(G, lane, seq, pos, n, room); sb = 1; }
+            else { v = stream_refill<SEG_SBLK>(G, lane, seq, pos, n, room); sb = 1; }
             cur = v.x; b1 = v.y; b2 = v.z; b3 = v.w;
           }
         }
@@ -1153,7 +1120,7 @@ void launch_fused(int mode, const FusedArgs &A, hipStream_t s) {
   // a persistent grid (measured: one block per four fragments is 10 % slower for 150-base reads -- the per-wave set-up is
   // not free here, unlike in the lane kernel); the deferral pass, whose length is only known on the device, likewise
   uint64_t blocks = (A.R + FW - 1) / FW;
-  static const int bpc = getenv("SLK_FUSED_BLOCKS_PER_CU") ? atoi(getenv("SLK_FUSED_BLOCKS_PER_CU")) : 8;  // (tuning experiment)
+  static const int bpc = (int)env_long("SLK_FUSED_BLOCKS_PER_CU", 8);  // (tuning experiment)
   const uint64_t cap = (A.work_list || bpc <= 0) ? 256 * 8 : (uint64_t)256 * bpc;
   if (blocks > cap) blocks = cap;
   dim3 g((unsigned)blocks), b(FW * 64);

@@ -1,6 +1,6 @@
-// hostside.h -- what the host-side translation units of the library share (capi.hip: the C ABI of one index / one stream;
-// shardset.hip: the table-sharded set of indices): the handles' structures, error reporting, the staged copies between caller
-// memory and HBM.  Internal: not part of the C ABI.
+// hostside.h -- what the host-side translation units of the library share (index.hip / classify.hip / capi.hip: the C ABI of one
+// index / one stream; shardset.hip: the table-sharded set of indices): the handles' structures, error reporting, the staged copies
+// between caller memory and HBM.  Internal: not part of the C ABI.
 #pragma once
 #include "../../include/slacken_amd.h"
 #include "engine.h"
@@ -96,11 +96,6 @@ struct DevBuf {   // device scratch that grows on demand
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T *as() const { return (T *)p; }
 };
-
-// SLK_* switches of the environment.  Which of them are read once per process (a `static const` at the place of use) and which
-// per call (tests move those) is the caller's business.
-inline bool env_on(const char *name) { const char *e = getenv(name); return e != nullptr && e[0] == '1'; }
-inline long env_long(const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; }
 
 // ---- host side of the copies ----------------------------------------------------------------------------------------------
 // A few threads that move bytes between the caller's (pageable) memory and the pinned staging buffers: one thread copies
@@ -236,7 +231,7 @@ struct slk_index {
   std::vector<int32_t> h_parents;  // host copy, for the dense renumbering at finalize
   // dense taxon ids (engine.h: TableView.to_orig): set up by slk_index_finalize when the caller's ids need more than 22 bits
   DevPtr<int32_t> d_parents_dense, d_to_orig, d_to_dense;
-  // Euler tours (capi.hip: build_tax_nodes).  The two owners: of the taxonomy as given (the staged classify kernel works in the
+  // Euler tours (index.hip: build_tax_nodes).  The two owners: of the taxonomy as given (the staged classify kernel works in the
   // caller's ids; null: more than 2^26 ids) and of the dense renumbering.  d_nodes is a VIEW of one of them: kernel_parents() with
   // its tour (engine.h: FusedArgs.nodes); null: more than 2^22 ids, no lane kernel.
   DevPtr<uint4> d_nodes_orig, d_nodes_dense;
@@ -245,10 +240,10 @@ struct slk_index {
   bool finalized = false;
   int32_t max_disp = 0;
   uint64_t records = 0, dups = 0;
-  uint64_t unplaced = 0;           // records of the last insert that found no cell within reach of the displacement field (capi.hip: insert_growing)
+  uint64_t unplaced = 0;           // records of the last insert that found no cell within reach of the displacement field (index.hip: insert_growing)
   uint32_t grown = 0;              // times the table was moved to a larger one because of that
   float load_target = 0;           // the load factor the table was sized for (given, or chosen by the free memory: slk_index_create)
-  bool spent = false;              // the table was lost while it was growing (capi.hip: grow_table): only slk_index_destroy takes the index
+  bool spent = false;              // the table was lost while it was growing (index.hip: grow_table): only slk_index_destroy takes the index
   Stream build_stream;
   DevBuf stage_keys, stage_taxa;
   Staging staging;    // host -> HBM copies of the build calls
@@ -397,7 +392,7 @@ inline int32_t copy_out(slk_stream *st, void *h_dst, const void *d_src, size_t n
 
 // Every entry point that takes an index starts here: select the index's device and drop whatever error code an earlier,
 // unrelated HIP call of this thread (this library's or the application's) left behind, so that the hipGetLastError()
-// after a launch reports that launch.  An index that lost its table (capi.hip: grow_table) is refused.
+// after a launch reports that launch.  An index that lost its table (index.hip: grow_table) is refused.
 inline int32_t check_spent(const slk_index *ix) {
   if (ix->spent)
     return fail(SLK_E_STATE, "this index lost its records when its table could not grow: destroy it and repeat the load (with a larger "
@@ -424,7 +419,7 @@ struct DrainOnExit {
   }
 };
 
-// defined in capi.hip, used by shardset.hip and bracken.hip too; not exported (the library exports its extern "C" names only)
+// defined in classify.hip, used by shardset.hip and bracken.hip too; not exported (the library exports its extern "C" names only)
 namespace slk {
 int32_t check_status(slk_stream *st);   // call after the stream has been synchronised
 uint64_t span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired);
@@ -434,4 +429,25 @@ bool lane_path_ok(const slk_index *ix);
 int32_t upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
                      const uint64_t *mate_offsets, uint64_t R, uint64_t *total, uint64_t *mate_total);
 int32_t counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets, uint64_t capacity);
+Thresholds thresholds_of(const double *v, int32_t C);
+int32_t ensure_outputs(slk_stream *st, uint64_t R, int32_t C);   // the stream's result rows (out_taxon .. out_nh) for R fragments
+struct HostRows { int32_t *taxon; uint8_t *classified; int32_t *nd, *tk; };   // a host call's results in the caller's memory (nullable from nd on)
+int32_t download_rows(slk_stream *st, const HostRows &out, uint64_t R, int32_t C);   // complete on return
+
+inline int ceil_log2_u64(uint64_t x) {
+  int b = 0;
+  while (b < 63 && (1ULL << b) < x) b++;
+  return b;
+}
+
+// argument checks the entry points repeat
+inline int32_t check_thresholds(const double *thresholds, int32_t C) {
+  return C < 1 || C > MAX_THRESHOLDS || !thresholds ? fail(SLK_E_INVALID, "need 1..%d thresholds", MAX_THRESHOLDS) : SLK_OK;
+}
+inline int32_t check_mates(const void *mate_bases, const void *mate_offsets) {
+  return (mate_bases == nullptr) != (mate_offsets == nullptr) ? fail(SLK_E_INVALID, "mate_bases and mate_offsets must be given together") : SLK_OK;
+}
+inline int32_t check_one_id_column(const slk_index *ix) {
+  return ix->W > 1 ? fail(SLK_E_UNSUPPORTED, "the staged and sharded entry points support minimizers of up to 32 nt (one id column)") : SLK_OK;
+}
 }  // namespace slk

@@ -242,12 +242,10 @@ __global__ void __launch_bounds__(256) probe_kernel(TableView T, const uint64_t 
 // ---------------------------------------------------------------------------------------------------------------
 struct Tax {
   const int32_t *parents;
-  const uint4 *nodes;   // {parent, tin, tout, -} per id from a depth-first tour (capi.hip: build_tax_nodes), or null
+  const uint4 *nodes;   // {parent, tin, tout, -} per id from a depth-first tour (index.hip: build_tax_nodes), or null
   int32_t T;
   __device__ __forceinline__ int32_t parent(int32_t t) const { return ((uint32_t)t < (uint32_t)T) ? parents[t] : 0; }
-  __device__ __forceinline__ uint4 node(int32_t t) const {   // an id outside the taxonomy is a tree of its own
-    return ((uint32_t)t < (uint32_t)T) ? nodes[t] : make_uint4(0u, 0x40000000u + (uint32_t)t, 0x40000000u + (uint32_t)t, 0u);
-  }
+  __device__ __forceinline__ uint4 node(int32_t t) const { return tax_node(nodes, T, t); }
 };
 
 // LowestCommonAncestor.apply :49-78 without the path buffer: first node on b's path that lies on a's path.
@@ -534,7 +532,7 @@ __global__ void __launch_bounds__(256) merged_hits_kernel(const uint64_t *__rest
   }
 }
 
-// ---- launchers (called from capi.hip) ----
+// ---- launchers (called from index.hip and classify.hip) ----
 // slk_index_finalize, dense taxon ids: the taxon field of every cell becomes to_dense[taxon] (cells whose taxon has no dense
 // id -- not a node of the taxonomy -- are counted; the caller first counts, and rewrites only if there are none)
 __global__ void __launch_bounds__(256) remap_cells_kernel(uint64_t *__restrict__ cells, uint64_t ncells, int32_t taxon_bits,

@@ -8,7 +8,7 @@
 // and probed cooperatively: 4 lanes read one bucket (4 x 16 B = one HBM line), 16 probes per wave instruction, four
 // instructions in flight per batch of 64.
 //
-//   scan    each lane consumes its read 16 bytes at a time (fetched 80 at a time, see stream_refill), rolls the forward and
+//   scan    each lane consumes its read 16 bytes at a time (fetched 80 at a time, see stream_refill in engine.h), rolls the forward and
 //           reverse-complement m-mer,
 //           takes the canonical / XOR / spaced-seed key, a width-w sliding minimum (registers for w = 5, a van-Herk
 //           prefix/suffix ring in LDS otherwise) and merges equal consecutive minima into super-mer spans.
@@ -89,13 +89,6 @@ __device__ __forceinline__ ulonglong2 SLK_PROBE_LOAD(const ulonglong2 *p) {
 #endif
 }
 
-__device__ __forceinline__ void lane_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint64_t lmin64(uint64_t a, uint64_t b) { return a < b ? a : b; }
-
 // Fold entry `meta`'s hit into its owner's 12-slot map: ONE round of LDS atomics per batch (NONE hits carry no information
 // for resolveTree and are dropped).
 template <bool LONG>
@@ -154,7 +147,7 @@ __device__ __forceinline__ int probe_batch(LaneLds *L, uint32_t *ocnt, const Tab
   st.z = (uint32_t)tag; st.w = (uint32_t)(tag >> 32);
   ((uint4 *)L->stash)[lane] = st;
   L->found[lane] = 0;
-  lane_wave_sync();
+  wave_sync();
   const int g = lane / LPB, c = lane % LPB;                               // 64 / LPB groups of LPB lanes
   const uint64_t tmask = (1ULL << T.g.taxon_bits) - 1;
   const char *cellbase = (const char *)T.cells + c * 16;
@@ -193,7 +186,7 @@ __device__ __forceinline__ int probe_batch(LaneLds *L, uint32_t *ocnt, const Tab
       const uint64_t k_old = L->q_key[qj];
       const uint16_t o_old = HITS ? L->q_ord[qj] : (uint16_t)0;
       const uint64_t R = __ballot(again);
-      lane_wave_sync();  // every key is in registers before a tail slot (which may wrap onto this batch) is written
+      wave_sync();  // every key is in registers before a tail slot (which may wrap onto this batch) is written
       if (again) {
         const int slot = (qhead + qn + requeued + __builtin_amdgcn_mbcnt_hi((uint32_t)(R >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)R, 0))) & (QCAP - 1);
         L->q_key[slot] = k_old;
@@ -203,7 +196,7 @@ __device__ __forceinline__ int probe_batch(LaneLds *L, uint32_t *ocnt, const Tab
       requeued += __popcll(R);
     }
   }
-  lane_wave_sync();
+  wave_sync();
   // step 3: one lane per entry
   const int32_t taxon = (int32_t)L->found[lane];
   if (!SLK_TUNE_ON(2)) fold_hit<LONG>(L, ocnt, in, meta, taxon);
@@ -214,7 +207,7 @@ __device__ __forceinline__ int probe_batch(LaneLds *L, uint32_t *ocnt, const Tab
     hit_taxon[at] = ext_taxon(T, taxon);
     hit_meta[at] = pack_meta((int32_t)((meta >> 7) & 0x1FFF), 1, (meta >> 6) & 1);
   }
-  lane_wave_sync();
+  wave_sync();
   return requeued;
 }
 
@@ -246,10 +239,6 @@ template <class T> __device__ __forceinline__ void SLK_STREAM_STORE(T *p, T v) {
 // The step kernel runs the local kernel's scan, so it forms the same probe batches in the same order; instead of probing them it
 // appends a batch's keys to the send regions of their owners and logs where each owner's group went.  Nothing but 8-byte keys,
 // 4-byte taxa and the log touches HBM: no per-probe slot addresses, no scatter of the answers, no compaction of the lists.
-__device__ __forceinline__ uint64_t lane_readlane64(uint64_t v, int src) {
-  uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, src), hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), src);
-  return ((uint64_t)hi << 32) | lo;
-}
 __device__ __forceinline__ uint32_t shard_owner(uint64_t key, uint32_t ns) {  // == slk_shard_of
   const uint64_t h = fmix64(key);
   return (ns & (ns - 1)) == 0 ? (uint32_t)(h & (ns - 1)) : (uint32_t)(h % ns);
@@ -276,7 +265,7 @@ __device__ __forceinline__ void side_probe(LaneLds *L, const TableView &T, const
   st.x = home; st.y = 0; st.z = (uint32_t)tag; st.w = (uint32_t)(tag >> 32);
   ((uint4 *)L->stash)[lane] = st;
   L->found[lane] = 0;
-  lane_wave_sync();
+  wave_sync();
   const int g = lane / LPB, c = lane % LPB;
   const uint64_t tmask = (1ULL << T.g.taxon_bits) - 1;
   const char *cellbase = (const char *)T.cells + c * 16;
@@ -301,7 +290,7 @@ __device__ __forceinline__ void side_probe(LaneLds *L, const TableView &T, const
     const uint64_t B = __ballot(m0 || m1 || e0 || e1 || !act || closed);
     if (((B >> (g * LPB)) & ((1u << LPB) - 1)) == 0) unresolved |= 1u << s;
   }
-  lane_wave_sync();
+  wave_sync();
   int32_t taxon = (int32_t)L->found[lane];
   const uint32_t ur = (uint32_t)__shfl((int)unresolved, (lane % PG) * LPB);   // entry `lane` was group lane % PG of step lane / PG
   if (in && ((ur >> (lane / PG)) & 1)) {
@@ -323,7 +312,7 @@ __device__ __forceinline__ void side_probe(LaneLds *L, const TableView &T, const
     }
   }
   if (in && !SLK_TUNE_ON(128)) SLK_STREAM_STORE(&S.side_out[i], ext_taxon(T, taxon));   // (128: timing experiment, the answers are not written)
-  lane_wave_sync();
+  wave_sync();
 }
 
 // APPLY job: the tile's rows of the log, four at a time -- lane i takes the i-th entry of a logged probe batch in (owner, rank)
@@ -380,7 +369,7 @@ __device__ __forceinline__ void apply_rows(LaneLds *L, const ApplyJob &J, int la
         fold_hit<false>(L, nullptr, in[u], meta[u], t);
       }
     }
-    lane_wave_sync();
+    wave_sync();
   }
 }
 
@@ -438,41 +427,7 @@ __device__ __forceinline__ void emit_batch(LaneLds *L, const FusedArgs &A, const
       SLK_STREAM_STORE(&S.send_meta[at], meta);
     }
   }
-  lane_wave_sync();
-}
-
-// {parent, tin, tout, -} of taxon t (engine.h: FusedArgs.nodes); an id outside the taxonomy is a tree of its own
-__device__ __forceinline__ uint4 lane_node(const uint4 *nodes, int32_t ntax, int32_t t) {
-  return ((uint32_t)t < (uint32_t)ntax) ? nodes[t] : make_uint4(0u, 0x40000000u + (uint32_t)t, 0x40000000u + (uint32_t)t, 0u);
-}
-// BitRepresentation.charToTwobit (BitRepresentation.scala:127-135) for one character: 0..3, or 5 for anything else
-__device__ __forceinline__ int lane_code(uint32_t c) {
-  const uint32_t VM = (1u << 1) | (1u << 3) | (1u << 7) | (1u << 20) | (1u << 21);  // A C G T U, either case
-  bool ok = ((c & 0xC0) == 0x40) && ((VM >> (c & 31)) & 1);
-  uint32_t t = (c >> 1) & 3;  // A,C,T/U,G -> 0,1,2,3
-  t ^= t >> 1;                // -> A=0 C=1 G=2 T=3
-  return ok ? (int)t : 5;
-}
-
-// Read stream.  A lane consumes its read 16 bytes at a time; fetching those 16 bytes alone every 16 steps asks the L2 for
-// every 64-byte line about four times, and with 20 waves x 64 lanes per CU the lines do not survive in the L2 between two
-// requests (PMC: ~1.0e8 of 5.2e8 fabric reads per launch were re-fetched read bytes).  So a refill fetches SBLK sub-blocks
-// back to back (the L1 merges requests to a line that is already on its way), keeps the first in registers and parks the
-// others in the lane's own LDS slots.  Measured per 10 M x 150 bp launch: 16 bytes per refill 9.28 ms, 48: 9.0, 64: 8.8,
-// 80: 8.5 (two refills per 150-base read), 96: 8.6, 112 and more: slower (the LDS they take costs resident waves).  Sub-blocks
-// starting at or beyond the end of the read are not fetched, and the block that holds the last bytes of the caller's buffer
-// is assembled from byte loads (load_block16; `room` = bytes from seq to the end of the buffer): nothing outside the buffer
-// is touched.
-__device__ __forceinline__ uint4 stream_refill(LaneLds *L, int lane, const uint8_t *seq, uint32_t p, uint32_t n, uint32_t room) {
-  uint4 v[SBLK];
-#pragma unroll
-  for (int i = 0; i < SBLK; i++) {
-    v[i] = make_uint4(0, 0, 0, 0);
-    if (p + 16u * i < n) v[i] = load_block16(seq + p + 16u * i, room - (p + 16u * i));
-  }
-#pragma unroll
-  for (int i = 1; i < SBLK; i++) L->sbuf[(i - 1) * 64 + lane] = v[i];
-  return v[0];
+  wave_sync();
 }
 
 // ---- the read stream as whole 128-byte lines (SLK_PACKED_STREAM) ----------------------------------------------------------------
@@ -562,7 +517,7 @@ __device__ __attribute__((noinline)) void hand_on(unsigned long long *hdr, uint3
     const int leader = __ffsll((long long)M) - 1;
     unsigned long long at = 0;
     if (lane == leader) at = atomicAdd(&hdr[HandOn::count_word(l)], (unsigned long long)__popcll(M));
-    at = lane_readlane64(at, leader);
+    at = readlane64(at, leader);
     if (dfr && route == l)
       lists[HandOn::list_at(l, stride, long_cap) + at + __builtin_amdgcn_mbcnt_hi((uint32_t)(M >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)M, 0))] = (uint32_t)r;
   }
@@ -648,7 +603,7 @@ __device__ __forceinline__ void resolve_lane(LaneLds *L, uint32_t *ocnt, const F
 #pragma unroll
     for (int j = 0; j < OMAP; j++) {
       if (j < D) {
-        const uint4 nj = lane_node(A.nodes, A.ntax, ENT_TAXON(j));
+        const uint4 nj = tax_node(A.nodes, A.ntax, ENT_TAXON(j));
         tin[j * 64 + lane] = nj.y;
         tout[j * 64 + lane] = nj.z;
       }
@@ -672,14 +627,14 @@ __device__ __forceinline__ void resolve_lane(LaneLds *L, uint32_t *ocnt, const F
         } else if (ain <= m_in && m_in <= aout) {
           maxTaxon = ENT_TAXON(a); m_in = ain; m_out = aout;
         } else {                   // neither: the first node above maxTaxon whose interval holds this taxon
-          int32_t x = (int32_t)lane_node(A.nodes, A.ntax, maxTaxon).x;
+          int32_t x = (int32_t)tax_node(A.nodes, A.ntax, maxTaxon).x;
           uint4 nx = make_uint4(0, 0, 0, 0);
           while (x != 0) {
-            nx = lane_node(A.nodes, A.ntax, x);
+            nx = tax_node(A.nodes, A.ntax, x);
             if (nx.y <= ain && ain <= nx.z) break;
             x = (int32_t)nx.x;
           }
-          if (x == 0) { x = 1; nx = lane_node(A.nodes, A.ntax, 1); }   // no common node: ROOT (:77)
+          if (x == 0) { x = 1; nx = tax_node(A.nodes, A.ntax, 1); }   // no common node: ROOT (:77)
           maxTaxon = x; m_in = nx.y; m_out = nx.z;
         }
       }
@@ -718,9 +673,9 @@ __device__ __forceinline__ void resolve_lane(LaneLds *L, uint32_t *ocnt, const F
           mt = ENT_TAXON(up); cin = up_in; cout = tout[up * 64 + lane];
           have_cur = false;
         } else {
-          if (!have_cur) cur = lane_node(A.nodes, A.ntax, mt);
+          if (!have_cur) cur = tax_node(A.nodes, A.ntax, mt);
           mt = (int32_t)cur.x;                                           // Taxonomy.parents
-          if (mt != 0) { cur = lane_node(A.nodes, A.ntax, mt); have_cur = true; cin = cur.y; cout = cur.z; }
+          if (mt != 0) { cur = tax_node(A.nodes, A.ntax, mt); have_cur = true; cin = cur.y; cout = cur.z; }
         }
       }
     }
@@ -795,14 +750,14 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
       if (it) {
         unsigned long long t = 0;
         if (lane == 0) t = atomicAdd(&A.hand_hdr[HandOn::LONG_DRAW], 1ULL);
-        tile = nwaves + lane_readlane64(t, 0);
+        tile = nwaves + readlane64(t, 0);
       }
     } else if (MODE == LANE_EMIT) {
       // persistent waves (they carry their chunks from tile to tile), tiles drawn from a counter as above
       if (it) {
         unsigned long long t = 0;
         if (lane == 0) t = atomicAdd(&S.cursors[S.n_shards], 1ULL);
-        tile = nwaves + lane_readlane64(t, 0);
+        tile = nwaves + readlane64(t, 0);
       }
     } else if (it) {
       tile += nwaves;
@@ -857,7 +812,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
       const bool have2 = r2 < Jp->A.R;
       const uint2 tr = Jp->tile_rows[tile];   // (wave-uniform load) {first row of the tile in the log, rows}
       if (HITS) L->rb[lane] = have2 ? span_region(Jp->A.offsets, Jp->A.mate_offsets, r2) : 0;
-      lane_wave_sync();                       // (the map's reset above and the span regions are seen by every lane)
+      wave_sync();                       // (the map's reset above and the span regions are seen by every lane)
       apply_rows<HITS>(L, *Jp, lane, tr.x, tr.y);
       const bool dfr2 = have2 && (Jp->defer[r2] != 0 || (L->o_flags[lane] & 0x80000000u));   // not taken by its EMIT, or its map overflowed just now
       const uint64_t DM = __ballot(dfr2);
@@ -873,7 +828,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
           resolve_lane<HITS, false>(L, nullptr, Jp->A, lane, r2, L->o_flags[lane], ri.x, ri.y, 0, dbg);
         }
       }
-      lane_wave_sync();                       // (resolve_lane's intervals lay over the queue and the read stream's slots: the scan below stages its first bytes there)
+      wave_sync();                       // (resolve_lane's intervals lay over the queue and the read stream's slots: the scan below stages its first bytes there)
     }
     // ---- scan state ----
     uint32_t pos = 0;
@@ -916,7 +871,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
             }
           }
         }
-        lane_wave_sync();
+        wave_sync();
       }
     }
     if (!fin && n > 0) {
@@ -924,7 +879,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
         const uint2 pk = packed_take(pcodes, pvalid, s0);
         cur = pk.x; b1 = pk.y;
       } else {
-        uint4 v = stream_refill(L, lane, seq, 0, n, room);
+        uint4 v = stream_refill<SBLK>(L, lane, seq, 0, n, room);
         cur = v.x; b1 = v.y; b2 = v.z; b3 = v.w;
       }
     }
@@ -998,16 +953,16 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
       const uint64_t key = (canon ^ P.xmask) & P.smask;                        // RandomXOR, then SpacedSeed
       uint64_t minv;
       if (W5) {
-        const uint64_t p = lmin64(key, k1);
-        const uint64_t m4 = lmin64(p, p2);
-        minv = lmin64(key, m41);  // minimum of the last five keys
+        const uint64_t p = umin64(key, k1);
+        const uint64_t m4 = umin64(p, p2);
+        minv = umin64(key, m41);  // minimum of the last five keys
         // pushed unconditionally: a window is only used once the last five pushes were keys of the current run
         k1 = key; p2 = p1; p1 = p; m41 = m4;
       } else {
         // van Herk: window = suffix of the previous w-block  U  prefix of the current one (blocks on the step counter)
         const uint64_t kk = havekey ? key : ~0ULL;
-        pre = lmin64(pre, kk);
-        minv = (tphase == w - 1) ? pre : lmin64(pre, win[(tphase + 1) * 64 + lane]);  // row tphase + 1: still the previous block's
+        pre = umin64(pre, kk);
+        minv = (tphase == w - 1) ? pre : umin64(pre, win[(tphase + 1) * 64 + lane]);  // row tphase + 1: still the previous block's
         win[tphase * 64 + lane] = kk;                                                  // row tphase: its suffix minimum was used last step
       }
       const bool havewin = havekey && nvalid >= (uint32_t)k;  // a k-mer window is complete: its minimizer VALUE is minv
@@ -1039,7 +994,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
             if (pos < n) {
               uint4 v;
               if (sb < SBLK) { v = L->sbuf[(sb - 1) * 64 + lane]; sb++; }
-              else { v = stream_refill(L, lane, seq, pos, n, room); sb = 1; }
+              else { v = stream_refill<SBLK>(L, lane, seq, pos, n, room); sb = 1; }
               cur = v.x; b1 = v.y; b2 = v.z; b3 = v.w;
             }
           }
@@ -1061,7 +1016,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
             const uint64_t o2 = A.mate_offsets[r];
             seq = A.mate_bases + o2; n = (uint32_t)(A.mate_offsets[r + 1] - o2); room = clamp_room(mates_end - o2); pos = 0;
             if (n > 0) {
-              uint4 v = stream_refill(L, lane, seq, 0, n, room);
+              uint4 v = stream_refill<SBLK>(L, lane, seq, 0, n, room);
               sb = 1;
               cur = v.x; b1 = v.y; b2 = v.z; b3 = v.w;
             }
@@ -1073,7 +1028,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
       if (!W5) {  // end of a w-block: rebuild the suffix minima of the block just completed (wave-uniform control flow)
         if (tphase == w - 1) {
           uint64_t sm = ~0ULL;
-          for (int j = w - 1; j >= 0; j--) { sm = lmin64(sm, win[j * 64 + lane]); win[j * 64 + lane] = sm; }  // in place
+          for (int j = w - 1; j >= 0; j--) { sm = umin64(sm, win[j * 64 + lane]); win[j * 64 + lane] = sm; }  // in place
           tphase = 0;
         } else {
           tphase++;
@@ -1099,7 +1054,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
         // (a loop, not an if: a batch can hand entries back -- bucket overflows re-queued with a larger displacement -- and
         // the next step may push 64 more; fewer than 64 must be left so that the 128-entry ring cannot overflow)
         while (qn >= 64) {
-          lane_wave_sync();
+          wave_sync();
           int back = 0;
           if (MODE == LANE_EMIT) emit_batch<HITS>(L, A, S, *Jp, qhead, 64, lane, row++, tile, ch_pos, ch_end, side_j, side_key, dbg);
           else if (!SLK_TUNE_ON(1)) back = probe_batch<HITS, LONG>(L, ocnt, A.T, qhead, qn, 64, lane, dbg, A.span_meta, A.span_taxon);
@@ -1109,7 +1064,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
       }
     }
     while (qn > 0) {  // drain, including entries re-queued by the batches themselves
-      lane_wave_sync();
+      wave_sync();
       const int cnt = min(qn, 64);
       int back = 0;
       if (MODE == LANE_EMIT) emit_batch<HITS>(L, A, S, *Jp, qhead, cnt, lane, row++, tile, ch_pos, ch_end, side_j, side_key, dbg);
@@ -1117,7 +1072,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
       qhead = (qhead + cnt) & (QCAP - 1);
       qn += back - cnt;
     }
-    lane_wave_sync();
+    wave_sync();
     if (MODE == LANE_EMIT) {
       if (tile < etiles) {   // what the APPLY cannot recompute without scanning again
         if (have) S.read_info[r] = make_int2(total, nhits);
@@ -1145,7 +1100,7 @@ __device__ __forceinline__ void lane_body(const FusedArgs &A, const ShardIO &S, 
     } else {
       if (have && too_long) defer[r] = 1;   // EMIT job: fragments this kernel does not take (the caller routes them)
     }
-    lane_wave_sync();
+    wave_sync();
   }
   if (MODE == LANE_EMIT) {
     // the tails of the chunks this wave still holds are never written: zero keys (they travel and are answered; nobody reads the answers)
@@ -1175,16 +1130,16 @@ static void launch_lane_mode(const FusedArgs &A, int32_t *defer, uint32_t max_le
   if (A.R == 0) return;
   const bool w5 = A.P.w == 5;
   const size_t per_wave = lane_lds_per_wave(HITS, w5, A.P.w, LONG);
-  static const int extra_lds = getenv("SLK_LANE_EXTRA_LDS") ? atoi(getenv("SLK_LANE_EXTRA_LDS")) : 0;  // (occupancy experiment)
+  static const int extra_lds = (int)env_long("SLK_LANE_EXTRA_LDS", 0);  // (occupancy experiment)
   size_t lds = per_wave * LW + (size_t)extra_lds;
   uint64_t tiles = (A.R + 63) / 64;
   uint64_t blocks = (tiles + LW - 1) / LW;
-  static const int bpc = getenv("SLK_LANE_BLOCKS_PER_CU") ? atoi(getenv("SLK_LANE_BLOCKS_PER_CU")) : 0;  // (tuning experiment)
+  static const int bpc = (int)env_long("SLK_LANE_BLOCKS_PER_CU", 0);  // (tuning experiment)
   if (bpc > 0 && blocks > (uint64_t)256 * bpc) blocks = (uint64_t)256 * bpc;
   if (LONG && blocks > 256 * 5) blocks = 256 * 5;   // (the number of hand-ons is only known on the device: the waves loop over them)
   dim3 g((unsigned)blocks), b(LW * 64);
 #ifdef SLK_TUNING
-  static const int dbg = getenv("SLK_DEBUG_ABLATE") ? atoi(getenv("SLK_DEBUG_ABLATE")) : 0;  // timing experiments only: 1 = no probes, 2 = no map updates
+  static const int dbg = (int)env_long("SLK_DEBUG_ABLATE", 0);  // timing experiments only: 1 = no probes, 2 = no map updates
 #else
   const int dbg = 0;
 #endif
@@ -1231,11 +1186,11 @@ static void launch_step_mode(const FusedArgs &A, const ShardIO &S, const ApplyJo
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)lane_step_kernel<W5, HITS>, LW * 64, lds) != hipSuccess || nb <= 0) nb = 4;
     if (W5) resident[1][HITS] = nb;
   }
-  static const int bpc = getenv("SLK_STEP_BLOCKS_PER_CU") ? atoi(getenv("SLK_STEP_BLOCKS_PER_CU")) : 0;  // (tuning experiment)
+  static const int bpc = (int)env_long("SLK_STEP_BLOCKS_PER_CU", 0);  // (tuning experiment)
   if (bpc > 0) nb = bpc;
   const uint64_t blocks = std::min<uint64_t>((tiles + LW - 1) / LW, (uint64_t)cus * nb);
 #ifdef SLK_TUNING
-  static const int dbg = getenv("SLK_DEBUG_ABLATE") ? atoi(getenv("SLK_DEBUG_ABLATE")) : 0;  // timing experiments only (4, 32, 128: see side_probe / emit_batch)
+  static const int dbg = (int)env_long("SLK_DEBUG_ABLATE", 0);  // timing experiments only (4, 32, 128: see side_probe / emit_batch)
 #else
   const int dbg = 0;
 #endif

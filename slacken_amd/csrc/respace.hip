@@ -13,7 +13,7 @@
 //
 // The taxon travels as the cell holds it (the dense id on an index that slk_index_finalize renumbered): the destination is given the
 // same taxon field and the same id tables.  The source is only read; LCA is associative, commutative and idempotent, so the pass can
-// be repeated into a fresh table from scratch (capi.hip does when a record finds no cell within the displacement limit).
+// be repeated into a fresh table from scratch (index.hip does when a record finds no cell within the displacement limit).
 #include <hip/hip_runtime.h>
 
 #include "engine.h"

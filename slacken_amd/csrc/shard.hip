@@ -15,12 +15,6 @@ namespace {
 
 constexpr int SW = 4;  // waves per block
 
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // 64 keys per wave iteration: lane i hashes key i; LPB lanes then read one bucket together (LPB x 16 B), 64 / LPB buckets per
 // wave instruction, LPB instructions in flight -- the access shape of the classify kernel's probe.  A key whose home bucket
 // is full without holding it, and has overflowed (its flag), continues alone in the next buckets.
@@ -52,7 +46,7 @@ __global__ void __launch_bounds__(SW * 64) lookup_coop_kernel(TableView T, const
     st.z = (uint32_t)tag;
     st.w = (uint32_t)(tag >> 32);
     stash[lane] = st;
-    wsync();
+    wave_sync();
     ulonglong2 cell[LPB];
 #pragma unroll
     for (int s = 0; s < LPB; s++) cell[s] = *(const ulonglong2 *)(cellbase + ((uint64_t)stash[s * PG + g].x << BUCKET_SHIFT));
@@ -69,7 +63,7 @@ __global__ void __launch_bounds__(SW * 64) lookup_coop_kernel(TableView T, const
       const uint64_t B = __ballot(m0 || m1 || e0 || e1 || !act || closed);
       if (((B >> (g * LPB)) & ((1u << LPB) - 1)) == 0) unresolved |= 1u << s;
     }
-    wsync();
+    wave_sync();
     int32_t taxon = (int32_t)stash[lane].y;
     // was entry `lane` unresolved?  its group was g' = lane % PG of step s' = lane / PG: ask lane LPB * g'
     const uint32_t ur = (uint32_t)__shfl((int)unresolved, (lane % PG) * LPB);
@@ -93,7 +87,7 @@ __global__ void __launch_bounds__(SW * 64) lookup_coop_kernel(TableView T, const
       }
     }
     if (in) out[i] = ext_taxon(T, taxon);
-    wsync();
+    wave_sync();
   }
 }
 
@@ -105,7 +99,7 @@ void launch_lookup_coop(const TableView &t, const int64_t *keys, uint64_t n, int
   // it wants every wave slot it can get (64 waves per CU: 12.8 ms per 3.9e8 keys with 8 waves per CU, alone, against a 68 GiB table).
   // Round 2 ran it BESIDE the scans of the next batch with 8 waves per CU (SLK_LOOKUP_BLOCKS_PER_CU=2), which was best against a
   // table small enough for the Infinity Cache; now the stages of the sharded pipeline follow each other on one stream.
-  static const int bpc = getenv("SLK_LOOKUP_BLOCKS_PER_CU") ? std::max(1, atoi(getenv("SLK_LOOKUP_BLOCKS_PER_CU"))) : 16;
+  static const int bpc = std::max(1, (int)env_long("SLK_LOOKUP_BLOCKS_PER_CU", 16));
   uint64_t blocks = std::min<uint64_t>((n + SW * 64 - 1) / (SW * 64), (uint64_t)256 * bpc);
   hipLaunchKernelGGL(lookup_coop_kernel, dim3((unsigned)blocks), dim3(SW * 64), 0, s, t, keys, n, out);
 }

@@ -298,23 +298,11 @@ int32_t staged_lookup(slk_shardset *set, const std::vector<const void *> &src_ke
                   [&](int a, int b) { return lay.soff[a][b]; });
 }
 
-int32_t ensure_outputs(slk_stream *st, uint64_t R, int32_t C) {
-  HIPCHK(st->out_taxon.ensure((size_t)C * R * 4));
-  HIPCHK(st->out_cls.ensure((size_t)C * R));
-  HIPCHK(st->out_nd.ensure(R * 4));
-  HIPCHK(st->out_tk.ensure(R * 4));
-  HIPCHK(st->out_nh.ensure(R * 4));
-  return SLK_OK;
-}
-
 // results of a member's staged batch to the caller's arrays (everything queued on its stream has been synchronised)
 int32_t download_staged(Member &mb, const slk_shard_batch &B, int32_t C) {
   slk_stream *st = mb.st;
   const uint64_t R = B.R;
-  int32_t rc = copy_out(st, B.out_taxon, st->out_taxon.p, (size_t)C * R * 4);
-  if (!rc) rc = copy_out(st, B.out_classified, st->out_cls.p, (size_t)C * R);
-  if (!rc && B.out_num_distinct) rc = copy_out(st, B.out_num_distinct, st->out_nd.p, R * 4);
-  if (!rc && B.out_total_kmers) rc = copy_out(st, B.out_total_kmers, st->out_tk.p, R * 4);
+  int32_t rc = download_rows(st, {B.out_taxon, B.out_classified, B.out_num_distinct, B.out_total_kmers}, R, C);
   if (rc) return rc;
   if (B.out_hit_offsets) {
     rc = counts_to_offsets(st, st->out_nh.as<int32_t>(), R, B.out_hit_offsets, B.out_hits ? B.hits_capacity : ~0ULL);
@@ -336,8 +324,7 @@ int32_t download_staged(Member &mb, const slk_shard_batch &B, int32_t C) {
 int32_t staged_round(slk_shardset *set, const RoundArgs &A) {
   const int W = set->n;
   std::vector<uint64_t> total(W, 0), mate_total(W, 0);
-  Thresholds thr{};
-  memcpy(thr.v, A.thresholds, A.C * sizeof(double));
+  const Thresholds thr = thresholds_of(A.thresholds, A.C);
   // scan into span arrays, count the keys per owner
   for (int g = 0; g < W; g++) {
     Member &mb = set->m[g];
@@ -954,12 +941,12 @@ int32_t run_rounds(slk_shardset *set, slk_shard_batch *batches, int rounds, bool
 
 int32_t check_batches(slk_shardset *set, slk_shard_batch *batches, int32_t rounds, bool on_device, const double *thresholds, int32_t C) {
   if (!set || !batches || rounds < 1) return fail(SLK_E_INVALID, "null argument");
-  if (C < 1 || C > MAX_THRESHOLDS || !thresholds) return fail(SLK_E_INVALID, "need 1..%d thresholds", MAX_THRESHOLDS);
+  if (int32_t rc = check_thresholds(thresholds, C)) return rc;
   for (int64_t i = 0; i < (int64_t)rounds * set->n; i++) {
     slk_shard_batch &B = batches[i];
     const int g = (int)(i % set->n);
     if (B.R && (!B.bases || !B.offsets || !B.out_taxon || !B.out_classified)) return fail(SLK_E_INVALID, "null argument (member %d)", g);
-    if ((B.mate_bases == nullptr) != (B.mate_offsets == nullptr)) return fail(SLK_E_INVALID, "mate_bases and mate_offsets must be given together");
+    if (int32_t rc = check_mates(B.mate_bases, B.mate_offsets)) return rc;
     if (B.R >= 0xFFFFFFFFull) return fail(SLK_E_INVALID, "a batch holds fewer than 2^32 fragments");
     if (on_device && (B.out_hit_offsets || B.out_hits)) return fail(SLK_E_UNSUPPORTED, "device-resident rounds return no hit lists");
     if (!on_device && B.out_hit_offsets) B.out_hit_offsets[0] = 0;

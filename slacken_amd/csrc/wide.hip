@@ -40,14 +40,6 @@ template <int W> __device__ __forceinline__ uint64_t key_hash(const uint64_t *k)
   return fmix64(h);
 }
 
-__device__ __forceinline__ int wide_code(uint8_t c) {  // BitRepresentation.charToTwobit :127-135; 5 = not a nucleotide
-  const uint32_t VM = (1u << 1) | (1u << 3) | (1u << 7) | (1u << 20) | (1u << 21);
-  bool ok = ((c & 0xC0) == 0x40) && ((VM >> (c & 31)) & 1);
-  uint32_t t = (c >> 1) & 3;
-  t ^= t >> 1;
-  return ok ? (int)t : 5;
-}
-
 template <int W> struct WideWriter {
   uint64_t *keys;
   int32_t *meta;
@@ -82,7 +74,7 @@ __device__ void wide_scan_mate(const WideParams &P, const uint8_t *__restrict__ 
   Key<W> zero{};
   for (uint32_t i = 0; i <= n; i++) {
     int t = 5, cls = -1;
-    if (i < n) { t = wide_code(seq[i]); cls = t < 4 ? 1 : 0; }
+    if (i < n) { t = base_code(seq[i]); cls = t < 4 ? 1 : 0; }
     if (run_len > 0 && cls != run_class) {
       if (run_class == 1 && nvalid >= (uint32_t)k) out.emit(cur_val, cur_run, 1);
       else if (run_len >= (uint32_t)k) out.emit(zero, (int32_t)run_len - (k - 1), 2);  // Supermers.scala:116-119

@@ -201,7 +201,7 @@ def test_flagged_buckets():
     ix = make(keys, taxa, 15, load_factor=0.8)
     info = ix.info()
     spare = info.bucket_bits - info.taxon_bits - (0 if info.buckets & (info.buckets - 1) == 0 else 1)
-    assert spare - 1 >= 4                      # the geometry has the flag bit (capi.hip: shape_of)
+    assert spare - 1 >= 4                      # the geometry has the flag bit (index.hip: shape_of)
     assert info.max_displacement >= 1                             # ... and records went past full buckets: those are flagged
     check(ix, taxa)
 

@@ -279,7 +279,7 @@ def _cut(w, length, rng):
 
 @pytest.mark.parametrize("k,m,spaces,canonical", [(45, 40, 7, True), (110, 100, 20, True)])
 def test_wide_reads_of_any_text(orc, k, m, spaces, canonical):
-    """wide_code is a classifier of its own (a bit trick over the byte): every byte value except the line breaks inside
+    """base_code (engine.h) is a classifier of its own (a bit trick over the byte): every byte value except the line breaks inside
     genome-derived reads, the junk a FASTQ line can hold, U for T, whole reads in lower case.  Only ACGTU in either case are
     nucleotides (BitRepresentation.scala:127-143); everything else splits the read."""
     rng = np.random.default_rng(31 * k + m)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A table announced for 6.0e9 records that receives 9.0e9 (slk_index_append_device, 2^27 at a time): it has to grow on the way
-(capi.hip: grow_table) -- on the device while both tables fit, through host memory with SLK_GROW_VIA_HOST=1 -- and every record must
+(index.hip: grow_table) -- on the device while both tables fit, through host memory with SLK_GROW_VIA_HOST=1 -- and every record must
 be found afterwards (a sample of 2^27 keys from the first, a middle and the last chunk, regenerated from their seeds).  GPU box."""
 import json
 import os

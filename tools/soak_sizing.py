@@ -3,7 +3,7 @@ be found again with its taxon, absent keys must miss, and the records must come 
 any number of buckets and its inverse, the displacement field, the buckets' overflow flag).  Every third case the library OUTGROWS
 its table -- expected_records is a fraction of what is appended, in several calls, so that the load passes what the cells'
 displacement field can count (loads of 0.8 to over 1 against 4- to 6-bit fields) -- and the table must grow instead of refusing
-(capi.hip: grow_table); SLK_SOAK_HOST_GROW=1 makes the growth go through host memory.  Run on the GPU box."""
+(index.hip: grow_table); SLK_SOAK_HOST_GROW=1 makes the growth go through host memory.  Run on the GPU box."""
 import sys
 sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
 import numpy as np
