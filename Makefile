@@ -27,9 +27,11 @@ $(STREAM_SUM): tools/stream_sum.hip
 	@mkdir -p slacken_amd/lib
 	$(HIPCC) -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -shared -o $@ tools/stream_sum.hip
 
-$(LIB): $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/index.hip $(CSRC)/classify.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/respace.hip $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h slacken_amd/host/pack.hpp include/slacken_amd.h
+HIPSRC := $(addprefix $(CSRC)/,kernels.hip fused.hip lane.hip build.hip shard.hip wide.hip capi.hip index.hip classify.hip shardset.hip bracken.hip migration.hip taxstats.hip respace.hip)
+
+$(LIB): $(HIPSRC) $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h slacken_amd/host/pack.hpp include/slacken_amd.h
 	@mkdir -p slacken_amd/lib
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(CSRC)/kernels.hip $(CSRC)/fused.hip $(CSRC)/lane.hip $(CSRC)/build.hip $(CSRC)/shard.hip $(CSRC)/wide.hip $(CSRC)/capi.hip $(CSRC)/index.hip $(CSRC)/classify.hip $(CSRC)/shardset.hip $(CSRC)/bracken.hip $(CSRC)/migration.hip $(CSRC)/taxstats.hip $(CSRC)/respace.hip -ldl
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIPSRC) -ldl
 
 # Parquet input of the CLI: the Arrow C++ libraries inside the pyarrow wheel, if there is one (no Arrow dev package here)
 PYARROW_DIR := $(shell python3 -c "import pyarrow, os; print(os.path.dirname(pyarrow.__file__))" 2>/dev/null)
@@ -48,7 +50,7 @@ slacken_amd/bin/parquet_sink.o: slacken_amd/host/parquet_sink.cpp slacken_amd/ho
 	@mkdir -p slacken_amd/bin
 	g++ -O2 -std=c++20 -Wall $(PQ_CXXFLAGS) -c -o $@ slacken_amd/host/parquet_sink.cpp
 
-$(CLI): slacken_amd/bin/parquet_source.o slacken_amd/bin/parquet_sink.o slacken_amd/host/library_writer.hpp slacken_amd/host/slacken_cli.cpp slacken_amd/host/taxonomy.hpp slacken_amd/host/seqio.hpp slacken_amd/host/pargz.hpp slacken_amd/host/parbz2.hpp slacken_amd/host/titles.hpp slacken_amd/host/output.hpp slacken_amd/host/migration.hpp slacken_amd/host/stats.hpp slacken_amd/host/pack.hpp include/slacken_amd.h $(LIB)
+$(CLI): slacken_amd/bin/parquet_source.o slacken_amd/bin/parquet_sink.o slacken_amd/host/slacken_cli.cpp $(wildcard slacken_amd/host/*.hpp) include/slacken_amd.h $(LIB)
 	@mkdir -p slacken_amd/bin
 	g++ -O2 -std=c++17 -Wall -o $@ slacken_amd/host/slacken_cli.cpp slacken_amd/bin/parquet_source.o slacken_amd/bin/parquet_sink.o $(PQ_LDFLAGS) -Lslacken_amd/lib -lslacken_amd -lz -ldl -lpthread -Wl,-rpath,'$$ORIGIN/../lib'
 

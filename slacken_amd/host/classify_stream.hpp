@@ -1,0 +1,223 @@
+// classify_stream.hpp -- one pass of the hot path over all input fragments: batches are parsed ahead on reader threads, classified by a
+// few workers, and handed on in input order (inputs: S/kmers/input/FileInputs.scala:64-85,156-221, InputReader.scala:105-131).
+#pragma once
+#include <atomic>
+#include <functional>
+
+#include "device_index.hpp"
+#include "pack.hpp"
+
+namespace slk_host {
+
+// Several input files (or pairs) are read side by side, each on its own threads (a gzip file on the cores' share of it, pargz.hpp), and
+// their batches are taken in turn: the order of the output is deterministic, though interleaved between files at batch
+// granularity (the reference's output order is whatever Spark's partitions give).
+class InputRotation {
+  const std::vector<std::string> &files_;
+  const bool paired_;
+  RepeatedTitles *rep_;
+  const size_t unit_, nsrc_;
+  size_t next_src_ = 0, turn_ = 0;
+  std::vector<std::unique_ptr<BatchPrefetcher>> active_;
+  std::unique_ptr<BatchPrefetcher> open_next() {
+    if (next_src_ >= nsrc_) return nullptr;
+    std::vector<std::string> fs(files_.begin() + next_src_ * unit_, files_.begin() + (next_src_ + 1) * unit_);
+    next_src_++;
+    return std::make_unique<BatchPrefetcher>(fs, paired_, rep_);
+  }
+ public:
+  InputRotation(const std::vector<std::string> &files, bool paired, RepeatedTitles *rep)
+      : files_(files), paired_(paired), rep_(rep), unit_(paired ? 2 : 1), nsrc_(files.size() / unit_) {
+    const char *cenv = getenv("SLK_INPUT_STREAMS");
+    const size_t conc = std::max<size_t>(1, std::min<size_t>(nsrc_, cenv ? (size_t)atol(cenv) : 8));
+    gz_concurrent_files() = (int)(conc * unit_);
+    while (active_.size() < conc) { auto r = open_next(); if (!r) break; active_.push_back(std::move(r)); }
+  }
+  FragmentBatchPtr next() {
+    while (!active_.empty()) {
+      if (turn_ >= active_.size()) turn_ = 0;
+      auto b = active_[turn_]->next();
+      if (b) { turn_++; return b; }
+      auto r = open_next();  // this file is exhausted: the next unopened one takes its place in the rotation
+      if (r) active_[turn_] = std::move(r);
+      else active_.erase(active_.begin() + turn_);
+    }
+    return nullptr;
+  }
+};
+
+// Batches carry the ticket they were taken with and are handed on in ticket order, whichever worker is done first.  The first
+// failure is kept and releases everybody who waits for a turn.
+class OrderedHandOver {
+  std::mutex mu_;
+  std::condition_variable cv_;
+  size_t next_out_ = 0;
+  std::exception_ptr failure_;
+  std::atomic<bool> failed_{false};
+ public:
+  size_t next_ticket = 0;   // under the lock of the input: a ticket is taken together with its batch
+  bool failed() const { return failed_; }
+  template <class Hand> void deliver(size_t ticket, Hand hand) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return next_out_ == ticket || failure_; });
+    if (!failure_) hand();
+    next_out_ = ticket + 1;
+    cv_.notify_all();
+  }
+  void fail(std::exception_ptr e) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!failure_) failure_ = e;
+    failed_ = true;
+    next_out_ = (size_t)-1;  // (nobody waits for a ticket any more)
+    cv_.notify_all();
+  }
+  void rethrow_failure() { if (failure_) std::rethrow_exception(failure_); }
+};
+
+// The batches are classified by a few worker threads, each with a stream of its own (its scratch, its staging buffers, its
+// HIP stream): one worker's copies overlap another's kernels.  Batches are taken and handed to f in input order.
+// --shard-table: a worker takes up to one batch per device table, classifies them as ONE round of its shard set, and hands them
+// on in input order; a second worker's round (its own set) overlaps the first one's copies and host work.
+template <class F> struct ClassifyPass {
+  DeviceIndex &dev;
+  const int min_hits;
+  const std::vector<double> &thresholds;
+  const bool want_spans, want_hits;
+  const std::function<void(const FragmentBatch &)> &pre;
+  F &f;
+  InputRotation input;
+  std::mutex mu_in, mu_stat;
+  OrderedHandOver order;
+  std::atomic<size_t> total{0}, n_batches{0};
+  double t_input = 0, t_device = 0, t_hand_over = 0;   // where the wall clock of the workers goes, by stage (SLK_HOST_TIMING)
+  // SLK_CLI_PACKED=1: reports-only calls send the reads packed (3 bits per base).  Off by default: this host is bound by parsing, not
+  // by the link -- 10 M reads from a FASTQ file, reports only: 0.83 s as text, 0.87 s packed (the packing is the workers' time;
+  // profiles/r04_cli_packed_ab.txt) -- the packed entry pays where the caller's reads are packed already or the link is the limit.
+  const bool packed_calls = getenv("SLK_CLI_PACKED") && getenv("SLK_CLI_PACKED")[0] == '1';
+
+  struct Lane { slk_index *ix = nullptr; slk_stream *st = nullptr; slk_shardset *set = nullptr; };   // what a worker drives: a stream or a shard set
+  struct Scratch { std::vector<int32_t> nd, tk; std::vector<uint32_t> pk_codes, pk_mcodes; std::vector<uint16_t> pk_valid, pk_mvalid; };   // a worker's own
+
+  // a batch's fragments into the record both modes fill; returns what the call is given for it
+  slk_shard_batch prepare(FragmentBatchPtr frags, ClassifiedBatch &b, Scratch &s) {
+    n_batches++;
+    b.frags = std::move(frags);
+    b.C = (int)thresholds.size();
+    const FragmentBatch &fb = *b.frags;
+    const size_t n = fb.size();
+    total += n;
+    if (pre) pre(fb);   // (on the worker's own time, not under the output's lock)
+    b.taxon.resize((size_t)b.C * n); b.classified.resize((size_t)b.C * n); s.nd.resize(n); s.tk.resize(n);
+    b.hit_offs.resize(n + 1);
+    const size_t cap = fb.bases.size() + fb.mate_bases.size() + n + 1;
+    if (want_hits) b.reserve_hits(cap);
+    return slk_shard_batch{fb.bases.data(), fb.offs.data(), fb.paired ? fb.mate_bases.data() : nullptr, fb.paired ? fb.mate_offs.data() : nullptr,
+                           n, b.taxon.data(), b.classified.data(), s.nd.data(), s.tk.data(), b.hit_offs.data(), want_hits ? b.hits.get() : nullptr, cap};
+  }
+
+  void classify_replicated(const Lane &lane, const slk_shard_batch &c, ClassifiedBatch &b, Scratch &s) {
+    const FragmentBatch &fb = *b.frags;
+    if (!want_hits && packed_calls) {
+      // reports only: nothing but the reads crosses the link, so they cross it in the engine's 3-bit form -- packed here, on the
+      // worker's own time (pack.hpp: AVX2 + BMI2), 6 bytes per 16 bases instead of 16
+      s.pk_codes.resize((fb.bases.size() + 15) / 16 + 1); s.pk_valid.resize(s.pk_codes.size());
+      slk::pack_bases(fb.bases.data(), fb.bases.size(), s.pk_codes.data(), s.pk_valid.data());
+      if (fb.paired) {
+        s.pk_mcodes.resize((fb.mate_bases.size() + 15) / 16 + 1); s.pk_mvalid.resize(s.pk_mcodes.size());
+        slk::pack_bases(fb.mate_bases.data(), fb.mate_bases.size(), s.pk_mcodes.data(), s.pk_mvalid.data());
+      }
+      SLK_CALL(slk_classify_batch_packed(lane.ix, lane.st, s.pk_codes.data(), s.pk_valid.data(), c.offsets, fb.paired ? s.pk_mcodes.data() : nullptr,
+                                         fb.paired ? s.pk_mvalid.data() : nullptr, c.mate_offsets, c.R, min_hits, thresholds.data(), b.C, c.out_taxon,
+                                         c.out_classified, c.out_num_distinct, c.out_total_kmers, c.out_hit_offsets, nullptr, c.hits_capacity));
+    } else {
+      SLK_CALL(slk_classify_batch(lane.ix, lane.st, c.bases, c.offsets, c.mate_bases, c.mate_offsets, c.R, min_hits, thresholds.data(), b.C,
+                                  c.out_taxon, c.out_classified, c.out_num_distinct, c.out_total_kmers, c.out_hit_offsets, c.out_hits, c.hits_capacity));
+    }
+    if (want_spans) {
+      b.span_offs.resize(c.R + 1);
+      b.spans.resize(c.hits_capacity);
+      SLK_CALL(slk_spans_batch(lane.ix, lane.st, c.bases, c.offsets, c.mate_bases, c.mate_offsets, c.R, b.span_offs.data(), b.spans.data(), c.hits_capacity));
+    }
+  }
+
+  size_t take(size_t G, std::vector<FragmentBatchPtr> &in) {   // up to G batches, in input order; returns the ticket of the first
+    std::lock_guard<std::mutex> lk(mu_in);
+    const size_t ticket0 = order.next_ticket;
+    for (FragmentBatchPtr fb; in.size() < G && (fb = input.next()); order.next_ticket++) in.push_back(std::move(fb));
+    return ticket0;
+  }
+
+  void work(const Lane &lane) {
+    const size_t G = lane.set ? dev.ixs.size() : 1;   // the group a worker takes at a time: a batch, or a round of one per device table
+    std::vector<Scratch> scratch(G);
+    std::vector<FragmentBatchPtr> in;
+    std::vector<std::shared_ptr<ClassifiedBatch>> out;
+    std::vector<slk_shard_batch> round;
+    double w_input = 0, w_device = 0, w_hand_over = 0;
+    try {
+      while (!order.failed()) {
+        const double t0 = wall_seconds();
+        in.clear();
+        const size_t ticket0 = take(G, in);
+        if (in.empty()) break;
+        const double t1 = wall_seconds();
+        out.clear();
+        round.assign(G, slk_shard_batch{});
+        for (size_t g = 0; g < in.size(); g++) {
+          out.push_back(new_classified_batch());
+          round[g] = prepare(std::move(in[g]), *out[g], scratch[g]);
+        }
+        if (lane.set) SLK_CALL(slk_shardset_classify(lane.set, round.data(), min_hits, thresholds.data(), (int)thresholds.size()));
+        else classify_replicated(lane, round[0], *out[0], scratch[0]);
+        const double t2 = wall_seconds();
+        for (size_t g = 0; g < out.size(); g++)
+          order.deliver(ticket0 + g, [&] { f(std::shared_ptr<const ClassifiedBatch>(std::move(out[g]))); });
+        w_input += t1 - t0; w_device += t2 - t1; w_hand_over += wall_seconds() - t2;
+      }
+    } catch (...) {
+      order.fail(std::current_exception());
+    }
+    std::lock_guard<std::mutex> lk(mu_stat);
+    t_input += w_input; t_device += w_device; t_hand_over += w_hand_over;
+  }
+};
+
+// merged_hits: the hit lists come merged as TaxonCounts.fromHits merges them (slk_stream_set_merged_hits) -- for a consumer that only
+// prints them (OutputSink), a sixth of the bytes on the way back; never with spans (their lists go by position) nor on a shard set.
+// Batches are handed to f with shared ownership: output formatting keeps them alive on its own threads.
+template <class F>
+void classify_stream(DeviceIndex &dev, const std::vector<std::string> &files, bool paired, int min_hits, const std::vector<double> &thresholds,
+                     bool want_spans, bool want_hits, F f, RepeatedTitles *rep = nullptr,
+                     const std::function<void(const FragmentBatch &)> &pre = nullptr, bool merged_hits = false) {
+  if (want_spans && dev.sharded) die("internal: classify_stream serves no spans from a sharded table");
+  using Pass = ClassifyPass<F>;
+  Pass pass{dev, min_hits, thresholds, want_spans, want_hits, pre, f, InputRotation(files, paired, rep)};
+  const char *wenv = getenv("SLK_CLASSIFY_THREADS");
+  // (SLK_CLASSIFY_THREADS: threads per device; with several devices worker i drives device i mod N, each on its own table)
+  const size_t per_dev = std::max<size_t>(1, std::min<size_t>(8, wenv ? (size_t)atol(wenv) : 2));
+  const size_t n_workers = per_dev * dev.ixs.size();
+  static const bool no_merge = getenv("SLK_CLI_MERGED_HITS") && getenv("SLK_CLI_MERGED_HITS")[0] == '0';   // (A/B switch)
+  const bool merge = merged_hits && want_hits && !want_spans && !no_merge;
+  std::vector<typename Pass::Lane> lanes(dev.sharded ? dev.sets.size() : n_workers);   // (sharded: a worker per shard set)
+  for (size_t i = 0; i < lanes.size(); i++) {
+    if (dev.sharded) { lanes[i].set = dev.sets[i]; continue; }
+    lanes[i].ix = dev.ixs[i % dev.ixs.size()];
+    lanes[i].st = dev.st;   // the first worker runs on the calling thread with the device's own stream
+    if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
+    SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merge ? 1 : 0));
+  }
+  std::vector<std::thread> workers;
+  for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&pass, &lanes, i] { pass.work(lanes[i]); });
+  pass.work(lanes[0]);
+  for (auto &t : workers) t.join();
+  for (size_t i = 1; i < lanes.size(); i++) if (lanes[i].st) slk_stream_destroy(lanes[i].st);
+  if (!dev.sharded) (void)slk_stream_set_merged_hits(dev.st, 0);   // (the device's own stream serves other callers: un-merged lists again)
+  pass.order.rethrow_failure();
+  if (getenv("SLK_HOST_TIMING"))
+    std::cerr << "host timing: " << pass.n_batches << " batches on " << n_workers << " classify thread(s) over " << dev.ixs.size() << " device table(s); summed over them: waiting for input "
+              << pass.t_input << " s, upload+kernels+download " << pass.t_device << " s, waiting for their turn and handing over to the output threads "
+              << pass.t_hand_over << " s" << std::endl;
+  std::cerr << pass.total << " fragments" << std::endl;
+}
+
+}  // namespace slk_host

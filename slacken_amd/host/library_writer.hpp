@@ -4,7 +4,7 @@
 //   LOC.properties   k, m, buckets, version, splitter=randomXOR, XORmask (signed decimal), canonical, minimizerSpaces
 //   LOC_taxonomy/    a byte copy of the source library's directory
 //   LOC/part-00000-<tag>_<bbbbb>.c000.snappy.parquet   one file per bucket, columns id1: int64, taxon: int32 (parquet_sink.cpp)
-//   or LOC.slkrec    the flat form of slacken_cli.cpp, when the build has no Arrow or the caller asks for it
+//   or LOC.slkrec    the flat form of library_io.hpp, when the build has no Arrow or the caller asks for it
 // Host only, no GPU.  Records arrive in chunks (add), in any order.  Everything is written under temporary names and renamed by
 // finish(), the properties last: a writer that dies or is destroyed before finish() returns leaves no LOC.properties, so nothing that
 // loads.  Used by `respace` and `copy-records`; `build` will need the same.

@@ -604,3 +604,71 @@ def test_cli_repeated_titles_randomised(tmp_path, seed):
     classify("-i", loc, "-o", out2, "-c", "0.0", "0.3", "--nodetailed", *(["-p"] if paired else []), f1, f2)
     for suffix in ("0.0", "0.3"):
         assert open(f"{out2}_c{suffix}/all_kreport.txt").read() == open(f"{out}_c{suffix}/all_kreport.txt").read()
+
+
+def _all_outputs(out, suffixes=("0.00", "0.15")):
+    """Every per-read file (its text) and every report of a run, by path below the output directories."""
+    got = {}
+    for suffix in suffixes:
+        d = f"{out}_c{suffix}"
+        for fn in sorted(glob.glob(os.path.join(d, "**", "*"), recursive=True)):
+            if os.path.isfile(fn):
+                got[(suffix, os.path.relpath(fn, d))] = gzip.open(fn, "rb").read() if fn.endswith(".gz") else open(fn, "rb").read()
+    return got
+
+
+@pytest.mark.gpu
+def test_cli_one_worker_serves_rounds_and_single_batches(tmp_path):
+    """The classify worker takes a group of batches at a time: one batch on replicated tables, a round of up to one per table under
+    --shard-table.  Ten batches over three tables leave the last round with one batch; with one shard set and with two, and
+    replicated with five threads, every per-read file and report is byte for byte that of a plain single-device run, and every run
+    counts the same fragments."""
+    g, loc, tax, reads = make_library(tmp_path)
+    chunk, n_batches = 1 << 16, 10
+    fq = tmp_path / "reads.fq"
+    size = n = 0
+    with open(fq, "w") as f:
+        while size <= (n_batches - 1) * chunk + 2048:     # a plain file is cut into batches of `chunk` bytes: the tenth has begun
+            t, s = reads[n % len(reads)]
+            size += f.write(f"@{t}.{n}\n{s}\n+\n{'I' * len(s)}\n")
+            n += 1
+    assert -(-size // chunk) == n_batches and n_batches % 3 == 1
+    runs = {"single": ([], {}),
+            "sharded-one-set": (["--devices", "0,0,0", "--shard-table"], {"SLK_SHARD_SETS": "1"}),
+            "sharded-two-sets": (["--devices", "0,0,0", "--shard-table"], {"SLK_SHARD_SETS": "2"}),
+            "five-threads": ([], {"SLK_CLASSIFY_THREADS": "5"})}
+    outputs = {}
+    for name, (extra, env) in runs.items():
+        out = tmp_path / name
+        r = subprocess.run([CLI, "classify", "-i", loc, "-o", str(out), "-c", "0.0", "0.15", *extra, str(fq)], capture_output=True, text=True,
+                           env=dict(os.environ, SLK_IO_CHUNK=str(chunk), SLK_HOST_TIMING="1", **env), timeout=120)
+        assert r.returncode == 0, r.stderr
+        assert f"host timing: {n_batches} batches on " in r.stderr, r.stderr
+        assert r.stderr.rstrip("\n").split("\n")[-2] == f"{n} fragments" and "Finish task: Classify reads" in r.stderr.split("\n")[-2], r.stderr
+        outputs[name] = _all_outputs(out)
+    want = outputs["single"]
+    assert {k[1] for k in want} == {"all_kreport.txt", os.path.join("sample=all", "part-00000.txt.gz")}
+    assert want[("0.00", os.path.join("sample=all", "part-00000.txt.gz"))].count(b"\n") > n // 2
+    for name in runs:
+        assert outputs[name] == want, name
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [[], ["--devices", "0,0", "--shard-table"]], ids=["replicated", "sharded"])
+def test_cli_input_failure_while_workers_are_busy(tmp_path, extra):
+    """The second input file is a .gz cut off in the middle, the first is long enough for batches to be in flight on every worker:
+    the run ends with the reader's message and a non-zero status instead of hanging or writing a short result.  (A host parse
+    error, not a device fault.)"""
+    g, loc, tax, reads = make_library(tmp_path)
+    good, cut = tmp_path / "good.fq", tmp_path / "cut.fq.gz"
+    with open(good, "w") as f:
+        for rep in range(40):
+            for t, s in reads:
+                f.write(f"@{t}.{rep}\n{s}\n+\n{'I' * len(s)}\n")
+    whole = gzip.compress("".join(f"@{t}.x{rep}\n{s}\n+\n{'I' * len(s)}\n" for rep in range(8) for t, s in reads).encode())
+    with open(cut, "wb") as f:
+        f.write(whole[:len(whole) // 2])
+    r = subprocess.run([CLI, "classify", "-i", loc, "-o", str(tmp_path / "out"), *extra, str(good), str(cut)], capture_output=True, text=True,
+                       env=dict(os.environ, SLK_IO_CHUNK=str(1 << 16)), timeout=120)
+    assert r.returncode > 0, (r.returncode, r.stderr)      # (an orderly exit, not a signal)
+    assert "read error (corrupt compressed input?)" in r.stderr, r.stderr
