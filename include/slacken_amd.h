@@ -186,6 +186,29 @@ int32_t slk_index_finalize(slk_index *ix);
  * keys: id_longs words per record, row-major.  The order is unspecified (a set).  *n_records receives the number of records; if it exceeds capacity only the first
  * `capacity` were written and SLK_E_CAPACITY is returned.  keys/taxa may be NULL with capacity 0 to query the count. */
 int32_t slk_index_export(const slk_index *ix, int64_t *keys, int32_t *taxa, uint64_t capacity, uint64_t *n_records);
+/* The records of table buckets [bucket0, bucket1), optionally grouped by Spark's bucket: the device half of
+ * KeyValueIndex.writeRecords (KeyValueIndex.scala:125-139), which persists the records CLUSTERED BY (id1) INTO n BUCKETS.  A table
+ * leaves the device piece by piece through this call (slk_index_export stages the whole record set on the device and again on
+ * the host): slk_index_info.buckets and bucket_cells bound the range and the count -- (bucket1 - bucket0) * bucket_cells records
+ * is an upper bound, and a caller who sizes by it never sees SLK_E_CAPACITY.  Records and taxa as slk_index_export gives them (the
+ * caller's ids, also on an index renumbered by slk_index_finalize); the pieces of a tiling of [0, buckets) hold every record once.
+ *   n_groups == 0   any order; group_offsets is ignored (may be NULL).
+ *   n_groups >= 1   the records are ordered by g = pmod(Murmur3_x86_32.hashLong(key, seed 42), n_groups), the bucket Spark computes
+ *                   for a long column; group_offsets[0 .. n_groups] receives where each group starts, group_offsets[n_groups] ==
+ *                   *n_records.  The order inside a group is unspecified.  A grouped call covers at most 2^32 cells
+ *                   (SLK_E_INVALID beyond: pieces are the intended use).
+ *   capacity        *n_records is always the full count of the range.  If it exceeds a capacity > 0, SLK_E_CAPACITY is returned and
+ *                   only the count means anything.  keys / taxa may be NULL with capacity 0 to query the count (group_offsets is
+ *                   not written then).  An empty range is SLK_OK with 0 records.
+ *   errors          SLK_E_INVALID: bucket0 > bucket1, bucket1 > buckets, n_groups < 0, a grouped call over more than 2^32 cells;
+ *                   SLK_E_UNSUPPORTED: several id columns; SLK_E_STATE: a spent index.
+ * Works before and after slk_index_finalize, after the table has grown, and on a dynamic library (slk_index_add_sequences); a shard
+ * of a table-sharded library (slk_index_set_shard) exports its own share.  The index is not changed.  Two passes over the range's
+ * cells and a scan on the device (export.hip); device staging is what the range needs -- 12 bytes per possible record and the group
+ * counters --, never the table's record count.  Up to SLK_EXPORT_LDS_GROUPS groups (environment; default 4096) are counted in the
+ * blocks' LDS.  Synchronous, on the build stream; not to be called while another thread adds records to the same index. */
+int32_t slk_index_export_range(const slk_index *ix, uint64_t bucket0, uint64_t bucket1, int32_t n_groups, int64_t *keys, int32_t *taxa,
+                               uint64_t capacity, uint64_t *group_offsets, uint64_t *n_records);
 /* Records per taxon of the resident table: replaces records.groupBy("taxon").agg(count("*")) -- KeyValueIndex.scala:241
  * (showIndexStats) and :278 (report); the depth histograms (:326-336) are sums of the same pairs.  One streaming pass over the
  * table on the device (taxstats.hip); nothing but the pairs crosses to the host.  (taxa[i], counts[i]) for i < *n_taxa, ascending

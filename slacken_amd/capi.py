@@ -73,7 +73,7 @@ HIT_DTYPE = np.dtype([("taxon", "<i4"), ("count", "<i4")])
 # every symbol include/slacken_amd.h declares
 EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc", "slk_host_register", "slk_host_free", "slk_index_create", "slk_index_append",
            "slk_index_append_device", "slk_index_set_shard", "slk_index_set_taxonomy", "slk_index_finalize", "slk_index_get_info",
-           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_taxon_counts", "slk_index_respace", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
+           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_export_range", "slk_index_taxon_counts", "slk_index_respace", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
            "slk_stream_hip_stream", "slk_stream_destroy", "slk_spans_batch", "slk_spans_batch_wide", "slk_classify_batch",
            "slk_classify_batch_packed", "slk_pack_bases",
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
@@ -127,6 +127,7 @@ def lib():
     L.slk_index_add_sequences.argtypes = [vp, u8p, u64p, i32p, C.c_uint64]
     L.slk_index_add_sequences_device.argtypes = [vp, u8p, u64p, i32p, C.c_uint64]
     L.slk_index_export.argtypes = [vp, i64p, i32p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.slk_index_export_range.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int32, i64p, i32p, C.c_uint64, u64p, C.POINTER(C.c_uint64)]
     L.slk_index_taxon_counts.argtypes = [vp, i32p, u64p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.slk_index_respace.argtypes = [vp, C.c_int32, C.POINTER(_TableConfig), C.POINTER(vp)]
     L.slk_index_destroy.argtypes = [vp]
@@ -292,6 +293,25 @@ class Index:
             return rows[order], taxa[order]
         order = np.argsort(keys, kind="stable")
         return keys[order], taxa[order]
+
+    def export_range(self, bucket0, bucket1, n_groups=0):
+        """The records of table buckets [bucket0, bucket1) (slk_index_export_range; info().buckets bounds the range), as they
+        leave the device: (keys, taxa) in any order, or with n_groups >= 1 (keys, taxa, group_offsets) ordered by Spark's bucket
+        pmod(Murmur3 hashLong(key, 42), n_groups), group g at [group_offsets[g], group_offsets[g + 1])."""
+        cap = max(0, int(bucket1) - int(bucket0)) * self.info().bucket_cells   # an upper bound: never SLK_E_CAPACITY
+        keys, taxa = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.int32)
+        offs = np.zeros(int(n_groups) + 1, np.uint64) if n_groups > 0 else None
+        n = C.c_uint64(0)
+        _check(lib().slk_index_export_range(self.h, int(bucket0), int(bucket1), int(n_groups), _ptr(keys), _ptr(taxa), max(cap, 1),
+                                            _ptr(offs), C.byref(n)))
+        keys, taxa = keys[:n.value].copy(), taxa[:n.value].copy()
+        return (keys, taxa, offs) if n_groups > 0 else (keys, taxa)
+
+    def export_pieces(self, piece_buckets, n_groups=0):
+        """export_range over the whole table, piece_buckets buckets at a time: a generator of its results."""
+        nb, step = int(self.info().buckets), max(1, int(piece_buckets))
+        for b0 in range(0, nb, step):
+            yield self.export_range(b0, min(nb, b0 + step), n_groups)
 
     def taxon_counts(self):
         """(taxa int32, counts uint64) of the resident table: records per taxon, ascending taxon, the caller's ids

@@ -6,8 +6,8 @@
 //   LOC/part-00000-<tag>_<bbbbb>.c000.snappy.parquet   one file per bucket, columns id1: int64, taxon: int32 (parquet_sink.cpp)
 //   or LOC.slkrec    the flat form of library_io.hpp, when the build has no Arrow or the caller asks for it
 // Host only, no GPU.  Records arrive in chunks (add), in any order.  Everything is written under temporary names and renamed by
-// finish(), the properties last: a writer that dies or is destroyed before finish() returns leaves no LOC.properties, so nothing that
-// loads.  Used by `respace` and `copy-records`; `build` will need the same.
+// finish(), the properties last, and a library that is at LOC already is kept until then: a writer that dies or is destroyed before finish() returns leaves no LOC.properties, so nothing that
+// loads.  Used by `build`, `respace` and `copy-records`.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "cli_common.hpp"
 #include "parquet_source.hpp"
 
 namespace slk_host {
@@ -47,16 +48,19 @@ struct LibraryProperties {
   bool canonical = true;
 };
 
-// The Parquet half (parquet_sink.cpp, built with the flags of parquet_source.cpp): `buckets` files under dir, rows dealt out by
-// spark_bucket.  Without Arrow the constructor throws.
+// The Parquet half (parquet_sink.cpp, built with the flags of parquet_source.cpp): `buckets` files under dir, a row in the file of
+// its spark_bucket.  Rows arrive grouped by bucket (add_grouped: group_offsets[0 .. buckets] says where each bucket's run starts, as
+// slk_index_export_range leaves them; nothing is hashed) or in any order (add: dealt into groups on the host, then the same path).
+// The buckets' writers are spread over `threads` host threads, a bucket always on the same one.  Without Arrow the constructor throws.
 class ParquetBucketSink {
   struct Impl;
   std::unique_ptr<Impl> impl_;
 
  public:
-  ParquetBucketSink(const std::string &dir, int buckets, const std::string &tag);
+  ParquetBucketSink(const std::string &dir, int buckets, const std::string &tag, size_t threads);
   ~ParquetBucketSink();
   void add(const int64_t *keys, const int32_t *taxa, uint64_t n);
+  void add_grouped(const int64_t *keys, const int32_t *taxa, const uint64_t *group_offsets);
   void close();   // footers written, files complete
 };
 
@@ -76,13 +80,12 @@ class LibraryWriter {
     if (format == PARQUET && !parquet_available()) throw std::runtime_error("--format parquet: this build has no Parquet support");
     if (props_.buckets < 1) throw std::runtime_error("buckets=" + std::to_string(props_.buckets) + " in the properties");
     if (fs::path(loc_).has_parent_path()) fs::create_directories(fs::path(loc_).parent_path());
-    fs::remove(loc_ + ".properties");   // (whatever was here stops being a library now, not when the new one is half written)
     tmp_ = loc_ + ".writing";
     fs::remove_all(tmp_);
     fs::remove_all(tmp_ + ".taxa");
     if (parquet_) {
       fs::create_directories(tmp_);
-      sink_.reset(new ParquetBucketSink(tmp_, props_.buckets, "slacken-amd"));
+      sink_.reset(new ParquetBucketSink(tmp_, props_.buckets, "slacken-amd", host_threads()));
     } else {
       keys_ = fopen(tmp_.c_str(), "wb");
       taxa_ = fopen((tmp_ + ".taxa").c_str(), "w+b");
@@ -110,13 +113,27 @@ class LibraryWriter {
     put(taxa_, taxa, n * 4);
   }
 
+  // records grouped by Spark's bucket (slk_index_export_range with n_groups = the properties' buckets): group_offsets[0 .. buckets],
+  // group_offsets[buckets] records in all.  The flat form ignores the grouping.
+  void add_grouped(const int64_t *keys, const int32_t *taxa, const uint64_t *group_offsets) {
+    const uint64_t n = group_offsets[props_.buckets];
+    if (!parquet_) { add(keys, taxa, n); return; }
+    for (uint64_t i = 0; i < n; i++) if (taxa[i] > max_taxon_) max_taxon_ = taxa[i];
+    n_ += n;
+    sink_->add_grouped(keys, taxa, group_offsets);
+  }
+  bool parquet() const { return parquet_; }
+
   uint64_t records() const { return n_; }
 
   void finish() {
     namespace fs = std::filesystem;
+    // Whatever library is at LOC is left alone until every record is on disk under its temporary name; it stops being one then
+    // (its properties go first), its records are replaced, and the new properties come last.
     if (parquet_) {
       sink_->close();
       sink_.reset();
+      fs::remove(loc_ + ".properties");
       fs::remove_all(loc_);
       fs::remove(loc_ + ".slkrec");   // (the readers prefer it: a stale one would hide the new records)
       fs::rename(tmp_, loc_);
@@ -135,6 +152,7 @@ class LibraryWriter {
       taxa_ = nullptr;
       if (!ok) throw std::runtime_error("cannot write " + tmp_);
       fs::remove(tmp_ + ".taxa");
+      fs::remove(loc_ + ".properties");
       fs::remove_all(loc_);
       fs::rename(tmp_, loc_ + ".slkrec");
     }

@@ -4,7 +4,9 @@
 // held on the devices by device_index.hpp and classified against by classify_stream.hpp; repeated_titles.hpp settles the titles that
 // occur more than once; taxonomy.hpp, output.hpp, migration.hpp and stats.hpp make the outputs.  Each cites what it mirrors.
 // Host-only subcommands (`report`, `parse`, `props`) exist so that this layer can be tested without a GPU.
+#include <future>
 #include <set>
+#include <sstream>
 
 #include "classify_stream.hpp"
 #include "migration.hpp"
@@ -320,24 +322,32 @@ static int cmd_classify(int argc, char **argv) {
 }
 
 // ---- classify2: two-step classification with a dynamic library (Dynamic.scala; Slacken.scala:199-260) ----
-// the sequences of DIR/library/**/*.fna (HDFSUtil.findFiles(location + "/library", ".fna")) whose header carries a label, in the
-// order of the sorted files: fn(sequence, taxon)
-template <class Fn>
-static void for_each_labelled_sequence(const std::string &library, const std::unordered_map<std::string, Taxon> &labels, Fn fn) {
+// the .fna files under DIR/library (HDFSUtil.findFiles(location + "/library", ".fna")), sorted
+static std::vector<std::string> library_fna_files(const std::string &library) {
   const fs::path dir = fs::path(library) / "library";
   if (!fs::exists(dir)) die("no such directory: " + dir.string());
   std::vector<std::string> fna;
   for (auto &e : fs::recursive_directory_iterator(dir))
     if (e.is_regular_file() && ends_with(e.path().string(), ".fna")) fna.push_back(e.path().string());
   std::sort(fna.begin(), fna.end());
-  for (auto &file : fna) {
+  return fna;
+}
+// every sequence of those files, in the order of the sorted files: fn(sequence id, sequence)
+template <class Fn>
+static void for_each_library_sequence(const std::string &library, Fn fn) {
+  for (auto &file : library_fna_files(library)) {
     AsyncRecordStream rs(file);  // (plain .fna files are parsed on several threads)
     std::string_view h, sq;
-    while (rs.next(h, sq)) {
-      auto it = labels.find(std::string(h));
-      if (it != labels.end()) fn(sq, it->second);
-    }
+    while (rs.next(h, sq)) fn(h, sq);
   }
+}
+// the sequences whose header carries a label: fn(sequence, taxon)
+template <class Fn>
+static void for_each_labelled_sequence(const std::string &library, const std::unordered_map<std::string, Taxon> &labels, Fn fn) {
+  for_each_library_sequence(library, [&](std::string_view h, std::string_view sq) {
+    auto it = labels.find(std::string(h));
+    if (it != labels.end()) fn(sq, it->second);
+  });
 }
 
 // "%.2f%%".format(d * 100) (Helpers.formatPerc, S/kmers/package.scala:60) with java.util.Formatter's rounding
@@ -852,6 +862,264 @@ static bool find_spaces_tag(const std::string &s, size_t *pos, size_t *len) {
   return false;
 }
 
+// A resident table onto disk, piece by piece: slk_index_export_range over SLK_EXPORT_PIECE_BUCKETS table buckets at a time (default
+// 2^23: 6.7e7 cells, a few tens of millions of records at the loads the table is sized for), grouped by Spark's bucket for the
+// Parquet form so that the writer appends runs (n_groups 0 for .slkrec, which has no buckets).  Two pinned host buffers: a piece is
+// written on a second thread while the next is exported.  Host memory is two pieces, whatever the table holds.
+struct ExportTimes { double export_s = 0, write_wait_s = 0; uint64_t pieces = 0; };
+static void export_to_writer(const slk_index *ix, LibraryWriter &w, int buckets, ExportTimes *times) {
+  slk_index_info info;
+  SLK_CALL(slk_index_get_info(ix, &info));
+  const long env_piece = getenv("SLK_EXPORT_PIECE_BUCKETS") ? atol(getenv("SLK_EXPORT_PIECE_BUCKETS")) : 0;
+  const uint64_t piece = std::min<uint64_t>(std::max<uint64_t>(info.buckets, 1), env_piece > 0 ? (uint64_t)env_piece : (uint64_t)1 << 23);
+  const uint64_t cap = piece * (uint64_t)info.bucket_cells;   // an upper bound on a piece's records: never SLK_E_CAPACITY
+  // (SLK_EXPORT_GROUPED=0: A/B switch of tools/bench_build.py -- pieces in any order, dealt into buckets by the writer on the host)
+  const bool on_device = !(getenv("SLK_EXPORT_GROUPED") && getenv("SLK_EXPORT_GROUPED")[0] == '0');
+  const int n_groups = w.parquet() && on_device ? buckets : 0;
+  struct Piece {
+    void *keys = nullptr, *taxa = nullptr;
+    std::vector<uint64_t> offsets;
+    uint64_t n = 0;
+    ~Piece() { if (keys) slk_host_free(keys); if (taxa) slk_host_free(taxa); }
+  } buf[2];
+  for (Piece &p : buf) {
+    SLK_CALL(slk_host_alloc(cap * 8, &p.keys));
+    SLK_CALL(slk_host_alloc(cap * 4, &p.taxa));
+    p.offsets.assign((size_t)n_groups + 1, 0);
+  }
+  std::future<void> writing;
+  int at = 0;
+  for (uint64_t b0 = 0; b0 < info.buckets; b0 += piece, at ^= 1) {
+    Piece &p = buf[at];   // (its last write was waited for before the other buffer's began)
+    const double t0 = wall_seconds();
+    SLK_CALL(slk_index_export_range(ix, b0, std::min<uint64_t>(info.buckets, b0 + piece), n_groups, (int64_t *)p.keys, (int32_t *)p.taxa, cap,
+                                    n_groups ? p.offsets.data() : nullptr, &p.n));
+    const double t1 = wall_seconds();
+    if (writing.valid()) writing.get();
+    const double t2 = wall_seconds();
+    if (times) { times->export_s += t1 - t0; times->write_wait_s += t2 - t1; times->pieces++; }
+    writing = std::async(std::launch::async, [&w, &p, n_groups] {
+      if (n_groups) w.add_grouped((const int64_t *)p.keys, (const int32_t *)p.taxa, p.offsets.data());
+      else w.add((const int64_t *)p.keys, (const int32_t *)p.taxa, p.n);
+    });
+  }
+  const double t2 = wall_seconds();
+  if (writing.valid()) writing.get();
+  if (times) times->write_wait_s += wall_seconds() - t2;
+}
+
+// ---- build (Slacken.scala:123-171): a library from the genomes of LIBRARY_DIR and the labels of LIBRARY_DIR/seqid2taxid.map ----
+static const char *BUILD_USAGE =
+    "usage: [--partitions N] build -i INDEX -t TAXONOMY_DIR -l LIBRARY_DIR [-k 35] [-m 31] [-s|--spaces 7] [--check] [--format parquet|slkrec] "
+    "[--expected-records N] [--devices D]";
+static int g_partitions = 200;          // --partitions, the reference's global option: `buckets` of a library that `build` writes
+constexpr int BUILD_MAX_WINDOW = 28;    // m-mers per window the library builder takes (slk_index_add_sequences)
+
+static bool is_nucleotide(char c) {     // what the scan takes for a base (BitRepresentation.charToTwobit: A C G T U, either case)
+  switch (c) { case 'A': case 'C': case 'G': case 'T': case 'U': case 'a': case 'c': case 'g': case 't': case 'u': return true; default: return false; }
+}
+
+// KeyValueIndex.checkInput (KeyValueIndex.scala:57-76), host only: a sequence has a super-mer, so a minimizer, exactly when it has
+// a window, a run of k valid bases; the counts of the records that share an id are summed, as the reference's groupBy does.
+static int check_build_input(const std::string &library, int k) {
+  std::map<std::string, bool> has_minimizer;
+  for_each_library_sequence(library, [&](std::string_view h, std::string_view sq) {
+    bool found = false;
+    size_t run = 0;
+    for (char c : sq) {
+      run = is_nucleotide(c) ? run + 1 : 0;
+      if (run >= (size_t)k) { found = true; break; }
+    }
+    bool &slot = has_minimizer[std::string(h)];
+    slot = slot || found;
+  });
+  std::vector<std::vector<std::string>> rows;
+  size_t none = 0;
+  for (auto &e : has_minimizer) {
+    if (e.second) continue;
+    none++;
+    // (Dataset.show(): the first 20 rows, cells cut to 20 characters)
+    if (rows.size() < 20) rows.push_back({e.first.size() > 20 ? e.first.substr(0, 17) + "..." : e.first, "0"});
+  }
+  if (none) {
+    std::cout << "Some input sequences had no minimizers (total " << none << "): \n" << show_table({"seqId", "sum"}, rows);
+    if (none > 20) std::cout << "only showing top 20 rows\n\n";
+  } else {
+    std::cout << "Input sequences checked, all had minimizers.\n";
+  }
+  std::cout.flush();
+  return 0;
+}
+
+// GenomeLibrary.inputStats (GenomeLibrary.scala:81-107) for the label file.  A label outside the taxonomy's arrays (the reference
+// would throw) counts as undefined.
+static std::string input_stats_text(const std::string &label_file, const std::vector<std::pair<std::string, Taxon>> &labels, const Taxonomy &tax) {
+  std::set<Taxon> labelled;
+  for (auto &lb : labels) labelled.insert(lb.second);
+  auto defined = [&](Taxon t) { return t >= 0 && t < tax.size() && tax.isDefined(t); };
+  std::vector<Taxon> invalid, valid;
+  size_t non_leaf = 0;
+  for (Taxon t : labelled) {
+    (defined(t) ? valid : invalid).push_back(t);
+    if (!stats_is_leaf(tax, t)) non_leaf++;
+  }
+  std::ostringstream o;
+  if (!invalid.empty()) {
+    o << invalid.size() << " unknown genomes in " << label_file << " were not indexed (missing from the taxonomy):\nList(";
+    for (size_t i = 0; i < invalid.size(); i++) o << (i ? ", " : "") << invalid[i];
+    o << ")\n";
+  }
+  if (non_leaf) o << non_leaf << " non-leaf genomes in " << label_file << "\n";
+  TaxonCounts as_counts;
+  for (Taxon t : valid) as_counts.emplace_back(t, 1);
+  o << valid.size() << " valid taxa in input sequences described by " << label_file << " (maximal implied tree size "
+    << stats_tree_size(tax, as_counts) << ")\n";
+  o << "Max leaf nodes in resulting database: " << (long)valid.size() - (long)non_leaf << "\n";
+  std::map<int, uint64_t> missing;
+  for (Taxon t : valid) for (int level : tax.missingStepsToRoot(t)) missing[level]++;
+  std::vector<std::vector<std::string>> rows;
+  for (auto &e : missing) rows.push_back({std::to_string(e.first), std::to_string(e.second), rank_titles(e.first + 1)});
+  o << show_table({"missingLevel", "count(missingLevel)", "label"}, rows);
+  return o.str();
+}
+
+static int cmd_build(int argc, char **argv) {
+  const char *why_one = "the library's table must fit one GPU";
+  std::string index, taxonomy, library, ordering = "xor";
+  int k = 35, m = 31, spaces = 7;
+  bool check = false;
+  uint64_t expected = 0;
+  std::vector<int> devices{0};
+  LibraryWriter::Format format = LibraryWriter::AUTO;
+  for (Args a(argc, argv); a.take();) {
+    if (a == "-i" || a == "--index") index = a.next();
+    else if (a == "-t" || a == "--taxonomy") taxonomy = a.next();
+    else if (a == "-l" || a == "--library") library = a.next();
+    else if (a == "-k") k = std::stoi(a.next());
+    else if (a == "-m" || a == "--minimizer-width") m = std::stoi(a.next());
+    else if (a == "-s" || a == "--spaces") spaces = std::stoi(a.next());
+    else if (a == "--ordering") ordering = a.next();
+    else if (a == "--check") check = true;
+    else if (a == "--format") format = LibraryWriter::parse_format(a.next());
+    else if (a == "--expected-records") expected = std::stoull(a.next());
+    else if (a == "--devices") devices = parse_single_device(a.next(), "build", why_one);
+    else if (a == "--shard-table") refuse_shard_table("build", why_one, BUILD_USAGE);
+    else die("unknown option " + a.opt + "\n" + BUILD_USAGE);
+  }
+  if (index.empty() || taxonomy.empty() || library.empty()) die(BUILD_USAGE);
+  // what this engine does not build is refused on the command line alone, before any file is read
+  if (ordering != "xor" && ordering != "random")
+    die("--ordering " + ordering + " is not supported by this engine (randomXOR only: xor or random)");
+  if (m > k) die("-m must be <= -k");
+  if (k < 1 || m < 1) die("-k and -m must be positive");
+  if (m > 32) die("build supports minimizers of up to 32 nt (-m " + std::to_string(m) + ")");
+  if (k - m + 1 > BUILD_MAX_WINDOW)
+    die("build supports windows of up to " + std::to_string(BUILD_MAX_WINDOW) + " m-mers (k - m + 1 = " + std::to_string(k - m + 1) + ")");
+  if (spaces < 0 || spaces > m / 2) die(std::to_string(spaces) + " spaces in minimizers of " + std::to_string(m) + " nt: at most " + std::to_string(m / 2));
+  if (g_partitions < 1) die("--partitions must be positive");
+  if (format == LibraryWriter::PARQUET && !parquet_available()) die("--format parquet: this build has no Parquet support");
+
+  IndexParams ip{k, m, spaces, SLK_DEFAULT_TOGGLE_MASK, true};
+  // (the reference prints the toString of a Scala object here; this line names the parameters in the engine's words)
+  std::cout << "Splitter randomXOR k=" << ip.k << " m=" << ip.m << " XORmask=" << (int64_t)ip.xorMask << " canonical=true minimizerSpaces=" << ip.spaces << std::endl;
+  if (check) return check_build_input(library, k);
+
+  const Taxonomy tax = Taxonomy::load(taxonomy);
+  const std::string label_file = library + "/seqid2taxid.map";
+  const auto all_labels = read_label_map(library);
+  std::unordered_map<std::string, Taxon> labels;   // KeyValueIndex.makeRecords :118-120: only defined taxa are indexed
+  for (auto &lb : all_labels)
+    if (lb.second >= 0 && lb.second < tax.size() && tax.isDefined(lb.second)) labels[lb.first] = lb.second;
+
+  // the table: --expected-records, or classify2's estimate from the size of the genome files (distinct minimizers <= super-mers:
+  // about 2 / (w + 1) per window on random sequence); it grows by itself when that proves too low
+  const int w = k - m + 1;
+  if (expected == 0) {
+    uint64_t bytes = 0;
+    for (auto &f : library_fna_files(library)) bytes += (uint64_t)fs::file_size(f);
+    expected = (uint64_t)((double)bytes * std::min(1.0, 2.5 / (w + 1))) + 1024;
+  }
+  DeviceIndex dev;
+  dev.devices = devices;
+  dev.create(ip, tax, expected, std::max<int32_t>(tax.size() - 1, 1));
+
+  // the walk: batches of whole sequences of about SLK_BUILD_BATCH_BASES bases (a longer sequence is a batch of its own); the next
+  // batch is read and parsed while slk_index_add_sequences runs on the last.  Host memory: two batches.
+  const long env_batch = getenv("SLK_BUILD_BATCH_BASES") ? atol(getenv("SLK_BUILD_BATCH_BASES")) : 0;
+  const uint64_t batch_bases = env_batch > 0 ? (uint64_t)env_batch : (uint64_t)1 << 30;
+  struct Batch {
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> offsets{0};
+    std::vector<int32_t> taxa;
+    void clear() { bases.clear(); offsets.assign(1, 0); taxa.clear(); }
+  } batch[2];
+  int fill = 0;
+  uint64_t n_seq = 0, n_bases = 0, n_batches = 0;
+  double t_add = 0, t_wait = 0;
+  std::future<std::pair<int32_t, std::string>> adding;
+  auto wait_for_add = [&] {
+    if (!adding.valid()) return;
+    const double t0 = wall_seconds();
+    const auto r = adding.get();
+    t_wait += wall_seconds() - t0;
+    if (r.first != SLK_OK) die("slk_index_add_sequences: " + r.second);
+  };
+  auto submit = [&] {
+    Batch &b = batch[fill];
+    if (b.taxa.empty()) return;
+    wait_for_add();   // (the other buffer is free from here on)
+    n_batches++;
+    adding = std::async(std::launch::async, [&dev, &b, &t_add] {
+      const double t0 = wall_seconds();
+      const int32_t rc = slk_index_add_sequences(dev.ix, b.bases.data(), b.offsets.data(), b.taxa.data(), b.taxa.size());
+      t_add += wall_seconds() - t0;   // (one add at a time: nobody else writes this)
+      return std::make_pair(rc, std::string(rc == SLK_OK ? "" : slk_last_error()));
+    });
+    fill ^= 1;
+    batch[fill].clear();
+  };
+  const double t_walk0 = wall_seconds();
+  {
+    Timer t("Build records");
+    for_each_labelled_sequence(library, labels, [&](std::string_view sq, Taxon taxon) {
+      if (!batch[fill].taxa.empty() && batch[fill].bases.size() + sq.size() > batch_bases) submit();
+      Batch &b = batch[fill];
+      b.bases.insert(b.bases.end(), sq.begin(), sq.end());
+      b.offsets.push_back(b.bases.size());
+      b.taxa.push_back(taxon);
+      n_seq++; n_bases += sq.size();
+    });
+    submit();
+    wait_for_add();
+    SLK_CALL(slk_index_finalize(dev.ix));
+  }
+  const double t_walk = wall_seconds() - t_walk0;
+  slk_index_info info;
+  SLK_CALL(slk_index_get_info(dev.ix, &info));
+
+  // writeRecords (KeyValueIndex.scala:125-139), IndexParams.write, Taxonomy.copyToLocation.  The writer keeps whatever library is at
+  // INDEX until finish(): a failed build leaves nothing that loads, and an existing library is replaced only by a finished one.
+  LibraryProperties lp;
+  lp.k = k; lp.m = m; lp.spaces = spaces; lp.buckets = g_partitions; lp.xorMask = ip.xorMask; lp.canonical = true;
+  ExportTimes et;
+  const double t_write0 = wall_seconds();
+  {
+    Timer t("Write records to " + index);
+    LibraryWriter wr(index, lp, taxonomy, format);
+    export_to_writer(dev.ix, wr, lp.buckets, &et);
+    wr.finish();
+  }
+  const double t_write = wall_seconds() - t_write0;
+  std::cerr << "build: " << n_seq << " sequences, " << n_bases << " bases in " << n_batches << " batches, " << info.records << " records (table grown "
+            << info.grown << " times); read and parse " << t_walk - t_wait << " s beside add_sequences " << t_add << " s (waited for it " << t_wait
+            << " s); export " << et.export_s << " s in " << et.pieces << " pieces beside the writer (waited for it " << et.write_wait_s << " s), "
+            << t_write << " s in all" << std::endl;
+  // showIndexStats(None) and GenomeLibrary.inputStats (Slacken.scala:166-168)
+  std::cout << index_stats_text(tax, device_taxon_counts(dev.ix), m) << input_stats_text(label_file, all_labels, tax);
+  std::cout.flush();
+  return 0;
+}
+
 static int cmd_respace(int argc, char **argv) {
   std::string index, output;
   std::vector<int> spaces, devices{0};
@@ -878,14 +1146,9 @@ static int cmd_respace(int argc, char **argv) {
     slk_index *nx = nullptr;
     SLK_CALL(slk_index_respace(lib.dev.ix, s, nullptr, &nx));   // (an s not above the library's own: the reference's wording, and the end)
     std::unique_ptr<slk_index, void (*)(slk_index *)> owner(nx, slk_index_destroy);
-    uint64_t n = 0;
-    SLK_CALL(slk_index_export(nx, nullptr, nullptr, 0, &n));
-    std::vector<int64_t> keys(n);
-    std::vector<int32_t> taxa(n);
-    if (n) SLK_CALL(slk_index_export(nx, keys.data(), taxa.data(), n, &n));
     lp.spaces = s;
     LibraryWriter w(out_loc, lp, index + "_taxonomy", format);
-    for (uint64_t o = 0; o < n; o += RecordFile::CHUNK) w.add(keys.data() + o, taxa.data() + o, std::min(RecordFile::CHUNK, n - o));
+    export_to_writer(nx, w, lp.buckets, nullptr);
     w.finish();
     std::cout << "Stats for " << out_loc << "\n" << index_stats_text(lib.tax, device_taxon_counts(nx), lib.ip.m);
     std::cout.flush();
@@ -937,6 +1200,12 @@ static const char *HELP =
     "  table (keys masked, records regrouped by LCA; no genome is read) and written to OUTPUT with its first _s<digits> replaced by\n"
     "  _sS -- .properties, _taxonomy and the records as bucketed Parquet (as .slkrec with --format slkrec or without Arrow) -- followed\n"
     "  by `Stats for <location>` and the two lines `stats` prints\n"
+    "  slacken-amd [--partitions N] build -i INDEX -t TAXONOMY_DIR -l LIBRARY_DIR [-k 35] [-m 31] [-s|--spaces 7] [--check]\n"
+    "  [--format parquet|slkrec] [--expected-records N] [--devices D] (Slacken.scala:123-171): a library from the genomes of\n"
+    "  LIBRARY_DIR/library/**/*.fna labelled in LIBRARY_DIR/seqid2taxid.map -- minimizers found and merged by LCA on the GPU, the table\n"
+    "  exported piece by piece, grouped by Spark's bucket, into --partitions (200) Parquet files (or INDEX.slkrec), with\n"
+    "  INDEX.properties and a copy of TAXONOMY_DIR as INDEX_taxonomy -- followed by the two lines `stats` prints and the label file's\n"
+    "  statistics.  --check only reports the sequences without a minimizer (host only, nothing is written)\n"
     "host-only helpers: copy-records -i INDEX -o OUTPUT [--format parquet|slkrec] (a library rewritten by the library writer) |\n"
     "  report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
     "  stats-report TAXONOMY_DIR COUNTS_TSV (taxon count) M [--histogram] [-o OUTPUT [--labels FILE]] |\n"
@@ -945,12 +1214,18 @@ static const char *HELP =
     "             SLK_PARSE_THREADS (threads parsing one plain input file, default min(8, cores/2)), SLK_GZIP_LEVEL (1..9, default zlib's),\n"
     "             SLK_GZ_THREADS (threads inflating one gzip input file, default min(16, cores / files read side by side); 0: zlib),\n"
     "             SLK_CLASSIFY_THREADS (threads classifying batches, each with its own stream, default 2),\n"
-    "             SLK_HOST_TIMING (report where the wall clock of the classify loop went)\n";
+    "             SLK_HOST_TIMING (report where the wall clock of the classify loop went),\n"
+    "             SLK_BUILD_BATCH_BASES (bases per batch of `build`, default 2^30), SLK_EXPORT_PIECE_BUCKETS (table buckets per exported\n"
+    "             piece of `build` and `respace`, default 2^23)\n";
 
 int main(int argc, char **argv) {
   int i = 1;
-  while (i < argc && std::string(argv[i]) == "--partitions") i += 2;  // global Spark option of the reference: accepted, unused
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|bracken-build|compare-index|respace|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
+  // global Spark option of the reference: `buckets` of the library `build` writes; the other commands accept and ignore it
+  while (i < argc && std::string(argv[i]) == "--partitions") {
+    if (i + 1 < argc) g_partitions = atoi(argv[i + 1]);
+    i += 2;
+  }
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|bracken-build|compare-index|respace|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -959,7 +1234,7 @@ int main(int argc, char **argv) {
       {"props", cmd_props}, {"records", cmd_records}, {"repeated", cmd_repeated}, {"taxonomy", cmd_taxonomy},
       {"bracken-build", cmd_bracken_build}, {"kmer-distrib", cmd_kmer_distrib}, {"compare-index", cmd_compare_index},
       {"compareIndex", cmd_compare_index}, {"migration-report", cmd_migration_report}, {"stats", cmd_stats}, {"inspect", cmd_inspect},
-      {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}};
+      {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build}};
   // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
   //  they were commands)
   const bool bare = (cmd == "stats" || cmd == "inspect") && i >= argc;
@@ -969,6 +1244,6 @@ int main(int argc, char **argv) {
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `bracken-build`, `compare-index`, `respace`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `bracken-build`, `compare-index`, `respace`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }

@@ -127,6 +127,19 @@ struct Taxonomy {
     return -1;
   }
 
+  // Taxonomy.missingStepsToRoot :298-304: which of the eight standard levels (superkingdom = depth 1 .. species = depth 8) no taxon
+  // on t's path to the root has as its depth
+  std::vector<int> missingStepsToRoot(Taxon t) const {
+    bool found[10] = {};
+    for (Taxon p = t; p > 0 && p < size(); p = parents[p]) {
+      const int d = depth(p);
+      if (d >= 0 && d <= 8) found[d] = true;
+    }
+    std::vector<int> missing;
+    for (int level = 1; level <= 8; level++) if (!found[level]) missing.push_back(level);
+    return missing;
+  }
+
   // Taxonomy.taxaWithDescendants :304-311 as a membership vector
   std::vector<uint8_t> withDescendants(const std::vector<Taxon> &taxa) const {
     std::vector<uint8_t> in(parents.size(), 0);
