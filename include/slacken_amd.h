@@ -545,6 +545,51 @@ int32_t slk_migration_result(slk_migration *m, uint64_t *n_triples, int32_t *t1,
                              uint64_t cap, uint64_t *matched, uint64_t *unmatched);
 void slk_migration_destroy(slk_migration *m);
 
+/* ---- Genome coverage: replaces the arithmetic of IndexStatistics.showTaxonFullCoverageStats (S/slacken/IndexStatistics.scala:86-111;
+ * its consumer is Dynamic.reportDynamicIndexSupport, S/slacken/Dynamic.scala:230-241) and the k-mers per source taxon that
+ * IndexStatistics.totalKmerCountReport needs (:38-52).  Every labelled sequence is scanned, every super-mer's minimizer
+ * (SplitterMinimizers.find, S/slacken/Minimizers.scala:43-76: one (minimizer, source taxon) row per super-mer, with repetitions)
+ * is looked up in the index's table; the rows are grouped by (minimizer, source) into countAll and countDistinct = 1 (:91),
+ * inner-joined with the records (:99-100: a minimizer the index lacks leaves the join) and grouped by (source, depth of the record's
+ * LCA taxon) into sumAll and sumDistinct (:101-102).
+ *   slk_coverage_create   the index: finalized (SLK_E_STATE otherwise), one id column and not a shard of a table-sharded library
+ *                         (slk_index_set_shard), a window of at most 28 m-mers as for slk_index_add_sequences (SLK_E_UNSUPPORTED
+ *                         otherwise).  depths[T] (copied): Taxonomy.depth (:94) for every id, with the meaning it has in
+ *                         slk_migration_create; an id outside [0, T) has depth -1.  max_pairs: the most (minimizer, source) pairs
+ *                         one group may hold (16 bytes per slot of a map kept at most half full); 0 = what fits half of the device
+ *                         memory free at the call -- a choice, not a measured number.
+ *   slk_coverage_add      R sequences exactly as slk_index_add_sequences takes them (no whitespace, split around anything that is
+ *                         not ACGTU) with the taxon each came from (the `taxon` column of GenomeLibrary.joinSequencesAndLabels, :87).
+ *                         source_taxa[i] is any int32 but NONE, need not be a node of the taxonomy, and is only carried; sequences
+ *                         with source NONE are skipped.  Synchronous on st.
+ *   slk_coverage_fold     closes a GROUP: the (minimizer, source) pairs counted so far go into the (source, depth) rows (:101-102)
+ *                         and are forgotten, which frees the map.  The caller promises that no source taxon has sequences on
+ *                         both sides of a fold: otherwise that taxon's `distinct` counts a minimizer once per group it occurs in.
+ *                         `all` and the totals are sums and do not care.
+ *   slk_coverage_result   folds what is pending, then the rows so far sorted by source then depth: all = sumAll, distinct =
+ *                         sumDistinct (:102).  *n_rows = their number; cap 0 queries only that, 0 < cap < *n_rows gives
+ *                         SLK_E_CAPACITY.  May be called repeatedly and between adds (it closes the group, as a fold does).
+ *   slk_coverage_totals   one row per source taxon seen, ascending, also those without a k-mer: kmers = the sum over its super-mers
+ *                         of length - (k - 1) (:45-46), supermers = their number, matched or not.  Same cap protocol.
+ *   slk_coverage_budget   the handle's max_pairs (what 0 was resolved to)
+ * Within one group the result does not depend on the order of the sequences or on how they are split over calls.
+ * The pair map starts at 2^SLK_COVERAGE_MAP_LOG2 slots (default 20, at least 10) and doubles between kernel launches, never beyond
+ * the budget; a launch covers no more k-mer windows than the map has free slots, so no launch can fill it.  More pairs in one group
+ * than max_pairs, or more than 2^28 source taxa, is SLK_E_CAPACITY.  After SLK_E_CAPACITY or SLK_E_HIP the handle has counted an
+ * unknown part and is spent: every call but slk_coverage_destroy returns SLK_E_STATE.  A call refused with SLK_E_INVALID counted
+ * nothing and leaves the handle usable.  The index must outlive the adds and must not change (its table is the minimizers' names). */
+typedef struct slk_coverage slk_coverage;
+int32_t slk_coverage_create(slk_index *ix, const int32_t *depths, int32_t T, uint64_t max_pairs, slk_coverage **out);
+int32_t slk_coverage_add(slk_coverage *c, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const int32_t *source_taxa,
+                         uint64_t R);
+int32_t slk_coverage_fold(slk_coverage *c, slk_stream *st);
+int32_t slk_coverage_result(slk_coverage *c, uint64_t *n_rows, int32_t *source, int32_t *depth, uint64_t *all, uint64_t *distinct,
+                            uint64_t cap);
+int32_t slk_coverage_totals(slk_coverage *c, uint64_t *n_sources, int32_t *source, uint64_t *kmers, uint64_t *supermers,
+                            uint64_t cap);
+uint64_t slk_coverage_budget(const slk_coverage *c);
+void slk_coverage_destroy(slk_coverage *c);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,7 +80,9 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_shard_of", "slk_stream_set_merged_hits", "slk_classify_hits_device", "slk_shard_batch_rows", "slk_shard_chunk", "slk_shard_step_device",
            "slk_stream_last_deferred", "slk_table_slot", "slk_table_hash_of",
            "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy",
-           "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy"]
+           "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy",
+           "slk_coverage_create", "slk_coverage_add", "slk_coverage_fold", "slk_coverage_result", "slk_coverage_totals", "slk_coverage_budget",
+           "slk_coverage_destroy"]
 
 
 def lib_path():
@@ -175,6 +177,15 @@ def lib():
                                        C.POINTER(C.c_uint64)]
     L.slk_migration_destroy.argtypes = [vp]
     L.slk_migration_destroy.restype = None
+    L.slk_coverage_create.argtypes = [vp, i32p, C.c_int32, C.c_uint64, C.POINTER(vp)]
+    L.slk_coverage_add.argtypes = [vp, vp, u8p, u64p, i32p, C.c_uint64]
+    L.slk_coverage_fold.argtypes = [vp, vp]
+    L.slk_coverage_result.argtypes = [vp, C.POINTER(C.c_uint64), i32p, i32p, u64p, u64p, C.c_uint64]
+    L.slk_coverage_totals.argtypes = [vp, C.POINTER(C.c_uint64), i32p, u64p, u64p, C.c_uint64]
+    L.slk_coverage_budget.argtypes = [vp]
+    L.slk_coverage_budget.restype = C.c_uint64
+    L.slk_coverage_destroy.argtypes = [vp]
+    L.slk_coverage_destroy.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -434,6 +445,61 @@ class MinimizerMigration:
     def close(self):
         if getattr(self, "h", None):
             lib().slk_migration_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Coverage:
+    """Genome coverage of labelled sequences against an index (slk_coverage_*: IndexStatistics.showTaxonFullCoverageStats,
+    S/slacken/IndexStatistics.scala:86-111, and the k-mers per source of totalKmerCountReport, :38-52).  depths[t] =
+    Taxonomy.depth(t) of the index's taxonomy.  add() takes whole sequences (no whitespace) with the taxon each came from; fold()
+    closes a group of sources; result() gives (source, depth, all, distinct) sorted by source then depth, totals() gives
+    (source, kmers, supermers) sorted by source: numpy arrays."""
+
+    def __init__(self, index, depths=None, max_pairs=0, stream=None):
+        self.index = index
+        self.stream = stream if stream is not None else index.stream()
+        h = C.c_void_p()
+        d = _np(depths, np.int32) if depths is not None else None
+        _check(lib().slk_coverage_create(index.h, _ptr(d), d.size if d is not None else 0, int(max_pairs), C.byref(h)))
+        self.h = h
+
+    def budget(self):
+        return int(lib().slk_coverage_budget(self.h))
+
+    def add(self, bases, offsets, source_taxa):
+        bases, offsets, taxa = _np(bases, np.uint8), _np(offsets, np.uint64), _np(source_taxa, np.int32)
+        assert offsets.size == taxa.size + 1
+        _check(lib().slk_coverage_add(self.h, self.stream.h, _ptr(bases), _ptr(offsets), _ptr(taxa), taxa.size))
+
+    def fold(self):
+        _check(lib().slk_coverage_fold(self.h, self.stream.h))
+
+    def result(self):
+        n = C.c_uint64(0)
+        _check(lib().slk_coverage_result(self.h, C.byref(n), None, None, None, None, 0))
+        source, depth = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        count, distinct = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_coverage_result(self.h, C.byref(n), _ptr(source), _ptr(depth), _ptr(count), _ptr(distinct), n.value))
+        return source, depth, count, distinct
+
+    def totals(self):
+        n = C.c_uint64(0)
+        _check(lib().slk_coverage_totals(self.h, C.byref(n), None, None, None, 0))
+        source, kmers, supermers = np.zeros(n.value, np.int32), np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_coverage_totals(self.h, C.byref(n), _ptr(source), _ptr(kmers), _ptr(supermers), n.value))
+        return source, kmers, supermers
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slk_coverage_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -153,6 +153,37 @@ __device__ __forceinline__ int32_t table_lookup(const TableView &t, uint64_t key
   return 0;
 }
 
+// The same probe, also telling where the record lies: *cell = bucket * CELLS + c of the matching cell (below 2^36: at most 2^32
+// buckets of at most 16 cells), untouched on a miss.  A finalized table does not move, so the position names the record for as long
+// as the index lives -- the only 64-bit name a record of a 32-nt minimizer has room for beside another field (coverage.hip).
+__device__ __forceinline__ int32_t table_lookup_cell(const TableView &t, uint64_t key, uint64_t *cell) {
+  uint64_t h = fmix64(key);
+  uint32_t home;
+  uint64_t rem_hi;
+  table_slot(t.g, h, home, rem_hi);
+  uint64_t tmask = (1ULL << t.g.taxon_bits) - 1;
+  for (int d = 0; d <= t.max_disp; d++) {
+    const uint64_t first = (uint64_t)table_bucket(t.g, home, (uint32_t)d) * CELLS;
+    const ulonglong2 *b = (const ulonglong2 *)(t.cells + first);
+    uint64_t tag = rem_hi | (uint64_t)d;
+    uint64_t cells[CELLS];
+#pragma unroll
+    for (int c = 0; c < LPB; c++) { ulonglong2 v = b[c]; cells[2 * c] = v.x; cells[2 * c + 1] = v.y; }
+    bool has_empty = false;
+    int32_t found = 0;
+    int at = 0;
+#pragma unroll
+    for (int c = 0; c < CELLS; c++) {
+      has_empty |= (cells[c] == 0);
+      if (cells[c] != 0 && cell_tag(t.g, cells[c]) == tag) { found = (int32_t)(cells[c] & tmask); at = c; }
+    }
+    if (found) { *cell = first + (uint64_t)at; return found; }
+    if (has_empty) return 0;
+    if (t.g.flag && !(cells[0] & t.g.flag)) return 0;  // full, but no record ever went past it
+  }
+  return 0;
+}
+
 __device__ __forceinline__ int32_t tax_parent(const int32_t *parents, int32_t ntax, int32_t t) {
   return ((uint32_t)t < (uint32_t)ntax) ? parents[t] : 0;
 }

@@ -1,5 +1,5 @@
 // pairmap.h -- the device-wide (a << 32 | b) -> uint64 count map that bracken.hip (source, dest) and migration.hip (t1, t2) add
-// into: open addressing with linear probing over a power-of-two number of slots, two parallel arrays in HBM.  Internal.
+// into, and that coverage.hip keys by (cell << 28 | source) and by (source << 32 | depth): open addressing with linear probing over a power-of-two number of slots, two parallel arrays in HBM.  Internal.
 #pragma once
 #include "hostside.h"
 
@@ -13,6 +13,24 @@ __device__ __forceinline__ bool pair_map_add(unsigned long long *keys, unsigned 
     const unsigned long long prev = atomicCAS(&keys[h], (unsigned long long)PAIR_EMPTY, key);
     if (prev == PAIR_EMPTY || prev == key) {
       atomicAdd(&counts[h], n);
+      if (n_pairs != nullptr && prev == PAIR_EMPTY) atomicAdd(n_pairs, 1ULL);
+      return true;
+    }
+    h = (h + 1) & mask;
+  }
+  return false;
+}
+
+// The same with two counters per key (coverage.hip: a sum and a number of distinct things): first[slot] += a, second[slot] += b.
+__device__ __forceinline__ bool pair_map_add2(unsigned long long *keys, unsigned long long *first, unsigned long long *second, uint64_t mask,
+                                              unsigned long long key, unsigned long long a, unsigned long long b,
+                                              unsigned long long *n_pairs) {
+  uint64_t h = slk::fmix64(key) & mask;
+  for (uint64_t probe = 0; probe <= mask; probe++) {
+    const unsigned long long prev = atomicCAS(&keys[h], (unsigned long long)PAIR_EMPTY, key);
+    if (prev == PAIR_EMPTY || prev == key) {
+      atomicAdd(&first[h], a);
+      atomicAdd(&second[h], b);
       if (n_pairs != nullptr && prev == PAIR_EMPTY) atomicAdd(n_pairs, 1ULL);
       return true;
     }

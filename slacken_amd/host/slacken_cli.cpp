@@ -9,6 +9,7 @@
 #include <sstream>
 
 #include "classify_stream.hpp"
+#include "coverage.hpp"
 #include "migration.hpp"
 #include "repeated_titles.hpp"
 
@@ -1120,6 +1121,53 @@ static int cmd_build(int argc, char **argv) {
   return 0;
 }
 
+// ---- coverage: the genome coverage of IndexStatistics (S/slacken/IndexStatistics.scala:38-52, 86-111), behind a command of its own.
+// The reference reaches it through `stats --library`, `inspect --library` and `classify2 --index-reports`; those stay refused here.
+static const char *COVERAGE_USAGE = "usage: coverage -i INDEX -l LIBRARY_DIR -o OUTPUT [--devices D]";
+
+static int cmd_coverage(int argc, char **argv) {
+  const char *why_one = "the library's table must fit one GPU";
+  CoverageOptions o;
+  for (Args a(argc, argv); a.take();) {
+    if (a == "-i" || a == "--index") o.index = a.next();
+    else if (a == "-l" || a == "--library") o.library = a.next();
+    else if (a == "-o" || a == "--output") o.output = a.next();
+    else if (a == "--devices") o.devices = parse_single_device(a.next(), "coverage", why_one);
+    else if (a == "--shard-table") refuse_shard_table("coverage", why_one, COVERAGE_USAGE);
+    else die("unknown option " + a.opt + "\n" + COVERAGE_USAGE);
+  }
+  if (o.index.empty() || o.library.empty() || o.output.empty()) die(COVERAGE_USAGE);
+  const IndexParams ip = read_index_params(o.index);
+  refuse_wide("coverage", ip);
+  if (ip.k - ip.m + 1 > BUILD_MAX_WINDOW)
+    die("coverage supports windows of up to " + std::to_string(BUILD_MAX_WINDOW) + " m-mers (k - m + 1 = " + std::to_string(ip.k - ip.m + 1) + ")");
+  // GenomeLibrary.joinSequencesAndLabels (GenomeLibrary.scala:50-57): the sequences joined with the labels by header -- every
+  // label, with no isDefined filter (unlike `build`: the source taxon is only carried)
+  std::unordered_map<std::string, Taxon> labels;
+  for (auto &lb : read_label_map(o.library)) labels[lb.first] = lb.second;
+  return coverage_run(o, [&](auto fn) { for_each_labelled_sequence(o.library, labels, fn); });
+}
+
+// coverage-report TAXONOMY_DIR COUNTS_TSV SIZES_TSV ROWS_TSV OUTPUT: the three files `coverage` writes, from "taxon \t records",
+// "source \t k-mers" and "source \t depth \t all \t distinct" lines (host only: the outputs without a GPU)
+static int cmd_coverage_report(int argc, char **argv) {
+  if (argc != 5) die("usage: coverage-report TAXONOMY_DIR COUNTS_TSV SIZES_TSV ROWS_TSV OUTPUT");
+  const Taxonomy tax = Taxonomy::load(argv[0]);
+  std::map<Taxon, uint64_t> records, sizes;
+  long long t, d;
+  unsigned long long c, c2;
+  std::ifstream f1 = open_input(argv[1]);
+  while (f1 >> t >> c) records[(Taxon)t] += c;
+  std::ifstream f2 = open_input(argv[2]);
+  while (f2 >> t >> c) sizes[(Taxon)t] += c;
+  std::vector<CoverageRow> rows;
+  std::ifstream f3 = open_input(argv[3]);
+  while (f3 >> t >> d >> c >> c2) rows.push_back({(int32_t)t, (int32_t)d, c, c2});
+  std::sort(rows.begin(), rows.end(), [](const CoverageRow &a, const CoverageRow &b) { return a.source != b.source ? a.source < b.source : a.depth < b.depth; });
+  write_coverage_files(tax, TaxonCounts(records.begin(), records.end()), std::vector<std::pair<Taxon, uint64_t>>(sizes.begin(), sizes.end()), rows, argv[4]);
+  return 0;
+}
+
 static int cmd_respace(int argc, char **argv) {
   std::string index, output;
   std::vector<int> spaces, devices{0};
@@ -1206,16 +1254,26 @@ static const char *HELP =
     "  exported piece by piece, grouped by Spark's bucket, into --partitions (200) Parquet files (or INDEX.slkrec), with\n"
     "  INDEX.properties and a copy of TAXONOMY_DIR as INDEX_taxonomy -- followed by the two lines `stats` prints and the label file's\n"
     "  statistics.  --check only reports the sequences without a minimizer (host only, nothing is written)\n"
+    "  slacken-amd coverage -i INDEX -l|--library LIBRARY_DIR -o OUTPUT [--devices D] (IndexStatistics.scala:38-52, 86-111; the reference's\n"
+    "  `stats --library`, `inspect --library` and `classify2 --index-reports` reach this arithmetic, here those flags stay refused): every\n"
+    "  genome of LIBRARY_DIR labelled in LIBRARY_DIR/seqid2taxid.map is scanned on the GPU and every super-mer's minimizer looked up in\n"
+    "  INDEX's resident table.  OUTPUT_support_report_minimizerCoverage.txt and OUTPUT_support_report_minimizerDistinctCoverage.txt: per\n"
+    "  source taxon `<taxon>  <depth>:<count>|..`, its minimizers (with repetitions / distinct) by the rank depth of the LCA taxon the\n"
+    "  library stores for them; OUTPUT_min_report.txt: the Kraken report of `inspect` with the columns TKC1-LeafOnly, TKC2-FirstChildren and\n"
+    "  TKC3-AllChildren (average k-mers per genome).  A library with more super-mers than the GPU's memory takes at once is counted in\n"
+    "  groups of source taxa, one pass over LIBRARY_DIR each\n"
     "host-only helpers: copy-records -i INDEX -o OUTPUT [--format parquet|slkrec] (a library rewritten by the library writer) |\n"
     "  report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
     "  stats-report TAXONOMY_DIR COUNTS_TSV (taxon count) M [--histogram] [-o OUTPUT [--labels FILE]] |\n"
-    "  migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV (t1 t2 count) OUTPUT | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
+    "  migration-report SUBJECT_TAXONOMY_DIR REFERENCE_TAXONOMY_DIR PAIRS_TSV (t1 t2 count) OUTPUT |\n"
+    "  coverage-report TAXONOMY_DIR COUNTS_TSV (taxon records) SIZES_TSV (source k-mers) ROWS_TSV (source depth all distinct) OUTPUT | parse FILE [MATE_FILE] | props INDEX | records INDEX | repeated [-p] FILES\n"
     "environment: SLK_HOST_THREADS (formatting/decoding threads), SLK_INPUT_STREAMS (input files read side by side, default 8),\n"
     "             SLK_PARSE_THREADS (threads parsing one plain input file, default min(8, cores/2)), SLK_GZIP_LEVEL (1..9, default zlib's),\n"
     "             SLK_GZ_THREADS (threads inflating one gzip input file, default min(16, cores / files read side by side); 0: zlib),\n"
     "             SLK_CLASSIFY_THREADS (threads classifying batches, each with its own stream, default 2),\n"
     "             SLK_HOST_TIMING (report where the wall clock of the classify loop went),\n"
-    "             SLK_BUILD_BATCH_BASES (bases per batch of `build`, default 2^30), SLK_EXPORT_PIECE_BUCKETS (table buckets per exported\n"
+    "             SLK_BUILD_BATCH_BASES (bases per batch of `build` and `coverage`, default 2^30), SLK_COVERAGE_MAX_PAIRS ((minimizer, source\n"
+    "             taxon) pairs `coverage` counts at a time, default: what half of the GPU's free memory holds), SLK_EXPORT_PIECE_BUCKETS (table buckets per exported\n"
     "             piece of `build` and `respace`, default 2^23)\n";
 
 int main(int argc, char **argv) {
@@ -1225,7 +1283,7 @@ int main(int argc, char **argv) {
     if (i + 1 < argc) g_partitions = atoi(argv[i + 1]);
     i += 2;
   }
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|bracken-build|compare-index|respace|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|bracken-build|compare-index|respace|coverage|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1234,7 +1292,8 @@ int main(int argc, char **argv) {
       {"props", cmd_props}, {"records", cmd_records}, {"repeated", cmd_repeated}, {"taxonomy", cmd_taxonomy},
       {"bracken-build", cmd_bracken_build}, {"kmer-distrib", cmd_kmer_distrib}, {"compare-index", cmd_compare_index},
       {"compareIndex", cmd_compare_index}, {"migration-report", cmd_migration_report}, {"stats", cmd_stats}, {"inspect", cmd_inspect},
-      {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build}};
+      {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build},
+      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}};
   // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
   //  they were commands)
   const bool bare = (cmd == "stats" || cmd == "inspect") && i >= argc;
@@ -1244,6 +1303,6 @@ int main(int argc, char **argv) {
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `bracken-build`, `compare-index`, `respace`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `bracken-build`, `compare-index`, `respace`, `coverage`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }

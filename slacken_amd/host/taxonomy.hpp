@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <functional>
 #include <map>
 #include <sstream>
 #include <stdexcept>
@@ -201,6 +202,10 @@ struct KrakenReport {
   const Taxonomy &tax;
   std::map<Taxon, long> taxonCounts, cladeTotals;
   long totalSequences = 0;
+  // What a subclass of the reference adds by overriding dataColumnHeaders / dataColumns (:57-70; TotalKmerCountReport,
+  // IndexStatistics.scala:114-128): text behind "In taxon", each column with its leading tab.  Unset: the plain report.
+  std::string extraHeaders;
+  std::function<std::string(Taxon)> extraColumns;
 
   KrakenReport(const Taxonomy &t, const std::vector<std::pair<Taxon, long>> &counts) : tax(t) {
     for (auto &c : counts) {  // TreeAggregator :27-41
@@ -216,7 +221,7 @@ struct KrakenReport {
   std::string reportLine(Taxon taxid, int rank, int rankDepth, int depth) const {  // :72-77
     std::ostringstream o;
     o << java_format_6_2f(100.0 * (double)clade(taxid) / (double)totalSequences) << '\t' << clade(taxid) << '\t' << own(taxid)
-      << '\t' << rank_codes(rank);
+      << (extraColumns ? extraColumns(taxid) : std::string()) << '\t' << rank_codes(rank);
     if (rankDepth != 0) o << rankDepth;
     o << '\t' << taxid << '\t' << std::string(2 * depth, ' ')
       << ((taxid >= 0 && taxid < tax.size() && tax.has_name[taxid]) ? tax.names[taxid] : "");
@@ -232,7 +237,7 @@ struct KrakenReport {
     for (auto &kc : kids) if (kc.second > 0) dfs(out, kc.first, r, rd, depth + 1);
   }
   void print(std::ostream &out) const {  // :104-116
-    out << "#Perc\tAggregate\tIn taxon\tRank\tTaxon\tName\n";
+    out << "#Perc\tAggregate\tIn taxon" << extraHeaders << "\tRank\tTaxon\tName\n";
     if (own(NONE) != 0) out << reportLine(NONE, 0, 0, 0) << '\n';
     dfs(out, ROOT, 1, 0, 0);
   }
