@@ -590,6 +590,39 @@ int32_t slk_coverage_totals(slk_coverage *c, uint64_t *n_sources, int32_t *sourc
 uint64_t slk_coverage_budget(const slk_coverage *c);
 void slk_coverage_destroy(slk_coverage *c);
 
+/* ---- Sample support: replaces the arithmetic of Dynamic.minimizersInSubjects (S/slacken/Dynamic.scala:95-117: the counts behind
+ * `classify2 -C` and `-D`) and of Dynamic.multiStatsPerTaxon (:152-180: totalKmerCount, distinctMinimizerCount and
+ * totalMinimizerCount of the support reports, :210-228).  Every SEQUENCE super-mer of every read is looked up in the index's table;
+ * a hit (a miss is NONE and never counts) whose taxon has depth >= min_depth (:103, :167-170) is grouped by taxon into
+ *   kmers       the sum of its k-mer windows (sum(kmerCount), :174)
+ *   minimizers  the number of such super-mers (count(*), :116, :176)
+ *   distinct    the number of different minimizers among them (count_distinct, :112, :175).
+ * A minimizer is one record, one cell of the table and one taxon, so `distinct` is the number of different cells hit: the handle
+ * keeps one bit per table cell (cells / 8 bytes of device memory), set the first time the cell is hit, for its whole life.
+ *   slk_support_create   the index: finalized (SLK_E_STATE otherwise), one id column, not a shard of a table-sharded library, a window
+ *                        of at most 28 m-mers (SLK_E_UNSUPPORTED otherwise), as for slk_coverage_create.  depths[T] (copied) has the
+ *                        meaning it has there; an id outside [0, T) has depth -1.  min_depth < 0 is SLK_E_INVALID.  want_distinct =
+ *                        0: no bitmap is allocated and every row's `distinct` is 0.
+ *   slk_support_add      R sequences exactly as slk_index_add_sequences takes them (no whitespace, split around anything that is not
+ *                        ACGTU).  The mates of paired reads are sequences of their own: the mate-pair border and ambiguous spans
+ *                        carry no true taxon and never count.  Synchronous on st.
+ *   slk_support_result   the rows with kmers > 0 || minimizers > 0, ascending by taxon, in the caller's ids.  *n_taxa = their number;
+ *                        cap 0 queries only that, 0 < cap < *n_taxa gives SLK_E_CAPACITY (the first cap rows are written).  May be
+ *                        called repeatedly and between adds.
+ *   slk_support_totals   sequences = those handed to slk_support_add; supermers = the SEQUENCE super-mers scanned; matched = those
+ *                        the table holds; kept = those that passed min_depth (the sum of `minimizers`).  Any pointer may be null.
+ * The result does not depend on the order of the sequences or on how they are split over calls; a super-mer that a long read's
+ * 512-window chunks cut in two counts once as a minimizer, with all its k-mers.  After SLK_E_HIP the handle has counted an unknown
+ * part and is spent: every call but slk_support_destroy returns SLK_E_STATE.  A call refused with SLK_E_INVALID counted nothing.
+ * The index must outlive the handle and must not change: its cells name the minimizers, and the bitmap is sized at create. */
+typedef struct slk_support slk_support;
+int32_t slk_support_create(slk_index *ix, const int32_t *depths, int32_t T, int32_t min_depth, int32_t want_distinct, slk_support **out);
+int32_t slk_support_add(slk_support *s, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, uint64_t R);
+int32_t slk_support_result(slk_support *s, uint64_t *n_taxa, int32_t *taxa, uint64_t *kmers, uint64_t *minimizers, uint64_t *distinct,
+                           uint64_t cap);
+int32_t slk_support_totals(slk_support *s, uint64_t *sequences, uint64_t *supermers, uint64_t *matched, uint64_t *kept);
+void slk_support_destroy(slk_support *s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,7 +82,8 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy",
            "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy",
            "slk_coverage_create", "slk_coverage_add", "slk_coverage_fold", "slk_coverage_result", "slk_coverage_totals", "slk_coverage_budget",
-           "slk_coverage_destroy"]
+           "slk_coverage_destroy",
+           "slk_support_create", "slk_support_add", "slk_support_result", "slk_support_totals", "slk_support_destroy"]
 
 
 def lib_path():
@@ -186,6 +187,12 @@ def lib():
     L.slk_coverage_budget.restype = C.c_uint64
     L.slk_coverage_destroy.argtypes = [vp]
     L.slk_coverage_destroy.restype = None
+    L.slk_support_create.argtypes = [vp, i32p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.slk_support_add.argtypes = [vp, vp, u8p, u64p, C.c_uint64]
+    L.slk_support_result.argtypes = [vp, C.POINTER(C.c_uint64), i32p, u64p, u64p, u64p, C.c_uint64]
+    L.slk_support_totals.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
+    L.slk_support_destroy.argtypes = [vp]
+    L.slk_support_destroy.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -500,6 +507,51 @@ class Coverage:
     def close(self):
         if getattr(self, "h", None):
             lib().slk_coverage_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Support:
+    """A sample's minimizers counted per taxon against an index (slk_support_*: Dynamic.minimizersInSubjects and multiStatsPerTaxon,
+    S/slacken/Dynamic.scala:95-117, 152-180).  depths[t] = Taxonomy.depth(t) of the index's taxonomy; hits of taxa below min_depth are
+    dropped.  add() takes sequences (no whitespace; the mates of paired reads are sequences of their own); result() gives
+    (taxon, kmers, minimizers, distinct) sorted by taxon as numpy arrays, totals() gives (sequences, supermers, matched, kept)."""
+
+    def __init__(self, index, depths=None, min_depth=0, want_distinct=True, stream=None):
+        self.index = index
+        self.stream = stream if stream is not None else index.stream()
+        h = C.c_void_p()
+        d = _np(depths, np.int32) if depths is not None else None
+        _check(lib().slk_support_create(index.h, _ptr(d), d.size if d is not None else 0, int(min_depth), 1 if want_distinct else 0, C.byref(h)))
+        self.h = h
+
+    def add(self, bases, offsets):
+        bases, offsets = _np(bases, np.uint8), _np(offsets, np.uint64)
+        assert offsets.size >= 1
+        _check(lib().slk_support_add(self.h, self.stream.h, _ptr(bases), _ptr(offsets), offsets.size - 1))
+
+    def result(self):
+        n = C.c_uint64(0)
+        _check(lib().slk_support_result(self.h, C.byref(n), None, None, None, None, 0))
+        taxa = np.zeros(n.value, np.int32)
+        kmers, minimizers, distinct = (np.zeros(n.value, np.uint64) for _ in range(3))
+        if n.value:
+            _check(lib().slk_support_result(self.h, C.byref(n), _ptr(taxa), _ptr(kmers), _ptr(minimizers), _ptr(distinct), n.value))
+        return taxa, kmers, minimizers, distinct
+
+    def totals(self):
+        v = [C.c_uint64(0) for _ in range(4)]
+        _check(lib().slk_support_totals(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slk_support_destroy(self.h)
             self.h = None
 
     def __del__(self):

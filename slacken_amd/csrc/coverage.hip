@@ -4,7 +4,7 @@
 // taxon) row per super-mer, with repetitions), groups the rows by (minimizer, source) into countAll and countDistinct = 1 (:91),
 // inner-joins them with the records (:99-100) and groups again by (source, depth(record's LCA taxon)) into sumAll and sumDistinct
 // (:101-102).  Here:
-//   scan   coverage_scan_kernel, build_kernel's scan (build.hip) with exact seams: one lane per chunk of BUILD_CHUNK_WINDOWS windows,
+//   scan   coverage_scan_kernel, build_kernel's scan (build.hip) with exact seams (chunkscan.h, shared with support.hip): one lane per chunk of BUILD_CHUNK_WINDOWS windows,
 //          every super-mer's minimizer looked up in the table (the one random HBM request per super-mer); a hit adds 1 to a
 //          device-wide pair map (pairmap.h) under (cell of the record << 28 | source ordinal) -- the first group-by and the join.
 //          The record's position stands for the minimizer: a 32-nt minimizer fills all 64 bits, the cell index needs 36.
@@ -19,6 +19,7 @@
 // The fold counts on the three levels of migration_kernel (migration.hip), in that order -- wave ballot, LDS map, device map -- since
 // a genome's slots nearly all land on two or three (source, depth) pairs; the scan's per-source totals are combined by the wave
 // before they reach the device arrays, since the chunks of a wave mostly belong to one sequence.
+#include "chunkscan.h"
 #include "hostside.h"
 #include "pairmap.h"
 
@@ -61,16 +62,6 @@ struct CovArgs {
   int32_t *status;                 // bit 1: a map is full; bit 2: a pair names a cell outside the table
 };
 
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1)
-    v += ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o);
-  return v;
-}
-
 __global__ void __launch_bounds__(CV_W * 64) coverage_scan_kernel(CovArgs A) {
   extern __shared__ uint64_t ring[];  // [w][CV_W*64]: the last w keys of every lane
   __shared__ CovLds L;
@@ -78,7 +69,6 @@ __global__ void __launch_bounds__(CV_W * 64) coverage_scan_kernel(CovArgs A) {
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t wib = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t stride = CV_W * 64;
-  const int w = P.w, k = P.k, m = P.m;
   const uint64_t c = (uint64_t)blockIdx.x * stride + tid;
   const bool mine = c < A.nchunks;
   const uint32_t len = mine ? A.chunk_len[c] : 0;
@@ -86,14 +76,8 @@ __global__ void __launch_bounds__(CV_W * 64) coverage_scan_kernel(CovArgs A) {
   const uint32_t src = mine ? A.chunk_src[c] : 0;
   const bool prime = (src & CV_PRIME) != 0;
   const uint32_t ord = src & CV_ORD_MASK;
-  uint32_t maxlen = len;
-  for (int o = 32; o > 0; o >>= 1) maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, o));
-  maxlen = __builtin_amdgcn_readfirstlane(maxlen);
-
-  uint64_t fwd = 0, rc = 0, minv = ~0ULL, cur_val = 0, lo = 0, hi = 0;
-  uint32_t nvalid = 0;
-  int head = w - 1, minage = 0;
-  bool have_cur = false;
+  const uint32_t maxlen = wave_max32(len);
+  ChunkScan S(P.w);
   uint32_t qhead = 0, qn = 0;          // wave-uniform
   uint32_t n_kmers = 0, n_supermers = 0;   // of this lane's chunk: its own windows, matched or not
 
@@ -110,55 +94,15 @@ __global__ void __launch_bounds__(CV_W * 64) coverage_scan_kernel(CovArgs A) {
   };
 
   for (uint32_t step = 0; step < maxlen; step++) {
-    if ((step & 15) == 0) {  // 16 bytes per lane every 16 steps (the buffer's last block: byte loads, engine.h)
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (step < len) v = load_block16(A.bases + start + step, clamp_room(A.total_bases - start - step));
-      lo = ((uint64_t)v.y << 32) | v.x;
-      hi = ((uint64_t)v.w << 32) | v.z;
-    }
-    uint32_t ch = (uint32_t)(lo & 0xff);
-    lo = (lo >> 8) | (hi << 56);
-    hi >>= 8;
-    int t = (step < len) ? base_code(ch) : 5;
-    bool emit = false;
-    if (t >= 4) {  // InputReader.removeInvalid (InputReader.scala:60-72): sequences are split around anything else
-      nvalid = 0; fwd = 0; rc = 0; head = w - 1; minage = 0; minv = ~0ULL; have_cur = false;
-    } else {
-      nvalid++;
-      fwd = (fwd << 2) | ((uint64_t)t << P.sh);
-      rc = ((rc >> 2) | ((uint64_t)(3 - t) << 62)) & P.keep;
-      if (nvalid >= (uint32_t)m) {
-        uint64_t canon = (P.canonical && rc < fwd) ? rc : fwd;
-        uint64_t key = (canon ^ P.xmask) & P.smask;
-        head = (head + 1 == w) ? 0 : head + 1;
-        ring[(uint32_t)head * stride + tid] = key;
-        if (key <= minv) { minv = key; minage = 0; }
-        else if (++minage >= w) {
-          int slot = (head + 1 == w) ? 0 : head + 1;
-          minv = ~0ULL;
-          for (int a = w - 1; a >= 0; a--) {
-            uint64_t v = ring[(uint32_t)slot * stride + tid];
-            if (v <= minv) { minv = v; minage = a; }
-            slot = (slot + 1 == w) ? 0 : slot + 1;
-          }
-        }
-        if (nvalid >= (uint32_t)k) {
-          const bool fresh = !have_cur || minv != cur_val;   // a new super-mer starts
-          have_cur = true;
-          cur_val = minv;
-          if (!(prime && step == (uint32_t)(k - 1))) {       // (the priming window belongs to the chunk before)
-            n_kmers++;
-            if (fresh) { emit = true; n_supermers++; }
-          }
-        }
-      }
-    }
+    const int window = S.step(P, ring, stride, tid, A.bases, start, A.total_bases, step, len, prime);
+    const bool emit = window == ChunkScan::FRESH;
+    if (window != ChunkScan::NO_WINDOW) { n_kmers++; if (emit) n_supermers++; }
     uint64_t mask = __ballot(emit);
     if (mask) {
       uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
       if (emit) {
         uint32_t e = (qhead + qn + before) & 127;
-        L.q_key[wib][e] = cur_val;
+        L.q_key[wib][e] = S.cur_val;
         L.q_ord[wib][e] = ord;
       }
       qn += (uint32_t)__popcll(mask);

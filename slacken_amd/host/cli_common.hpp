@@ -1,5 +1,5 @@
 // cli_common.hpp -- what every part of the command-line host shares: the fatal error, the check of an slk_* call, the task timer,
-// the wall clock, the cursor of the option loops, the size of the host's thread pools.
+// the wall clock, the cursor of the option loops, --devices and --shard-table, the size of the host's thread pools.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -9,6 +9,7 @@
 #include <iostream>
 #include <string>
 #include <thread>
+#include <vector>
 
 #include "../../include/slacken_amd.h"
 
@@ -41,6 +42,33 @@ struct Args {
   std::string next() { return i < argc ? argv[i++] : (die("missing value for " + opt), ""); }
   const char *peek() const { return i < argc ? argv[i] : nullptr; }   // (for the options that take a list of values)
 };
+
+inline std::vector<int> parse_device_list(const std::string &v) {   // --devices: `all` or e.g. 0,1,2,3
+  std::vector<int> out;
+  if (v == "all") {
+    for (int d = 0; d < slk_device_count(); d++) out.push_back(d);
+    if (out.empty()) die("--devices all: no GPU visible");
+    return out;
+  }
+  size_t p0 = 0;
+  while (p0 <= v.size()) {
+    size_t p1 = v.find(',', p0);
+    if (p1 == std::string::npos) p1 = v.size();
+    if (p1 == p0 || !isdigit((unsigned char)v[p0])) die("--devices wants `all` or a comma-separated list of device numbers");
+    out.push_back(std::stoi(v.substr(p0, p1 - p0)));
+    p0 = p1 + 1;
+  }
+  return out;
+}
+
+// --devices of a command whose table must fit one GPU (`why` says which): `all` and lists are refused, --shard-table likewise
+inline std::vector<int> parse_single_device(const std::string &v, const std::string &cmd, const std::string &why) {
+  if (v == "all" || v.find(',') != std::string::npos) die(cmd + " takes one device: " + why);
+  return parse_device_list(v);
+}
+[[noreturn]] inline void refuse_shard_table(const std::string &cmd, const std::string &why, const std::string &usage) {
+  die("--shard-table is not supported by " + cmd + ": " + why + "\n" + usage);
+}
 
 inline std::ifstream open_input(const std::string &path) {
   std::ifstream f(path);

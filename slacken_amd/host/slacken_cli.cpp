@@ -12,6 +12,7 @@
 #include "coverage.hpp"
 #include "migration.hpp"
 #include "repeated_titles.hpp"
+#include "support.hpp"
 
 using namespace slk_host;
 namespace fs = std::filesystem;
@@ -191,33 +192,6 @@ struct ClassifyOpts {
   int bracken_length = 0;       // --bracken-length (Slacken.scala:220,259): Bracken weights for the dynamic library as well
 };
 
-static std::vector<int> parse_device_list(const std::string &v) {   // --devices: `all` or e.g. 0,1,2,3
-  std::vector<int> out;
-  if (v == "all") {
-    for (int d = 0; d < slk_device_count(); d++) out.push_back(d);
-    if (out.empty()) die("--devices all: no GPU visible");
-    return out;
-  }
-  size_t p0 = 0;
-  while (p0 <= v.size()) {
-    size_t p1 = v.find(',', p0);
-    if (p1 == std::string::npos) p1 = v.size();
-    if (p1 == p0 || !isdigit((unsigned char)v[p0])) die("--devices wants `all` or a comma-separated list of device numbers");
-    out.push_back(std::stoi(v.substr(p0, p1 - p0)));
-    p0 = p1 + 1;
-  }
-  return out;
-}
-
-// --devices of a command whose table must fit one GPU (`why` says which): `all` and lists are refused, --shard-table likewise
-static std::vector<int> parse_single_device(const std::string &v, const std::string &cmd, const std::string &why) {
-  if (v == "all" || v.find(',') != std::string::npos) die(cmd + " takes one device: " + why);
-  return parse_device_list(v);
-}
-[[noreturn]] static void refuse_shard_table(const std::string &cmd, const std::string &why, const std::string &usage) {
-  die("--shard-table is not supported by " + cmd + ": " + why + "\n" + usage);
-}
-
 static void refuse_wide(const char *cmd, const IndexParams &ip) {
   if (ip.m > 32) die(std::string(cmd) + " supports minimizers of up to 32 nt (this library has m=" + std::to_string(ip.m) + ")");
 }
@@ -251,7 +225,7 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
       if (o.bracken_length < 1) die("--bracken-length must be a positive number of bases");
     }
     else if (two_step && a == "--index-reports")
-      die(a.opt + " is not supported by this engine (index reports are outside the classify path)");
+      die(a.opt + " is not supported by this engine (index reports are outside the classify path: `coverage` and `support` write them)");
     else if (a.opt[0] == '@') { std::ifstream lf(a.opt.substr(1)); std::string l; while (std::getline(lf, l)) if (!trim(l).empty()) o.files.push_back(trim(l)); }
     else if (a.opt[0] == '-') die("unknown option " + a.opt);
     else o.files.push_back(a.opt);
@@ -423,32 +397,14 @@ static std::vector<Taxon> read_gold_set(const Taxonomy &tax, const std::string &
 
 // step 1 of classify2: per-taxon support in the sample (Dynamic.findTaxonSet :213-243), by one of three strategies
 using TaxonSupport = std::map<Taxon, long>;
-// the hits with a true taxon at depth >= rank (minimizersInSubjects :73-86) of all reads: fn(taxon, batch, read, hit)
-template <class Fn>
-static void for_each_ranked_hit(DeviceIndex &base, const ClassifyOpts &o, const Taxonomy &tax, int rank_depth, bool want_spans, Fn fn) {
-  classify_stream(base, o.files, o.paired, o.min_hits, {0.0}, want_spans, true, [&](std::shared_ptr<const ClassifiedBatch> b) {
-    for (size_t i = 0; i < b->frags->size(); i++)
-      for (size_t j = b->hit_offs[i]; j < b->hit_offs[i + 1]; j++) {
-        Taxon t = b->hits[j].taxon;
-        if (t == SLK_TAXON_AMBIGUOUS || t == SLK_TAXON_MATE_PAIR_BORDER || tax.depth(t) < rank_depth) continue;
-        fn(t, *b, i, j);
-      }
-  });
-}
-static TaxonSupport support_by_minimizer_count(DeviceIndex &base, const ClassifyOpts &o, const Taxonomy &tax, int rank_depth) {   // -C: MinimizerTotalCount
+// -C: MinimizerTotalCount, -D: MinimizerDistinctCount -- the hits with a true taxon at depth >= rank (minimizersInSubjects :95-107)
+// grouped by taxon and counted, with repetitions or distinct (:111-117), on the device (support.hpp; one device: the first)
+static TaxonSupport support_by_minimizers(DeviceIndex &base, const ClassifyOpts &o, const Taxonomy &tax, int rank_depth, bool distinct) {
+  note_one_support_device(o.devices);
+  const SupportCounts c = support_pass(base, tax, o.files, o.paired, rank_depth, distinct);
+  std::cerr << c.sequences << " sequences" << std::endl;
   TaxonSupport m;
-  for_each_ranked_hit(base, o, tax, rank_depth, false, [&](Taxon t, const ClassifiedBatch &, size_t, size_t) { m[t] += 1; });
-  return m;
-}
-static TaxonSupport support_by_distinct_minimizers(DeviceIndex &base, const ClassifyOpts &o, const Taxonomy &tax, int rank_depth) {   // -D: MinimizerDistinctCount
-  std::vector<std::pair<Taxon, int64_t>> pairs;
-  for_each_ranked_hit(base, o, tax, rank_depth, true, [&](Taxon t, const ClassifiedBatch &b, size_t i, size_t j) {
-    pairs.emplace_back(t, b.spans[b.span_offs[i] + (j - b.hit_offs[i])].key);
-  });
-  std::sort(pairs.begin(), pairs.end());
-  pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
-  TaxonSupport m;
-  for (auto &pr : pairs) m[pr.first] += 1;
+  for (const SupportRow &r : c.rows) m[r.taxon] = (long)(distinct ? r.distinct : r.minimizers);
   return m;
 }
 // -R: ClassifiedReadCount(threshold, confidence): classified reads per taxon (classifiedReadsPerTaxon :133-141).  That count goes
@@ -510,8 +466,8 @@ static std::vector<std::pair<Taxon, long>> detect_taxon_support(TwoStep &s) {
   }
   TaxonSupport m;
   if (s.with_gold) {}   // (no detection pass)
-  else if (o.min_count >= 0) m = support_by_minimizer_count(base, o, s.tax, s.rank_depth);
-  else if (o.min_distinct >= 0) m = support_by_distinct_minimizers(base, o, s.tax, s.rank_depth);
+  else if (o.min_count >= 0) m = support_by_minimizers(base, o, s.tax, s.rank_depth, false);
+  else if (o.min_distinct >= 0) m = support_by_minimizers(base, o, s.tax, s.rank_depth, true);
   else m = support_by_classified_reads(base, o);
   return std::vector<std::pair<Taxon, long>>(m.begin(), m.end());
 }
@@ -1148,6 +1104,30 @@ static int cmd_coverage(int argc, char **argv) {
   return coverage_run(o, [&](auto fn) { for_each_labelled_sequence(o.library, labels, fn); });
 }
 
+// ---- support: the sample support reports of Dynamic.reportDynamicIndexSupport (S/slacken/Dynamic.scala:210-228), behind a command of
+// its own as `coverage` is; `classify2 --index-reports` stays refused.  The two coverage files of that method are `coverage`'s.
+static int cmd_support(int argc, char **argv) {
+  SupportOptions o = parse_support_options(argc, argv);
+  const IndexParams ip = read_index_params(o.index);
+  refuse_wide("support", ip);
+  if (ip.k - ip.m + 1 > BUILD_MAX_WINDOW)
+    die("support supports windows of up to " + std::to_string(BUILD_MAX_WINDOW) + " m-mers (k - m + 1 = " + std::to_string(ip.k - ip.m + 1) + ")");
+  note_one_support_device(o.devices);
+  o.devices.resize(1);
+  const double t0 = wall_seconds();
+  LoadedIndex lib(o.index, o.devices);
+  const SupportCounts c = support_pass(lib.dev, lib.tax, o.files, o.paired, o.rank_depth, true);
+  // Classifier.classify(subjects, cpar, 0.0) grouped by taxon (multiStatsPerTaxon :160-162): the detection pass of classify2 -R at
+  // confidence 0, titles regrouped
+  ClassifyOpts co;
+  co.files = o.files; co.paired = o.paired; co.min_hits = o.min_hits; co.init_confidence = 0.0;
+  const TaxonSupport classified = support_by_classified_reads(lib.dev, co);
+  write_support_files(lib.tax, c.rows, std::vector<std::pair<Taxon, long>>(classified.begin(), classified.end()), o.output);
+  std::cout << "support: " << c.sequences << " sequences, " << c.supermers << " super-mers, " << c.matched << " matched, " << c.kept << " at rank "
+            << o.rank << " or below, " << c.rows.size() << " taxa, " << wall_seconds() - t0 << " s" << std::endl;
+  return 0;
+}
+
 // coverage-report TAXONOMY_DIR COUNTS_TSV SIZES_TSV ROWS_TSV OUTPUT: the three files `coverage` writes, from "taxon \t records",
 // "source \t k-mers" and "source \t depth \t all \t distinct" lines (host only: the outputs without a GPU)
 static int cmd_coverage_report(int argc, char **argv) {
@@ -1262,6 +1242,13 @@ static const char *HELP =
     "  library stores for them; OUTPUT_min_report.txt: the Kraken report of `inspect` with the columns TKC1-LeafOnly, TKC2-FirstChildren and\n"
     "  TKC3-AllChildren (average k-mers per genome).  A library with more super-mers than the GPU's memory takes at once is counted in\n"
     "  groups of source taxa, one pass over LIBRARY_DIR each\n"
+    "  slacken-amd support -i INDEX -o OUTPUT [--rank RANK (species)] [--min-hits N] [-p] [--devices D] FILES... (Dynamic.scala:152-180,\n"
+    "  210-228; the sample support reports of the reference's `classify2 --index-reports`): every super-mer of every read (FILES as for\n"
+    "  classify, ambiguous regions kept) is looked up on the GPU, the hits whose taxon lies at RANK or below are grouped by taxon, and\n"
+    "  four Kraken reports are written: OUTPUT_support_report_totalKmerCount.txt (k-mers of the hit super-mers),\n"
+    "  OUTPUT_support_report_totalMinimizerCount.txt (hit super-mers), OUTPUT_support_report_distinctMinimizerCount.txt (different\n"
+    "  minimizers among them) and OUTPUT_support_report_classifiedReadCount.txt (reads classified at confidence 0, --min-hits as for\n"
+    "  classify).  The counts are taken on one device, the first of --devices; the two coverage files are written by `coverage`\n"
     "host-only helpers: copy-records -i INDEX -o OUTPUT [--format parquet|slkrec] (a library rewritten by the library writer) |\n"
     "  report TAXONOMY_DIR COUNTS_TSV | kmer-distrib TRIPLES_TSV (dest source count) |\n"
     "  stats-report TAXONOMY_DIR COUNTS_TSV (taxon count) M [--histogram] [-o OUTPUT [--labels FILE]] |\n"
@@ -1283,7 +1270,7 @@ int main(int argc, char **argv) {
     if (i + 1 < argc) g_partitions = atoi(argv[i + 1]);
     i += 2;
   }
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|bracken-build|compare-index|respace|coverage|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|bracken-build|compare-index|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1293,7 +1280,7 @@ int main(int argc, char **argv) {
       {"bracken-build", cmd_bracken_build}, {"kmer-distrib", cmd_kmer_distrib}, {"compare-index", cmd_compare_index},
       {"compareIndex", cmd_compare_index}, {"migration-report", cmd_migration_report}, {"stats", cmd_stats}, {"inspect", cmd_inspect},
       {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build},
-      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}};
+      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}, {"support", cmd_support}};
   // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
   //  they were commands)
   const bool bare = (cmd == "stats" || cmd == "inspect") && i >= argc;
@@ -1303,6 +1290,6 @@ int main(int argc, char **argv) {
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `bracken-build`, `compare-index`, `respace`, `coverage`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `bracken-build`, `compare-index`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }
