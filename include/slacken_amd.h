@@ -321,6 +321,53 @@ int32_t slk_classify_batch_packed(slk_index *ix, slk_stream *st, const uint32_t 
                                   uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity);
 int32_t slk_pack_bases(const uint8_t *bases, uint64_t n, uint32_t *codes, uint16_t *valid);
 
+/* ---- FASTA / FASTQ text parsed on the device: replaces FastaTextInput and FastqTextInput (S/kmers/input/FileInputs.scala:155-183,
+ * 188-221) -- the records of a text as the layout the classify entry points take (bases without whitespace, offsets[R+1]) plus
+ * where every record's title lies in the text.  Per byte:
+ *   FASTQ  a line ends at \n, \r\n or a lone \r; a last line without a terminator is a line, the empty piece after the last
+ *          terminator is not.  Line i starts a record iff its first byte is '@', line i+2 exists and its first byte is '+' (the
+ *          window slides by ONE line, :204-221); the sequence is line i+1 verbatim, the title line i after the '@' up to the first
+ *          space.
+ *   FASTA  the text is cut at every '>' (:166); the title is what precedes the piece's first \n or \r, up to the first space; the
+ *          sequence every later byte of the piece that is neither \n nor \r; a piece is a record iff its sequence is not empty.
+ *   final = 0  the text is a chunk of a longer one: a FASTQ line counts only when its terminator lies inside the chunk (a \r on
+ *          the last byte is undecided) and a record only when lines i, i+1 and i+2 are all there; a FASTA record only when the '>'
+ *          that ends it is inside the chunk.  consumed = the first byte that no taken record or skipped line owns (FASTQ: the start
+ *          of the first line whose window could not be decided; FASTA: the '>' that opens the first record not taken, 0 if the chunk
+ *          holds none): the caller puts text[consumed, n) in front of the next chunk, and any sequence of such calls, the last one
+ *          with final = 1, yields the records of the whole text in order.  consumed == 0 on a non-final chunk: the chunk must grow.
+ * Limits: n < 2^32 per call (SLK_E_INVALID beyond); single-end.  title_pos[r] is a position in `text` (FASTQ: behind the '@'),
+ * title_len[r] the bytes of the title.  The counts record is four uint64: records, bases, consumed, overflow.
+ *   slk_parse_device  every pointer on the stream's device, d_text aligned to 16 bytes, nothing past text[n) is read; asynchronous
+ *                     on st.  d_offsets holds records_capacity + 1 entries.  More records than records_capacity or more bases than
+ *                     bases_capacity: overflow = 1, records and bases say what was needed, consumed = 0, and none of the output
+ *                     arrays is written.  Scratch is the stream's, sized from n (FASTQ 8 bytes per byte of text, FASTA 20 bytes per
+ *                     4 KiB) -- no other allocation.
+ *   slk_parse_text    the same from and to host memory, synchronous: the parser alone.  Overflow is SLK_E_CAPACITY, with
+ *                     *out_records and *out_n_bases what the capacities would have to be.
+ *   slk_classify_text uploads the text, parses it on the device and classifies the records where they lie, as
+ *                     slk_classify_batch_device would: what slk_classify_batch returns for the parsed reads (out_taxon and
+ *                     out_classified are [C * *out_records], threshold-major with stride *out_records; hit lists follow
+ *                     slk_stream_set_merged_hits) plus out_offsets[R+1] and the titles' positions.  Every per-record array holds
+ *                     records_capacity entries (out_offsets and out_hit_offsets one more); more records is SLK_E_CAPACITY with
+ *                     *out_records the number needed.  Synchronous on every return, as slk_classify_batch.  One id column only
+ *                     (SLK_E_UNSUPPORTED otherwise).
+ *   slk_parse_tile_bytes  the bytes of text one workgroup takes at a time (tests place record borders on its multiples). */
+#define SLK_FORMAT_FASTA 0
+#define SLK_FORMAT_FASTQ 1
+uint32_t slk_parse_tile_bytes(void);
+int32_t slk_parse_device(slk_stream *st, const uint8_t *d_text, uint64_t n, int32_t format, int32_t final, uint8_t *d_bases,
+                         uint64_t bases_capacity, uint64_t *d_offsets, uint64_t *d_title_pos, uint32_t *d_title_len,
+                         uint64_t records_capacity, uint64_t *d_counts);
+int32_t slk_parse_text(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, int32_t final, uint8_t *out_bases,
+                       uint64_t *out_offsets, uint64_t *out_title_pos, uint32_t *out_title_len, uint64_t bases_capacity,
+                       uint64_t records_capacity, uint64_t *out_records, uint64_t *out_n_bases, uint64_t *out_consumed);
+int32_t slk_classify_text(slk_index *ix, slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, int32_t final,
+                          int32_t min_hit_groups, const double *thresholds, int32_t C, int32_t *out_taxon, uint8_t *out_classified,
+                          int32_t *out_num_distinct, int32_t *out_total_kmers, uint64_t *out_offsets, uint64_t *out_title_pos,
+                          uint32_t *out_title_len, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t records_capacity,
+                          uint64_t hits_capacity, uint64_t *out_records, uint64_t *out_consumed);
+
 /* ---- kernel-3-only entry: Classifier.classify (object, S/slacken/Classifier.scala:439-454) on hit lists the caller holds
  * (host pointers; synchronous): TaxonCounts.toMap/totalKmers + resolveTree + the minHitGroups test for R lists of un-merged
  * hits in ordinal order.  This is what the host uses to reproduce the reference's regrouping by TITLE

@@ -83,7 +83,24 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy",
            "slk_coverage_create", "slk_coverage_add", "slk_coverage_fold", "slk_coverage_result", "slk_coverage_totals", "slk_coverage_budget",
            "slk_coverage_destroy",
-           "slk_support_create", "slk_support_add", "slk_support_result", "slk_support_totals", "slk_support_destroy"]
+           "slk_support_create", "slk_support_add", "slk_support_result", "slk_support_totals", "slk_support_destroy",
+           "slk_parse_tile_bytes", "slk_parse_device", "slk_parse_text", "slk_classify_text"]
+
+FORMAT_FASTA, FORMAT_FASTQ = 0, 1   # SLK_FORMAT_* of the header
+
+
+def _format(fmt):
+    if fmt in (FORMAT_FASTA, FORMAT_FASTQ):
+        return int(fmt)
+    try:
+        return {"fasta": FORMAT_FASTA, "fa": FORMAT_FASTA, "fastq": FORMAT_FASTQ, "fq": FORMAT_FASTQ}[str(fmt).lower()]
+    except KeyError:
+        raise ValueError(f"format {fmt!r}: 'fasta' or 'fastq'") from None
+
+
+def parse_tile_bytes():
+    """The bytes of text one workgroup of the device parser takes at a time (slk_parse_tile_bytes)"""
+    return int(lib().slk_parse_tile_bytes())
 
 
 def lib_path():
@@ -193,6 +210,14 @@ def lib():
     L.slk_support_totals.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 4
     L.slk_support_destroy.argtypes = [vp]
     L.slk_support_destroy.restype = None
+    L.slk_parse_tile_bytes.argtypes = []
+    L.slk_parse_tile_bytes.restype = C.c_uint32
+    L.slk_parse_device.argtypes = [vp, u8p, C.c_uint64, C.c_int32, C.c_int32, u8p, C.c_uint64, u64p, u64p, vp, C.c_uint64, u64p]
+    L.slk_parse_text.argtypes = [vp, u8p, C.c_uint64, C.c_int32, C.c_int32, u8p, u64p, u64p, vp, C.c_uint64, C.c_uint64,
+                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.slk_classify_text.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, i32p, u8p,
+                                    i32p, i32p, u64p, u64p, vp, u64p, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -818,6 +843,72 @@ class Stream:
             out["num_hits"] = np.diff(hit_off.astype(np.int64)).astype(np.int32)
         elif with_num_hits:
             out["num_hits"] = np.diff(hit_off.astype(np.int64)).astype(np.int32)
+        return out
+
+    def parse_text_raw(self, data, fmt, final=True, bases_capacity=None, records_capacity=None, guard=0):
+        """slk_parse_text as it stands: -> dict(bases, offsets, title_pos, title_len, R, n_bases, consumed).  The output arrays are
+        allocated with `guard` extra elements behind the capacities, filled with 0xA5 bytes, and returned whole under the keys
+        raw_*: what the call must not touch."""
+        data = np.frombuffer(bytes(data), np.uint8) if not isinstance(data, np.ndarray) else _np(data, np.uint8)
+        n = data.size
+        bcap = n if bases_capacity is None else int(bases_capacity)
+        rcap = n // 2 + 2 if records_capacity is None else int(records_capacity)
+        bases = np.full(bcap + guard, 0xA5, np.uint8)
+        offsets = np.full(rcap + 1 + guard, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        tpos = np.full(rcap + guard, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        tlen = np.full(rcap + guard, 0xA5A5A5A5, np.uint32)
+        R, nb, consumed = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        rc = lib().slk_parse_text(self.h, _ptr(data), n, _format(fmt), 1 if final else 0, _ptr(bases), _ptr(offsets), _ptr(tpos), _ptr(tlen),
+                                  bcap, rcap, C.byref(R), C.byref(nb), C.byref(consumed))
+        out = dict(raw_bases=bases, raw_offsets=offsets, raw_title_pos=tpos, raw_title_len=tlen, R=int(R.value), n_bases=int(nb.value),
+                   consumed=int(consumed.value), bases_capacity=bcap, records_capacity=rcap)
+        if rc != 0:
+            err = SlackenError(rc, lib().slk_last_error().decode())
+            err.partial = out
+            raise err
+        out.update(bases=bases[:out["n_bases"]], offsets=offsets[:out["R"] + 1], title_pos=tpos[:out["R"]], title_len=tlen[:out["R"]])
+        return out
+
+    def parse_text(self, data, fmt, final=True):
+        """FASTA / FASTQ text (bytes) parsed on the device (slk_parse_text) -> (titles, seqs, consumed): two lists of str, and where the
+        caller's next chunk starts (len(data) when final)."""
+        data = bytes(data)
+        o = self.parse_text_raw(data, fmt, final)
+        off = o["offsets"]
+        seqs = [o["bases"][int(off[r]):int(off[r + 1])].tobytes().decode("latin-1") for r in range(o["R"])]
+        titles = [data[int(p):int(p) + int(l)].decode("latin-1") for p, l in zip(o["title_pos"], o["title_len"])]
+        return titles, seqs, o["consumed"]
+
+    def classify_text(self, data, fmt, final=True, min_hit_groups=2, thresholds=(0.0,), with_hits=True, records_capacity=None,
+                      hits_capacity=None):
+        """classify_batch on the records of a FASTA / FASTQ text that is parsed on the device (slk_classify_text): the result dict of
+        classify_batch plus offsets [R+1], title_pos, title_len, titles (list of str), R and consumed."""
+        data = bytes(data)
+        text = np.frombuffer(data, np.uint8)
+        n = text.size
+        rcap = n // 2 + 2 if records_capacity is None else int(records_capacity)
+        Cn = len(thresholds)
+        thr = (C.c_double * Cn)(*thresholds)
+        taxon, cls = np.zeros(Cn * rcap, np.int32), np.zeros(Cn * rcap, np.uint8)
+        nd, tk = np.zeros(rcap, np.int32), np.zeros(rcap, np.int32)
+        offsets, tpos, tlen = np.zeros(rcap + 1, np.uint64), np.zeros(rcap, np.uint64), np.zeros(rcap, np.uint32)
+        hit_off = hits = None
+        cap = 0
+        if with_hits:
+            cap = hits_capacity if hits_capacity is not None else n + 1
+            hit_off, hits = np.zeros(rcap + 1, np.uint64), np.zeros(cap, HIT_DTYPE)
+        R, consumed = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().slk_classify_text(self.index.h, self.h, _ptr(text), n, _format(fmt), 1 if final else 0, min_hit_groups, thr, Cn,
+                                       _ptr(taxon), _ptr(cls), _ptr(nd), _ptr(tk), _ptr(offsets), _ptr(tpos), _ptr(tlen), _ptr(hit_off),
+                                       _ptr(hits), rcap, cap, C.byref(R), C.byref(consumed)))
+        R = int(R.value)
+        out = dict(taxon=taxon[:Cn * R].reshape(Cn, R), classified=cls[:Cn * R].reshape(Cn, R), num_distinct=nd[:R], total_kmers=tk[:R],
+                   offsets=offsets[:R + 1], title_pos=tpos[:R], title_len=tlen[:R], R=R, consumed=int(consumed.value))
+        out["titles"] = [data[int(p):int(p) + int(l)].decode("latin-1") for p, l in zip(out["title_pos"], out["title_len"])]
+        if with_hits:
+            out["hit_offsets"] = hit_off[:R + 1]
+            out["hits"] = hits[:int(hit_off[R])]
+            out["num_hits"] = np.diff(hit_off[:R + 1].astype(np.int64)).astype(np.int32)
         return out
 
     def classify_hits(self, hit_offsets, hits, distinct=None, min_hit_groups=2, thresholds=(0.0,)):

@@ -986,3 +986,61 @@ int32_t slk_classify_batch_packed(slk_index *ix, slk_stream *st, const uint32_t 
   return classify_batch_host(ix, st, src, offsets, mate_offsets, R, min_hit_groups, thresholds, C, out_taxon, out_classified, out_num_distinct,
                              out_total_kmers, out_hit_offsets, out_hits, hits_capacity);
 }
+
+// slk_classify_batch with the reads still FASTA / FASTQ text: the text goes up as it is, textparse.hip finds the records and leaves
+// them in the stream's read buffers in the layout the kernels take, and the batch goes the way of slk_classify_batch_device from
+// there.  What comes back beside the results is where every record's sequence and title lie.
+int32_t slk_classify_text(slk_index *ix, slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, int32_t final,
+                          int32_t min_hit_groups, const double *thresholds, int32_t C, int32_t *out_taxon, uint8_t *out_classified,
+                          int32_t *out_num_distinct, int32_t *out_total_kmers, uint64_t *out_offsets, uint64_t *out_title_pos,
+                          uint32_t *out_title_len, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t records_capacity,
+                          uint64_t hits_capacity, uint64_t *out_records, uint64_t *out_consumed) {
+  int32_t rc = check_ready(ix, st, true);
+  if (rc) return rc;
+  if (!out_records || !out_consumed || !out_offsets || (n && !text) ||
+      (records_capacity && (!out_taxon || !out_classified || !out_title_pos || !out_title_len)))
+    return fail(SLK_E_INVALID, "null argument");
+  *out_records = *out_consumed = 0;
+  if ((rc = check_thresholds(thresholds, C))) return rc;
+  if ((rc = check_parse_args(n, format))) return rc;
+  if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "slk_classify_text supports minimizers of up to 32 nt (one id column)");
+  rc = set_device(ix);
+  if (rc) return rc;
+  out_offsets[0] = 0;
+  if (out_hit_offsets) out_hit_offsets[0] = 0;
+  DrainOnExit drain(st);
+  uint64_t counts[4] = {0, 0, 0, 0};
+  rc = parse_uploaded(st, text, n, format, final != 0, n, records_capacity, counts);   // (the sequences are fewer bytes than the text)
+  const uint64_t R = counts[0], total = counts[1];
+  *out_records = R;   // (with SLK_E_CAPACITY too: the records_capacity the text needs)
+  if (rc) return rc;
+  *out_consumed = counts[2];
+  if (R == 0) return SLK_OK;
+  rc = copy_out(st, out_offsets, st->offsets.p, (R + 1) * 8);
+  if (!rc) rc = copy_out(st, out_title_pos, st->parse_title_pos.p, R * 8);
+  if (!rc) rc = copy_out(st, out_title_len, st->parse_title_len.p, R * 4);
+  if (!rc) rc = validate_reads(out_offsets, nullptr, R);
+  if (!rc) rc = ensure_outputs(st, R, C);
+  if (rc) return rc;
+  const bool want_hits = out_hit_offsets != nullptr && out_hits != nullptr;
+  ClassifyCall whole;
+  whole.in = {st->bases.as<uint8_t>(), st->offsets.as<uint64_t>(), nullptr, nullptr, R, total, 0};
+  whole.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
+               st->out_nh.as<int32_t>(), nullptr, R};
+  whole.thr = thresholds_of(thresholds, C); whole.C = C; whole.min_hit_groups = min_hit_groups; whole.want_hits = want_hits;
+  st->reran = false;
+  rc = run_classify(ix, st, whole);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(st->s));
+  rc = check_status(st);  // (re-runs the batch through the unbounded path if a taxon map overflowed)
+  if (rc) return rc;
+  rc = download_rows(st, HostRows{out_taxon, out_classified, out_num_distinct, out_total_kmers}, R, C);
+  if (rc) return rc;
+  if (out_hit_offsets) {
+    double th[3] = {0, 0, 0};
+    rc = assemble_hits(st, whole.in, want_hits, out_hit_offsets, out_hits, hits_capacity, false, th);
+    if (rc) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st->s));
+  return check_status(st);
+}

@@ -294,7 +294,8 @@ struct slk_stream {
   bool merged_hits = false;                 // slk_stream_set_merged_hits: hit lists as TaxonCounts.fromHits merges them
   DevBuf pk_codes, pk_valid, pk_mate_codes, pk_mate_valid;   // slk_classify_batch_packed: the reads as they arrive (3 bits per base)
   Event ev_unpack;
-  Stream s2;                                // the segment pass and the wave pass run here, beside the long-lane pass on s
+  DevBuf parse_text, parse_scratch, parse_title_pos, parse_title_len, parse_counts;   // textparse.hip: the raw text, the passes' scratch, what comes back beside bases / offsets
+  Stream s2;                               // the segment pass and the wave pass run here, beside the long-lane pass on s
   Event ev_fork, ev_join;
   DevPtr<int32_t> d_status;        // device error bits of the fused kernels
   PinnedPtr<int32_t> h_status;     // pinned copy, refreshed after every classify launch
@@ -433,6 +434,10 @@ Thresholds thresholds_of(const double *v, int32_t C);
 int32_t ensure_outputs(slk_stream *st, uint64_t R, int32_t C);   // the stream's result rows (out_taxon .. out_nh) for R fragments
 struct HostRows { int32_t *taxon; uint8_t *classified; int32_t *nd, *tk; };   // a host call's results in the caller's memory (nullable from nd on)
 int32_t download_rows(slk_stream *st, const HostRows &out, uint64_t R, int32_t C);   // complete on return
+// textparse.hip: FASTA / FASTQ text parsed on the device (used by classify.hip: slk_classify_text)
+int32_t check_parse_args(uint64_t n, int32_t format);
+int32_t parse_uploaded(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, bool final, uint64_t bases_capacity,
+                       uint64_t records_capacity, uint64_t counts[4]);
 
 inline int ceil_log2_u64(uint64_t x) {
   int b = 0;

@@ -1,0 +1,519 @@
+// textparse.hip -- FASTA / FASTQ text parsed on the device: the record rules of FastaTextInput and FastqTextInput
+// (S/kmers/input/FileInputs.scala:155-221), which host/seqio.hpp applies byte by byte on the CPU, as byte classification, scans and
+// scatters over the raw text.  Both rules are local (seqio.hpp: PlainSegmentParser), so every byte can decide its own fate from a few
+// prefix quantities:
+//   FASTQ   a line starts at 0 and after every \n, \r\n or lone \r.  Line j starts a record iff its first byte is '@', line j + 2
+//           exists and its first byte is '+'; the sequence is line j + 1 verbatim, the title line j after the '@' up to the first space.
+//   FASTA   the text is cut at every '>'.  Per byte: g = the last '>' at or before it, t = the last \n or \r at or before it; a byte
+//           that is none of the three is KEPT (a nucleotide) iff t > g.  A piece is a record iff a byte of it is kept; the title is
+//           what follows its '>' up to the first \n, \r or space.
+// Chunks (final = 0): a FASTQ line counts only with its terminator inside the chunk (a \r on the last byte is undecided), a record
+// only with lines j .. j + 2 present; a FASTA record only when the '>' that ends it is inside the chunk.  `consumed` is where the
+// caller's next chunk starts.
+//
+// Layout.  A TILE is TP_TILE = 4096 bytes: a block of 256 lanes, 16 bytes per lane in one load (the text must be 16-byte aligned; the
+// bytes past n are never read: a lane whose 16 bytes cross n assembles them from byte loads).  Inside a block, ranks are wave scans
+// (shuffles; ballots and mbcnt where a lane holds one flag) and four wave totals in LDS.  Across blocks every quantity takes the
+// count / scan / scatter shape of export.hip: a pass leaves one number per tile, one block scans the tiles' numbers, the next pass
+// reads its tile's carry.  No block waits for another inside a kernel.
+//   FASTQ   lines<0> counts the tiles' line starts | scan | lines<1> writes the line starts S[] | records<0> flags the record lines
+//           (one lane per line: the first bytes of lines j and j + 2) and sums records and sequence bytes per 256 lines | scan |
+//           records<1> writes offsets, titles and where every line's bytes go | copy: every byte finds its line and moves itself.
+//   FASTA   stage 0 leaves the tiles' last '>' and last terminator | max-scan | stage 1 the tiles' kept bytes | scan | stage 2 the
+//           tiles' records (a '>' -- or the end of the final chunk -- closes a record iff a byte was kept since the '>' before) |
+//           scan | stage 3 moves the kept bytes and writes offsets and titles.
+// A record of any length is spread over as many lanes as it has bytes.  What stays serial is the walk along a TITLE to its first
+// space, one lane per record.
+// Scratch is sized from n alone (FASTQ: 8 bytes per byte of text for the line starts and the lines' destinations, every byte may be
+// a line; FASTA: 20 bytes per tile), kept on the stream and grown like its other buffers.
+#include "hostside.h"
+
+namespace {
+
+constexpr int TP_BLOCK = 256;
+constexpr int TP_LANE_BYTES = 16;
+constexpr uint32_t TP_TILE = TP_BLOCK * TP_LANE_BYTES;
+constexpr int TP_SCAN_BLOCK = 1024;
+constexpr unsigned TP_MAX_GRID = 2048;   // 256 CUs x 8 blocks; the kernels stride over their tiles
+constexpr uint32_t TP_NONE = 0xFFFFFFFFu;
+
+struct TpArgs {
+  const uint8_t *text;
+  uint64_t n;          // bytes of text (< 2^32)
+  uint32_t ntiles;     // tiles of TP_TILE positions (FASTA, final: n + 1 positions -- the end of the text closes a record)
+  uint32_t final;
+  uint32_t *tiles;     // per-tile numbers, arrays of ntiles + 1 (the scan leaves the total behind the last tile's carry)
+  uint32_t *S;         // FASTQ: line starts [M + 2], S[M] = S[M + 1] = n
+  uint32_t *dst;       // FASTQ: [M + 1] where in `bases` line j goes, TP_NONE = nowhere
+  uint32_t *ltiles;    // FASTQ: per 256 lines, two arrays of nlt_max + 1: records, sequence bytes
+  uint32_t nlt_max;
+  uint8_t *bases;
+  uint64_t bases_capacity;
+  uint64_t *offsets;
+  uint64_t *title_pos;
+  uint32_t *title_len;
+  uint64_t records_capacity;
+  uint64_t *counts;    // [4]: records, bases, consumed, overflow
+};
+
+__device__ __forceinline__ uint32_t tp_op(bool mx, uint32_t a, uint32_t b) { return mx ? (a > b ? a : b) : a + b; }
+
+// exclusive prefix of v over the block's 256 lanes (sum, or max with 0 as "nothing"); total = over all of them.  lds: 4 words.
+template <bool MAX>
+__device__ __forceinline__ uint32_t tp_block_excl(uint32_t v, uint32_t *lds, uint32_t &total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc = tp_op(MAX, inc, t);
+  }
+  if (lane == 63) lds[w] = inc;
+  __syncthreads();
+  uint32_t before = 0;
+  total = 0;
+#pragma unroll
+  for (int i = 0; i < TP_BLOCK / 64; i++) {
+    const uint32_t t = lds[i];
+    if (i < w) before = tp_op(MAX, before, t);
+    total = tp_op(MAX, total, t);
+  }
+  __syncthreads();   // (the words are free again)
+  uint32_t excl = __shfl_up(inc, 1, 64);
+  if (lane == 0) excl = 0;
+  return tp_op(MAX, before, excl);
+}
+
+// the lane's 16 positions [p, p + 16) as four words, little-endian; positions at or beyond n read as 0 and are not touched in memory
+__device__ __forceinline__ void tp_load16(const uint8_t *text, uint64_t n, uint64_t p, uint32_t (&w)[4]) {
+  if (p + TP_LANE_BYTES <= n) {
+    const uint4 v = *(const uint4 *)(text + p);
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  } else {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    for (int k = 0; k < TP_LANE_BYTES; k++)
+      if (p + k < n) w[k >> 2] |= (uint32_t)text[p + k] << ((k & 3) * 8);
+  }
+}
+__device__ __forceinline__ uint32_t tp_byte(const uint32_t (&w)[4], int k) { return (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu; }
+__device__ __forceinline__ uint32_t tp_below(uint32_t mask, int k) { return mask & ((1u << k) - 1u); }
+__device__ __forceinline__ int tp_top(uint32_t mask) { return 31 - __clz((int)mask); }   // mask != 0
+
+// per-tile arrays, scanned in place by one block each: v[i] = what tiles 0 .. i - 1 hold, v[count] = what all hold.  The count is
+// given, or ceil(*m_dev / div) where only the device knows it; bit a of max_mask: array a is a max-scan, else a sum.
+__global__ void __launch_bounds__(TP_SCAN_BLOCK) tp_scan_kernel(uint32_t *base, uint64_t stride, uint32_t count, const uint32_t *m_dev,
+                                                                uint32_t div, uint32_t max_mask) {
+  __shared__ uint32_t part[TP_SCAN_BLOCK];
+  uint32_t *v = base + (uint64_t)blockIdx.x * stride;
+  const bool mx = (max_mask >> blockIdx.x) & 1u;
+  const uint64_t n = m_dev ? ((uint64_t)*m_dev + div - 1) / div : count;
+  const uint64_t per = (n + TP_SCAN_BLOCK - 1) / TP_SCAN_BLOCK;
+  const uint64_t a = umin64(n, threadIdx.x * per), b = umin64(n, a + per);
+  uint32_t acc = 0;
+  for (uint64_t g = a; g < b; g++) acc = tp_op(mx, acc, v[g]);
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int o = 1; o < TP_SCAN_BLOCK; o <<= 1) {
+    const uint32_t add = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+    __syncthreads();
+    part[threadIdx.x] = tp_op(mx, part[threadIdx.x], add);
+    __syncthreads();
+  }
+  uint32_t run = threadIdx.x ? part[threadIdx.x - 1] : 0;
+  for (uint64_t g = a; g < b; g++) {
+    const uint32_t x = v[g];
+    v[g] = run;
+    run = tp_op(mx, run, x);
+  }
+  if (threadIdx.x == TP_SCAN_BLOCK - 1) v[n] = part[TP_SCAN_BLOCK - 1];
+}
+
+// ---- FASTQ --------------------------------------------------------------------------------------------------------------------
+
+// bit k: position p + k (< n) starts a line -- seqio.hpp: is_line_start
+__device__ __forceinline__ uint32_t fq_start_mask(const TpArgs &A, uint64_t p, const uint32_t (&w)[4]) {
+  if (p >= A.n) return 0;
+  uint32_t prev = p ? A.text[p - 1] : '\n';
+  uint32_t mask = 0;
+#pragma unroll
+  for (int k = 0; k < TP_LANE_BYTES; k++) {
+    const uint32_t c = tp_byte(w, k);
+    if (p + k < A.n && (prev == '\n' || (prev == '\r' && c != '\n'))) mask |= 1u << k;
+    prev = c;
+  }
+  return mask;
+}
+
+// WRITE = 0: tiles[t] = the line starts of tile t.  WRITE = 1 (tiles scanned): S[] = their positions, in order.
+template <int WRITE>
+__global__ void __launch_bounds__(TP_BLOCK) fq_lines_kernel(TpArgs A) {
+  __shared__ uint32_t lds[TP_BLOCK / 64];
+  for (uint32_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
+    const uint64_t p = (uint64_t)t * TP_TILE + threadIdx.x * TP_LANE_BYTES;
+    uint32_t w[4];
+    tp_load16(A.text, A.n, p, w);
+    const uint32_t mask = fq_start_mask(A, p, w);
+    uint32_t total;
+    const uint32_t excl = tp_block_excl<false>(__popc(mask), lds, total);
+    if (!WRITE) {
+      if (threadIdx.x == 0) A.tiles[t] = total;
+    } else {
+      uint32_t j = A.tiles[t] + excl;
+      for (uint32_t m = mask; m; m &= m - 1) A.S[j++] = (uint32_t)(p + (__ffs((int)m) - 1));
+      if (t == 0 && threadIdx.x == 0) {
+        const uint32_t M = A.tiles[A.ntiles];
+        A.S[M] = (uint32_t)A.n;
+        A.S[M + 1] = (uint32_t)A.n;
+      }
+    }
+  }
+}
+
+// the end of the line [s, next) without its terminator (\n, \r\n, \r or, on the last line of the text, none)
+__device__ __forceinline__ uint32_t fq_line_end(const uint8_t *text, uint32_t s, uint32_t next) {
+  uint32_t e = next;
+  if (e > s && text[e - 1] == '\n') {
+    e--;
+    if (e > s && text[e - 1] == '\r') e--;
+  } else if (e > s && text[e - 1] == '\r') {
+    e--;
+  }
+  return e;
+}
+
+// One lane per line.  WRITE = 0: the records and sequence bytes of every 256 lines.  WRITE = 1 (those scanned): offsets, titles, the
+// lines' destinations and the counts record.
+template <int WRITE>
+__global__ void __launch_bounds__(TP_BLOCK) fq_records_kernel(TpArgs A) {
+  __shared__ uint32_t lds[TP_BLOCK / 64];
+  const uint32_t M = A.tiles[A.ntiles];   // lines that start inside the text (>= 1: n > 0)
+  // lines that are PRESENT: all of a final chunk; otherwise those whose terminator is inside and decided
+  const uint32_t Lp = A.final ? M : (A.text[A.n - 1] == '\n' ? M : M - 1);
+  const uint32_t nlt = (M + TP_BLOCK - 1) / TP_BLOCK;
+  uint32_t *lt_rec = A.ltiles, *lt_bases = A.ltiles + (A.nlt_max + 1);
+  bool over = false;
+  if (WRITE) over = lt_rec[nlt] > A.records_capacity || lt_bases[nlt] > A.bases_capacity;
+  for (uint32_t lt = blockIdx.x; lt < nlt; lt += gridDim.x) {
+    const uint64_t j = (uint64_t)lt * TP_BLOCK + threadIdx.x;
+    bool rec = false;
+    uint32_t s0 = 0, s1 = 0, len = 0;
+    if (j + 2 < Lp) {
+      s0 = A.S[j];
+      const uint32_t s2 = A.S[j + 2];
+      if (A.text[s0] == '@' && A.text[s2] == '+') {
+        rec = true;
+        s1 = A.S[j + 1];
+        len = fq_line_end(A.text, s1, s2) - s1;
+      }
+    }
+    // a lane holds one flag: its rank in the wave is a ballot and mbcnt; the waves' totals pass through LDS
+    const unsigned long long ballot = __ballot(rec);
+    const uint32_t rank_w = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    uint32_t rank = rank_w, rec_total = 0;
+#pragma unroll
+    for (int i = 0; i < TP_BLOCK / 64; i++) {
+      if (i < (int)(threadIdx.x >> 6)) rank += lds[i];
+      rec_total += lds[i];
+    }
+    __syncthreads();
+    uint32_t len_total;
+    const uint32_t len_excl = tp_block_excl<false>(len, lds, len_total);
+    if (!WRITE) {
+      if (threadIdx.x == 0) { lt_rec[lt] = rec_total; lt_bases[lt] = len_total; }
+      continue;
+    }
+    const uint32_t r = lt_rec[lt] + rank, d = lt_bases[lt] + len_excl;
+    if (j < M) A.dst[j + 1] = rec && !over ? d : TP_NONE;   // (line j + 1 is the sequence of the record line j starts)
+    if (j == 0) A.dst[0] = TP_NONE;
+    if (rec && !over) {
+      const uint32_t e0 = fq_line_end(A.text, s0, s1);
+      uint32_t q = s0 + 1;
+      while (q < e0 && A.text[q] != ' ') q++;
+      A.offsets[r] = d;
+      A.title_pos[r] = (uint64_t)s0 + 1;
+      A.title_len[r] = q - (s0 + 1);
+    }
+  }
+  if (WRITE && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (!over) A.offsets[lt_rec[nlt]] = lt_bases[nlt];
+    A.counts[0] = lt_rec[nlt];
+    A.counts[1] = lt_bases[nlt];
+    // the first line whose window could not be decided: the last but one that is present
+    A.counts[2] = over ? 0 : A.final ? A.n : (Lp >= 2 ? A.S[Lp - 2] : 0);
+    A.counts[3] = over ? 1 : 0;
+  }
+}
+
+// every byte of a sequence line to its place in `bases`: the byte's line is the rank of the last line start at or before it
+__global__ void __launch_bounds__(TP_BLOCK) fq_copy_kernel(TpArgs A) {
+  __shared__ uint32_t lds[TP_BLOCK / 64];
+  const uint32_t M = A.tiles[A.ntiles];
+  const uint32_t nlt = (M + TP_BLOCK - 1) / TP_BLOCK;
+  if (A.ltiles[nlt] > A.records_capacity || A.ltiles[A.nlt_max + 1 + nlt] > A.bases_capacity) return;   // overflow: nothing is written
+  for (uint32_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
+    const uint64_t p = (uint64_t)t * TP_TILE + threadIdx.x * TP_LANE_BYTES;
+    uint32_t w[4];
+    tp_load16(A.text, A.n, p, w);
+    const uint32_t mask = fq_start_mask(A, p, w);
+    uint32_t total;
+    const uint32_t excl = tp_block_excl<false>(__popc(mask), lds, total);
+    if (p >= A.n) continue;
+    uint32_t line = A.tiles[t] + excl;   // line starts before p; position 0 is one, so the line of p + k is (starts <= p + k) - 1
+    uint32_t d = TP_NONE, s = 0;
+    if (!(mask & 1u)) { d = A.dst[line - 1]; s = A.S[line - 1]; }
+#pragma unroll
+    for (int k = 0; k < TP_LANE_BYTES; k++) {
+      if (p + k >= A.n) continue;
+      if (mask & (1u << k)) { d = A.dst[line]; s = A.S[line]; line++; }
+      const uint32_t c = tp_byte(w, k);
+      if (d != TP_NONE && c != '\n' && c != '\r') {
+        const uint64_t at = (uint64_t)d + ((uint32_t)(p + k) - s);
+        if (at < A.bases_capacity) A.bases[at] = (uint8_t)c;
+      }
+    }
+  }
+}
+
+// ---- FASTA --------------------------------------------------------------------------------------------------------------------
+// Positions travel as pos + 1 in 32 bits, 0 = none: the max-scans' neutral element.  tiles: five arrays of ntiles + 1 --
+// [0] last '>', [1] last terminator, [2] kept bytes, [3] last kept byte, [4] records.
+// STAGE 0: arrays 0, 1.  STAGE 1 (0, 1 scanned): arrays 2, 3.  STAGE 2 (2, 3 scanned): array 4.  STAGE 3 (4 scanned): the output.
+template <int STAGE>
+__global__ void __launch_bounds__(TP_BLOCK) fa_kernel(TpArgs A) {
+  __shared__ uint32_t lds[TP_BLOCK / 64];
+  const uint64_t stride = (uint64_t)A.ntiles + 1;
+  uint32_t *t_gt = A.tiles, *t_tm = A.tiles + stride, *t_kept = A.tiles + 2 * stride, *t_lk = A.tiles + 3 * stride, *t_rec = A.tiles + 4 * stride;
+  // Bytes are kept below `limit`: the end of a final chunk; else the last '>' of the chunk, which opens the first record not taken
+  // (no '>' at all: nothing is taken).
+  uint64_t limit = A.n;
+  if (STAGE >= 1 && !A.final) limit = t_gt[A.ntiles] ? t_gt[A.ntiles] - 1 : 0;
+  bool over = false;
+  if (STAGE == 3) over = t_rec[A.ntiles] > A.records_capacity || t_kept[A.ntiles] > A.bases_capacity;
+  for (uint32_t t = blockIdx.x; t < A.ntiles; t += gridDim.x) {
+    const uint64_t p = (uint64_t)t * TP_TILE + threadIdx.x * TP_LANE_BYTES;
+    uint32_t w[4];
+    tp_load16(A.text, A.n, p, w);
+    uint32_t m_gt = 0, m_tm = 0, m_other = 0;
+#pragma unroll
+    for (int k = 0; k < TP_LANE_BYTES; k++) {
+      const uint32_t c = tp_byte(w, k);
+      if (p + k >= A.n) continue;
+      if (c == '>') m_gt |= 1u << k;
+      else if (c == '\n' || c == '\r') m_tm |= 1u << k;
+      else m_other |= 1u << k;
+    }
+    const uint32_t P1 = (uint32_t)p + 1;   // (only used where the lane holds a byte below n: no wrap)
+    uint32_t tot_gt, tot_tm;
+    uint32_t lg = tp_block_excl<true>(m_gt ? P1 + tp_top(m_gt) : 0, lds, tot_gt);
+    uint32_t lt = tp_block_excl<true>(m_tm ? P1 + tp_top(m_tm) : 0, lds, tot_tm);
+    if (STAGE == 0) {
+      if (threadIdx.x == 0) { t_gt[t] = tot_gt; t_tm[t] = tot_tm; }
+      continue;
+    }
+    lg = max(lg, t_gt[t]);   // the last '>' and the last terminator before the lane's bytes
+    lt = max(lt, t_tm[t]);
+    // the kept bytes: neither '>' nor a terminator, a terminator since the last '>', below the limit
+    uint32_t m_keep = 0;
+    {
+      uint32_t g = lg, x = lt;
+#pragma unroll
+      for (int k = 0; k < TP_LANE_BYTES; k++) {
+        if (m_gt & (1u << k)) g = P1 + k;
+        else if (m_tm & (1u << k)) x = P1 + k;
+        else if ((m_other & (1u << k)) && x > g && p + k < limit) m_keep |= 1u << k;
+      }
+    }
+    uint32_t tot_kept, tot_lk;
+    uint32_t K = tp_block_excl<false>(__popc(m_keep), lds, tot_kept);
+    uint32_t lk = tp_block_excl<true>(m_keep ? P1 + tp_top(m_keep) : 0, lds, tot_lk);
+    if (STAGE == 1) {
+      if (threadIdx.x == 0) { t_kept[t] = tot_kept; t_lk[t] = tot_lk; }
+      continue;
+    }
+    K += t_kept[t];           // kept bytes before the lane's
+    lk = max(lk, t_lk[t]);    // the last of them
+    // what closes a piece: every '>', and the end of a final chunk (position n).  It closes a RECORD iff a byte was kept since the
+    // '>' before it.
+    uint32_t m_mark = m_gt;
+    if (A.final && A.n >= p && A.n < p + TP_LANE_BYTES) m_mark |= 1u << (int)(A.n - p);
+    uint32_t m_emit = 0;
+    for (uint32_t m = m_mark; m; m &= m - 1) {
+      const int k = __ffs((int)m) - 1;
+      const uint32_t gb = tp_below(m_gt, k), kb = tp_below(m_keep, k);
+      const uint32_t g = gb ? P1 + tp_top(gb) : lg, kk = kb ? P1 + tp_top(kb) : lk;
+      if (kk > g) m_emit |= 1u << k;
+    }
+    uint32_t tot_rec;
+    uint32_t r = tp_block_excl<false>(__popc(m_emit), lds, tot_rec);
+    if (STAGE == 2) {
+      if (threadIdx.x == 0) t_rec[t] = tot_rec;
+      continue;
+    }
+    if (over) continue;
+    r += t_rec[t];
+    for (uint32_t m = m_keep; m; m &= m - 1) {
+      const int k = __ffs((int)m) - 1;
+      const uint64_t at = (uint64_t)K + __popc(tp_below(m_keep, k));
+      if (at < A.bases_capacity) A.bases[at] = (uint8_t)tp_byte(w, k);
+    }
+    for (uint32_t m = m_emit; m; m &= m - 1, r++) {
+      const int k = __ffs((int)m) - 1;
+      const uint32_t gb = tp_below(m_gt, k);
+      const uint64_t start = gb ? (uint64_t)p + tp_top(gb) + 1 : lg;   // behind the '>' that opens the record; 0: the text's first piece
+      uint64_t q = start;
+      while (q < p + k) {
+        const uint8_t c = A.text[q];
+        if (c == ' ' || c == '\n' || c == '\r') break;
+        q++;
+      }
+      if (r < A.records_capacity) {
+        A.offsets[r + 1] = (uint64_t)K + __popc(tp_below(m_keep, k));   // where record r ends = where record r + 1 starts
+        A.title_pos[r] = start;
+        A.title_len[r] = (uint32_t)(q - start);
+      }
+    }
+  }
+  if (STAGE == 3 && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (!over) A.offsets[0] = 0;
+    A.counts[0] = t_rec[A.ntiles];
+    A.counts[1] = t_kept[A.ntiles];
+    A.counts[2] = over ? 0 : A.final ? A.n : limit;
+    A.counts[3] = over ? 1 : 0;
+  }
+}
+
+// an empty text: no record, nothing consumed
+__global__ void tp_empty_kernel(uint64_t *offsets, uint64_t *counts) {
+  offsets[0] = 0;
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+}
+
+}  // namespace
+
+namespace slk {
+
+// The passes of one parse, queued on the stream's HIP stream.  All pointers on the device; d_offsets holds records_capacity + 1.
+int32_t launch_parse(slk_stream *st, const uint8_t *d_text, uint64_t n, int32_t format, bool final, uint8_t *d_bases, uint64_t bases_capacity,
+                     uint64_t *d_offsets, uint64_t *d_title_pos, uint32_t *d_title_len, uint64_t records_capacity, uint64_t *d_counts) {
+  hipStream_t s = st->s;
+  if (n == 0) {
+    hipLaunchKernelGGL(tp_empty_kernel, dim3(1), dim3(1), 0, s, d_offsets, d_counts);
+    HIPCHK(hipGetLastError());
+    return SLK_OK;
+  }
+  const bool fastq = format == SLK_FORMAT_FASTQ;
+  TpArgs A{};
+  A.text = d_text;
+  A.n = n;
+  A.final = final ? 1 : 0;
+  A.ntiles = (uint32_t)(((fastq || !final ? n : n + 1) + TP_TILE - 1) / TP_TILE);
+  A.nlt_max = (uint32_t)(n / TP_BLOCK + 1);
+  // scratch, in words: the tiles' arrays, then (FASTQ) the line starts, the lines' destinations and the line tiles' two arrays
+  const uint64_t tile_words = (fastq ? 1 : 5) * ((uint64_t)A.ntiles + 1);
+  const uint64_t words = tile_words + (fastq ? 2 * (n + 2) + 2 * ((uint64_t)A.nlt_max + 1) : 0);
+  HIPCHK(st->parse_scratch.ensure(words * 4));
+  A.tiles = st->parse_scratch.as<uint32_t>();
+  A.S = A.tiles + tile_words;
+  A.dst = A.S + (n + 2);
+  A.ltiles = A.dst + (n + 2);
+  A.bases = d_bases; A.bases_capacity = bases_capacity;
+  A.offsets = d_offsets; A.title_pos = d_title_pos; A.title_len = d_title_len; A.records_capacity = records_capacity;
+  A.counts = d_counts;
+  const dim3 grid(std::min<unsigned>(A.ntiles, TP_MAX_GRID)), block(TP_BLOCK);
+  if (fastq) {
+    const dim3 lgrid(std::min<unsigned>(A.nlt_max, TP_MAX_GRID));
+    hipLaunchKernelGGL(fq_lines_kernel<0>, grid, block, 0, s, A);
+    hipLaunchKernelGGL(tp_scan_kernel, dim3(1), dim3(TP_SCAN_BLOCK), 0, s, A.tiles, (uint64_t)0, A.ntiles, (const uint32_t *)nullptr, 1u, 0u);
+    hipLaunchKernelGGL(fq_lines_kernel<1>, grid, block, 0, s, A);
+    hipLaunchKernelGGL(fq_records_kernel<0>, lgrid, block, 0, s, A);
+    hipLaunchKernelGGL(tp_scan_kernel, dim3(2), dim3(TP_SCAN_BLOCK), 0, s, A.ltiles, (uint64_t)A.nlt_max + 1, 0u, (const uint32_t *)(A.tiles + A.ntiles),
+                       (uint32_t)TP_BLOCK, 0u);
+    hipLaunchKernelGGL(fq_records_kernel<1>, lgrid, block, 0, s, A);
+    hipLaunchKernelGGL(fq_copy_kernel, grid, block, 0, s, A);
+  } else {
+    const uint64_t stride = (uint64_t)A.ntiles + 1;
+    hipLaunchKernelGGL(fa_kernel<0>, grid, block, 0, s, A);
+    hipLaunchKernelGGL(tp_scan_kernel, dim3(2), dim3(TP_SCAN_BLOCK), 0, s, A.tiles, stride, A.ntiles, (const uint32_t *)nullptr, 1u, 3u);
+    hipLaunchKernelGGL(fa_kernel<1>, grid, block, 0, s, A);
+    hipLaunchKernelGGL(tp_scan_kernel, dim3(2), dim3(TP_SCAN_BLOCK), 0, s, A.tiles + 2 * stride, stride, A.ntiles, (const uint32_t *)nullptr, 1u, 2u);
+    hipLaunchKernelGGL(fa_kernel<2>, grid, block, 0, s, A);
+    hipLaunchKernelGGL(tp_scan_kernel, dim3(1), dim3(TP_SCAN_BLOCK), 0, s, A.tiles + 4 * stride, stride, A.ntiles, (const uint32_t *)nullptr, 1u, 0u);
+    hipLaunchKernelGGL(fa_kernel<3>, grid, block, 0, s, A);
+  }
+  HIPCHK(hipGetLastError());
+  return SLK_OK;
+}
+
+int32_t check_parse_args(uint64_t n, int32_t format) {
+  if (format != SLK_FORMAT_FASTA && format != SLK_FORMAT_FASTQ) return fail(SLK_E_INVALID, "format %d is neither SLK_FORMAT_FASTA nor SLK_FORMAT_FASTQ", format);
+  if (n >= (1ULL << 32)) return fail(SLK_E_INVALID, "a parse call takes less than 2^32 bytes of text (%llu given): cut it into chunks", (unsigned long long)n);
+  return SLK_OK;
+}
+
+// text -> the stream's text buffer; parsed into the stream's read buffers (bases, offsets) and title buffers; the counts record to
+// the host.  Synchronises st->s.  counts: records, bases, consumed, overflow.
+int32_t parse_uploaded(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, bool final, uint64_t bases_capacity,
+                       uint64_t records_capacity, uint64_t counts[4]) {
+  HIPCHK(st->parse_text.ensure(std::max<uint64_t>(n, 16)));
+  HIPCHK(st->bases.ensure(std::max<uint64_t>(bases_capacity, 16)));
+  HIPCHK(st->offsets.ensure((records_capacity + 1) * 8));
+  HIPCHK(st->parse_title_pos.ensure(std::max<uint64_t>(records_capacity, 1) * 8));
+  HIPCHK(st->parse_title_len.ensure(std::max<uint64_t>(records_capacity, 1) * 4));
+  HIPCHK(st->parse_counts.ensure(4 * 8));
+  int32_t rc = copy_in(st, st->parse_text.p, text, n);
+  if (rc) return rc;
+  rc = launch_parse(st, st->parse_text.as<uint8_t>(), n, format, final, st->bases.as<uint8_t>(), bases_capacity, st->offsets.as<uint64_t>(),
+                    st->parse_title_pos.as<uint64_t>(), st->parse_title_len.as<uint32_t>(), records_capacity, st->parse_counts.as<uint64_t>());
+  if (rc) return rc;
+  rc = copy_out(st, counts, st->parse_counts.p, 4 * 8);
+  if (rc) return rc;
+  if (counts[3])
+    return fail(SLK_E_CAPACITY, "the text holds %llu records of %llu bases, the capacities are %llu and %llu", (unsigned long long)counts[0],
+                (unsigned long long)counts[1], (unsigned long long)records_capacity, (unsigned long long)bases_capacity);
+  return SLK_OK;
+}
+
+}  // namespace slk
+
+extern "C" uint32_t slk_parse_tile_bytes(void) { return TP_TILE; }
+
+extern "C" int32_t slk_parse_device(slk_stream *st, const uint8_t *d_text, uint64_t n, int32_t format, int32_t final, uint8_t *d_bases,
+                                    uint64_t bases_capacity, uint64_t *d_offsets, uint64_t *d_title_pos, uint32_t *d_title_len,
+                                    uint64_t records_capacity, uint64_t *d_counts) {
+  if (!st || !d_offsets || !d_counts || (n && !d_text) || (bases_capacity && !d_bases) || (records_capacity && (!d_title_pos || !d_title_len)))
+    return fail(SLK_E_INVALID, "null argument");
+  int32_t rc = check_parse_args(n, format);
+  if (rc) return rc;
+  if ((uintptr_t)d_text % TP_LANE_BYTES) return fail(SLK_E_INVALID, "d_text must be aligned to %d bytes", TP_LANE_BYTES);
+  if ((rc = set_device(st->ix))) return rc;
+  return launch_parse(st, d_text, n, format, final != 0, d_bases, bases_capacity, d_offsets, d_title_pos, d_title_len, records_capacity, d_counts);
+}
+
+extern "C" int32_t slk_parse_text(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, int32_t final, uint8_t *out_bases,
+                                  uint64_t *out_offsets, uint64_t *out_title_pos, uint32_t *out_title_len, uint64_t bases_capacity,
+                                  uint64_t records_capacity, uint64_t *out_records, uint64_t *out_n_bases, uint64_t *out_consumed) {
+  if (!st || !out_offsets || !out_records || !out_n_bases || !out_consumed || (n && !text) || (bases_capacity && !out_bases) ||
+      (records_capacity && (!out_title_pos || !out_title_len)))
+    return fail(SLK_E_INVALID, "null argument");
+  *out_records = *out_n_bases = *out_consumed = 0;
+  int32_t rc = check_parse_args(n, format);
+  if (rc) return rc;
+  if ((rc = set_device(st->ix))) return rc;
+  DrainOnExit drain(st);
+  uint64_t counts[4] = {0, 0, 0, 0};
+  rc = parse_uploaded(st, text, n, format, final != 0, bases_capacity, records_capacity, counts);
+  *out_records = counts[0];   // (with SLK_E_CAPACITY too: what the capacities would have to be)
+  *out_n_bases = counts[1];
+  if (rc) return rc;
+  *out_consumed = counts[2];
+  const uint64_t R = counts[0];
+  rc = copy_out(st, out_offsets, st->offsets.p, (R + 1) * 8);
+  if (!rc) rc = copy_out(st, out_bases, st->bases.p, counts[1]);
+  if (!rc) rc = copy_out(st, out_title_pos, st->parse_title_pos.p, R * 8);
+  if (!rc) rc = copy_out(st, out_title_len, st->parse_title_len.p, R * 4);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(st->s));
+  return SLK_OK;
+}

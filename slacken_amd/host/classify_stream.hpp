@@ -220,4 +220,231 @@ void classify_stream(DeviceIndex &dev, const std::vector<std::string> &files, bo
   std::cerr << pass.total << " fragments" << std::endl;
 }
 
+// ---- --device-parse: the device finds the records (slk_classify_text, slk_parse_text) --------------------------------
+// The raw bytes of a file -- a plain file's, or what the inflate threads deliver -- go to the device in chunks.  A chunk that is not
+// the file's last is parsed with final = 0: the device takes the records that are decided inside it and says where the next chunk
+// starts (`consumed`).  That position follows from the last few lines of the chunk alone, so the reader computes it here as well
+// (text_chunk_cut: a walk back over two lines, or to the last '>') and carries text[cut, n) over without waiting for the device; the
+// workers then run side by side, and each checks the device's answer against the cut it was given.
+
+// the largest line start below q (seqio.hpp: is_line_start); q > 0
+inline size_t prev_line_start(const char *d, size_t q) {
+  for (size_t p = q - 1; p > 0; p--)
+    if (d[p - 1] == '\n' || (d[p - 1] == '\r' && d[p] != '\n')) return p;
+  return 0;
+}
+// `consumed` of a non-final chunk, as the device parser defines it: FASTQ -- the start of the last but one line that is present (a
+// line is present when its terminator lies inside the chunk; a \r on the last byte is undecided), FASTA -- the last '>'; 0: the chunk
+// must grow
+inline size_t text_chunk_cut(const char *d, size_t n, bool fastq) {
+  if (n == 0) return 0;
+  if (!fastq) {
+    const void *g = memrchr(d, '>', n);
+    return g ? (size_t)((const char *)g - d) : 0;
+  }
+  const size_t end = d[n - 1] == '\n' ? n : prev_line_start(d, n);   // where the lines that are present end
+  if (end == 0) return 0;
+  const size_t last = prev_line_start(d, end);
+  return last == 0 ? 0 : prev_line_start(d, last);
+}
+
+struct PinnedText {   // a worker's chunk in pinned memory: the upload is a DMA out of it
+  char *p = nullptr;
+  size_t cap = 0;
+  PinnedText() = default;
+  PinnedText(const PinnedText &) = delete;
+  ~PinnedText() { if (p) (void)slk_host_free(p); }
+  void ensure(size_t bytes, size_t keep) {   // the first `keep` bytes survive
+    if (bytes <= cap) return;
+    void *q = nullptr;
+    const size_t want = bytes + bytes / 4 + 4096;
+    SLK_CALL(slk_host_alloc(want, &q));
+    if (keep) memcpy(q, p, keep);
+    if (p) (void)slk_host_free(p);
+    p = (char *)q;
+    cap = want;
+  }
+};
+
+// The chunks of a list of files, in order; one caller at a time.  A compressed file or a pipe is read through ByteSource into the
+// caller's pinned buffer, behind what the chunk before left over.  A plain file is mapped, as the host parser maps it: a chunk is a
+// range of the mapping (c.p points into it: the library stages the upload on its copy threads, as it does for a parsed batch), the next
+// one starts at the cut, and nothing is copied here.  The mappings live as long as this object.
+class TextChunks {
+ public:
+  static constexpr size_t MAX_CHUNK = (size_t)1 << 30;
+  struct Chunk { const char *p = nullptr; size_t n = 0, cut = 0; bool final = false, fastq = false; };
+ private:
+  const std::vector<std::string> &files_;
+  size_t next_file_ = 0;
+  std::unique_ptr<ByteSource> src_;
+  std::string file_, carry_;
+  bool fastq_ = false;
+  const size_t chunk_ = io_chunk_bytes();
+  struct Mapping { const char *p; size_t n; };
+  std::vector<Mapping> maps_;
+  const char *map_ = nullptr;   // the plain file being read, or null
+  size_t map_len_ = 0, map_pos_ = 0;
+
+  static bool plain_file(const std::string &file) {
+    if (!ByteSource::regular_file(file) || ends_with(file, ".gz") || ends_with(file, ".bz2")) return false;
+    FILE *f = fopen(file.c_str(), "rb");
+    if (!f) die("cannot open " + file);
+    unsigned char m[2] = {0, 0};
+    const size_t k = fread(m, 1, 2, f);
+    fclose(f);
+    return !(k == 2 && m[0] == 0x1f && m[1] == 0x8b);   // (zlib would inflate a gzip file under any name)
+  }
+  bool open_next() {
+    if (next_file_ >= files_.size()) return false;
+    file_ = files_[next_file_++];
+    fastq_ = RecordStream::is_fastq_name(file_);
+    carry_.clear();
+    if (!plain_file(file_)) { src_ = std::make_unique<ByteSource>(file_); return true; }
+    const int fd = open(file_.c_str(), O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0) die("cannot open " + file_);
+    map_len_ = (size_t)sb.st_size;
+    map_pos_ = 0;
+    void *m = map_len_ ? mmap(nullptr, map_len_, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+    close(fd);
+    if (map_len_ && m == MAP_FAILED) die("cannot map " + file_);
+    if (map_len_) { madvise(m, map_len_, MADV_SEQUENTIAL); maps_.push_back({(const char *)m, map_len_}); }
+    static const char empty = 0;
+    map_ = map_len_ ? (const char *)m : &empty;
+    return true;
+  }
+  bool next_mapped(Chunk &c) {   // false: this file is through
+    const size_t left = map_len_ - map_pos_;
+    if (left == 0) { map_ = nullptr; return false; }
+    c.p = map_ + map_pos_;
+    c.fastq = fastq_;
+    for (size_t n = std::min(chunk_, left);; n = std::min(2 * n, std::min(left, MAX_CHUNK))) {
+      c.n = n;
+      c.final = n == left;
+      c.cut = c.final ? n : text_chunk_cut(c.p, n, fastq_);
+      if (c.cut > 0) break;
+      if (n >= MAX_CHUNK)
+        die("a record of " + file_ + " does not fit the largest chunk the device parser takes (1 GiB): classify this input without --device-parse");
+    }
+    map_pos_ += c.cut;
+    return true;
+  }
+ public:
+  explicit TextChunks(const std::vector<std::string> &files) : files_(files) {}
+  TextChunks(const TextChunks &) = delete;
+  ~TextChunks() { for (const Mapping &m : maps_) munmap((void *)m.p, m.n); }
+  bool next(PinnedText &b, Chunk &c) {   // false: the input is exhausted
+    for (;;) {
+      if (!src_ && !map_ && !open_next()) return false;
+      if (map_) {
+        if (next_mapped(c)) return true;
+        continue;
+      }
+      size_t n = carry_.size(), want = chunk_;
+      b.ensure(n + want, 0);
+      memcpy(b.p, carry_.data(), n);
+      c.fastq = fastq_;
+      for (;;) {
+        b.ensure(n + want, n);
+        const size_t got = src_->read(b.p + n, want);
+        n += got;
+        if (got == 0) { c.final = true; c.cut = n; break; }
+        c.final = false;
+        c.cut = text_chunk_cut(b.p, n, fastq_);
+        if (c.cut > 0) break;
+        if (n >= MAX_CHUNK)
+          die("a record of " + file_ + " does not fit the largest chunk the device parser takes (1 GiB): classify this input without --device-parse");
+        want = std::min(std::max(n, chunk_), MAX_CHUNK - n);   // no record ends inside the chunk: twice the bytes
+      }
+      c.n = n;
+      c.p = b.p;
+      if (c.final) src_.reset();
+      else carry_.assign(b.p + c.cut, n - c.cut);
+      if (n > 0) return true;   // (a file that ends on a chunk border leaves an empty last chunk: on to the next file)
+    }
+  }
+};
+
+// classify_stream with the records found on the device: unpaired input, a replicated table, one id column (the command line refuses
+// the rest).  A batch is a chunk of text; what comes back fills a FragmentBatch that holds the offsets and the titles only -- the
+// titles copied out of the chunk by (position, length) -- and everything downstream of f works on it as on a parsed batch.
+template <class F>
+void classify_text_stream(DeviceIndex &dev, const std::vector<std::string> &files, int min_hits, const std::vector<double> &thresholds,
+                          bool want_hits, F f, bool merged_hits = false) {
+  if (dev.sharded) die("internal: classify_text_stream runs on a replicated table");
+  TextChunks input(files);
+  std::mutex mu_in;
+  OrderedHandOver order;
+  std::atomic<size_t> total{0}, n_batches{0};
+  const int C = (int)thresholds.size();
+  struct Lane { slk_index *ix = nullptr; slk_stream *st = nullptr; };
+  auto work = [&](const Lane &lane) {
+    PinnedText buf;
+    std::vector<int32_t> nd, tk;
+    std::vector<uint64_t> tpos;
+    std::vector<uint32_t> tlen;
+    try {
+      while (!order.failed()) {
+        TextChunks::Chunk c;
+        size_t ticket;
+        {
+          std::lock_guard<std::mutex> lk(mu_in);
+          if (!input.next(buf, c)) break;
+          ticket = order.next_ticket++;
+        }
+        n_batches++;
+        auto out = new_classified_batch();
+        ClassifiedBatch &b = *out;
+        b.frags = new_fragment_batch(1);
+        b.C = C;
+        FragmentBatch &fb = *b.frags;
+        if (want_hits) b.reserve_hits(c.n + 1);   // (a span per base at most)
+        uint64_t R = 0, consumed = 0;
+        size_t rcap = c.n / 64 + 1024;   // records the arrays hold: a guess, and what the call asks for if the guess was short
+        for (int attempt = 0;; attempt++) {
+          b.taxon.resize((size_t)C * rcap); b.classified.resize((size_t)C * rcap); nd.resize(rcap); tk.resize(rcap);
+          fb.offs.resize(rcap + 1); tpos.resize(rcap); tlen.resize(rcap); b.hit_offs.resize(rcap + 1);
+          const int32_t rc = slk_classify_text(lane.ix, lane.st, (const uint8_t *)c.p, c.n, c.fastq ? SLK_FORMAT_FASTQ : SLK_FORMAT_FASTA, c.final ? 1 : 0,
+                                               min_hits, thresholds.data(), C, b.taxon.data(), b.classified.data(), nd.data(), tk.data(), fb.offs.data(),
+                                               tpos.data(), tlen.data(), b.hit_offs.data(), want_hits ? b.hits.get() : nullptr, rcap, c.n + 1, &R, &consumed);
+          if (rc == SLK_E_CAPACITY && attempt == 0 && R > rcap) { rcap = R; continue; }
+          if (rc != SLK_OK) die(std::string("slk_classify_text: ") + slk_last_error());
+          break;
+        }
+        if (!c.final && consumed != c.cut)
+          die("internal: the device parser consumed " + std::to_string(consumed) + " bytes of a chunk that was cut at " + std::to_string(c.cut));
+        b.taxon.resize((size_t)C * R); b.classified.resize((size_t)C * R);
+        fb.offs.resize(R + 1); b.hit_offs.resize(R + 1);
+        fb.title_off.resize(R + 1);
+        for (uint64_t r = 0; r < R; r++) fb.title_off[r + 1] = fb.title_off[r] + tlen[r];
+        fb.titles.resize(fb.title_off[R]);
+        for (uint64_t r = 0; r < R; r++) memcpy(&fb.titles[fb.title_off[r]], c.p + tpos[r], tlen[r]);
+        total += R;
+        order.deliver(ticket, [&] { f(std::shared_ptr<const ClassifiedBatch>(std::move(out))); });
+      }
+    } catch (...) {
+      order.fail(std::current_exception());
+    }
+  };
+  const char *wenv = getenv("SLK_CLASSIFY_THREADS");
+  const size_t per_dev = std::max<size_t>(1, std::min<size_t>(8, wenv ? (size_t)atol(wenv) : 2));
+  std::vector<Lane> lanes(per_dev * dev.ixs.size());
+  for (size_t i = 0; i < lanes.size(); i++) {
+    lanes[i].ix = dev.ixs[i % dev.ixs.size()];
+    lanes[i].st = dev.st;
+    if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
+    SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merged_hits && want_hits ? 1 : 0));
+  }
+  std::vector<std::thread> workers;
+  for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&work, &lanes, i] { work(lanes[i]); });
+  work(lanes[0]);
+  for (auto &t : workers) t.join();
+  for (size_t i = 1; i < lanes.size(); i++) slk_stream_destroy(lanes[i].st);
+  (void)slk_stream_set_merged_hits(dev.st, 0);
+  order.rethrow_failure();
+  if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_batches << " chunks parsed on the device by " << lanes.size() << " classify thread(s)" << std::endl;
+  std::cerr << total << " fragments" << std::endl;
+}
+
 }  // namespace slk_host

@@ -71,8 +71,56 @@ static int cmd_gunzip(int argc, char **argv) {
   }
   return 0;
 }
+// parse --device FILE: the same lines with the records found on the device (slk_parse_text) -- the file's bytes, inflated if need be, go
+// up chunk by chunk out of pinned memory, the rest of a chunk that `consumed` leaves is carried over to the next
+static int parse_on_device(int argc, char **argv) {
+  if (argc != 1) die("usage: parse --device FILE");
+  const std::vector<std::string> files{argv[0]};
+  const slk_params sp{35, 31, 7, 1, SLK_DEFAULT_TOGGLE_MASK, 1, 0};   // (a stream belongs to an index: an empty one of the default shape)
+  const slk_table_config cfg{1024, 0, 0.0f};
+  slk_index *ix = nullptr;
+  slk_stream *st = nullptr;
+  SLK_CALL(slk_index_create(&sp, &cfg, 0, &ix));
+  SLK_CALL(slk_stream_create(ix, &st));
+  {
+    TextChunks input(files);
+    PinnedText buf;
+    TextChunks::Chunk c;
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> offs, tpos;
+    std::vector<uint32_t> tlen;
+    std::string out;
+    while (input.next(buf, c)) {
+      uint64_t R = 0, nb = 0, consumed = 0;
+      size_t rcap = c.n / 64 + 1024;
+      bases.resize(c.n);
+      for (int attempt = 0;; attempt++) {
+        offs.resize(rcap + 1); tpos.resize(rcap); tlen.resize(rcap);
+        const int32_t rc = slk_parse_text(st, (const uint8_t *)c.p, c.n, c.fastq ? SLK_FORMAT_FASTQ : SLK_FORMAT_FASTA, c.final ? 1 : 0, bases.data(),
+                                          offs.data(), tpos.data(), tlen.data(), bases.size(), rcap, &R, &nb, &consumed);
+        if (rc == SLK_E_CAPACITY && attempt == 0 && R > rcap) { rcap = R; continue; }
+        if (rc != SLK_OK) die(std::string("slk_parse_text: ") + slk_last_error());
+        break;
+      }
+      if (!c.final && consumed != c.cut)
+        die("internal: the device parser consumed " + std::to_string(consumed) + " bytes of a chunk that was cut at " + std::to_string(c.cut));
+      out.clear();
+      for (uint64_t r = 0; r < R; r++) {
+        out.append(c.p + tpos[r], tlen[r]);
+        out += '\t';
+        out.append((const char *)bases.data() + offs[r], offs[r + 1] - offs[r]);
+        out += '\n';
+      }
+      std::cout << out;
+    }
+  }
+  slk_stream_destroy(st);
+  slk_index_destroy(ix);
+  return 0;
+}
 static int cmd_parse(int argc, char **argv) {  // parse <file> [<file2>]: header \t nucleotides [\t nucleotides2]
-  if (argc < 1) die("usage: parse [--count] FILE [MATE_FILE]");
+  if (argc < 1) die("usage: parse [--count] FILE [MATE_FILE] | parse --device FILE");
+  if (std::string(argv[0]) == "--device") return parse_on_device(argc - 1, argv + 1);
   if (std::string(argv[0]) == "--count") {  // read through the batch reader only: fragments, bases, a checksum, seconds
     std::vector<std::string> files(argv + 1, argv + std::min(argc, 3));
     const double t0 = wall_seconds();
@@ -182,6 +230,7 @@ struct ClassifyOpts {
   std::vector<std::string> files;
   std::vector<int> devices{0};  // --devices: the GPUs that share the reads (table replicated on each)
   bool shard_table = false;     // --shard-table: the table is spread over the devices instead (a library beyond one GPU's memory)
+  bool device_parse = false;    // --device-parse: the raw text goes to the device, which finds the records (classify_text_stream)
   // classify2 (Slacken.scala:199-260)
   std::string library, rank = "species";
   int min_count = -1, min_distinct = -1, reads = -1;
@@ -211,6 +260,10 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
     else if (a == "--sample-regex") o.sample_regex = a.next();
     else if (a == "--devices") o.devices = parse_device_list(a.next());
     else if (a == "--shard-table") { if (two_step) die("--shard-table is for classify (the dynamic library of classify2 is small)"); o.shard_table = true; }
+    else if (a == "--device-parse") {
+      if (two_step) die("--device-parse is for classify (classify2 reads its input through the host parser)");
+      o.device_parse = true;
+    }
     else if (two_step && (a == "-l" || a == "--library")) o.library = a.next();
     else if (two_step && a == "--rank") o.rank = a.next();
     else if (two_step && (a == "-C" || a == "--min-count")) o.min_count = std::stoi(a.next());
@@ -235,6 +288,8 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
                  : "usage: classify -i INDEX -o OUTPUT [-p] [-c T...] [--min-hits N] [--sample-regex RE] FILES");
   if (two_step && o.gold_set.empty() && (o.classify_with_gold || !o.promote_rank.empty()))
     die("--classify-with-gold and --promote-gold-set qualify a gold set: give one with -g FILE");
+  if (o.device_parse && o.paired) die("--device-parse takes unpaired input (the mates of paired reads are joined by title, on the host)");
+  if (o.device_parse && o.shard_table) die("--device-parse needs the whole table on the device that parses (not --shard-table)");
   if (o.thresholds.empty()) o.thresholds.push_back(0.0);
   for (double t : o.thresholds) if (t < 0 || t > 1) die("confidence must be in [0, 1]");
   if (o.paired && o.files.size() % 2 != 0)
@@ -281,8 +336,11 @@ static void classify_and_write(DeviceIndex &dev, const IndexParams &ip, const Ta
   oo.with_unclassified = o.with_unclassified; oo.detailed = o.detailed; oo.k = ip.k;
   Timer t("Classify reads");
   OutputSink sink(oo, tax, host_threads());
-  classify_stream(dev, o.files, o.paired, o.min_hits, o.thresholds, false, o.detailed,   // (hit lists only feed the per-read lines)
-                  [&](std::shared_ptr<const ClassifiedBatch> b) { sink.submit(std::move(b)); }, &sink.repeated(), nullptr, true);
+  if (o.device_parse)
+    classify_text_stream(dev, o.files, o.min_hits, o.thresholds, o.detailed, [&](std::shared_ptr<const ClassifiedBatch> b) { sink.submit(std::move(b)); }, true);
+  else
+    classify_stream(dev, o.files, o.paired, o.min_hits, o.thresholds, false, o.detailed,   // (hit lists only feed the per-read lines)
+                    [&](std::shared_ptr<const ClassifiedBatch> b) { sink.submit(std::move(b)); }, &sink.repeated(), nullptr, true);
   sink.drain();
   sink.repeated().settle_unmatched([&](uint64_t h) { return sink.has_title(h); });
   if (!sink.repeated().empty()) resolve_repeated_titles(dev, ip, o, sink);
@@ -291,6 +349,8 @@ static void classify_and_write(DeviceIndex &dev, const IndexParams &ip, const Ta
 
 static int cmd_classify(int argc, char **argv) {
   ClassifyOpts o = parse_classify_opts(argc, argv, false);
+  if (o.device_parse && read_index_params(o.index).m > 32)
+    die("--device-parse supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
   LoadedIndex lib(o.index, o.devices, o.shard_table);
   classify_and_write(lib.dev, lib.ip, lib.tax, o);
   return 0;
@@ -1203,6 +1263,8 @@ static const char *HELP =
     "      --devices LIST     GPUs that share the reads, `all` or e.g. 0,1,2,3 (default 0); the library is replicated on each\n"
     "      --shard-table      classify: spread the library over the devices instead (each holds the records whose minimizer falls to it;\n"
     "                         minimizers travel to their owners and taxa back): for a library beyond one GPU's memory\n"
+    "      --device-parse     classify: send the files' text to the device as it is and find the records there (unpaired input, a\n"
+    "                         replicated table, m <= 32; `parse --device FILE` shows what the device finds); the default parses on the host\n"
     "  FILES                  FASTA / FASTQ, plain, .gz or .bz2; @list.txt names a file of file names\n"
     "options of classify2 (Slacken.scala:199-260): --library DIR (DIR/library/**/*.fna, DIR/seqid2taxid.map), --rank RANK (species),\n"
     "  -R, --reads N (100) | -C, --min-count N | -D, --min-distinct N, --init-confidence X (0.15)\n"
