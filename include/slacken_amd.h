@@ -336,7 +336,7 @@ int32_t slk_pack_bases(const uint8_t *bases, uint64_t n, uint32_t *codes, uint16
  *          of the first line whose window could not be decided; FASTA: the '>' that opens the first record not taken, 0 if the chunk
  *          holds none): the caller puts text[consumed, n) in front of the next chunk, and any sequence of such calls, the last one
  *          with final = 1, yields the records of the whole text in order.  consumed == 0 on a non-final chunk: the chunk must grow.
- * Limits: n < 2^32 per call (SLK_E_INVALID beyond); single-end.  title_pos[r] is a position in `text` (FASTQ: behind the '@'),
+ * Limits: n < 2^32 per call (SLK_E_INVALID beyond); two mate files go through the paired entries below.  title_pos[r] is a position in `text` (FASTQ: behind the '@'),
  * title_len[r] the bytes of the title.  The counts record is four uint64: records, bases, consumed, overflow.
  *   slk_parse_device  every pointer on the stream's device, d_text aligned to 16 bytes, nothing past text[n) is read; asynchronous
  *                     on st.  d_offsets holds records_capacity + 1 entries.  More records than records_capacity or more bases than
@@ -367,6 +367,55 @@ int32_t slk_classify_text(slk_index *ix, slk_stream *st, const uint8_t *text, ui
                           int32_t *out_num_distinct, int32_t *out_total_kmers, uint64_t *out_offsets, uint64_t *out_title_pos,
                           uint32_t *out_title_len, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t records_capacity,
                           uint64_t hits_capacity, uint64_t *out_records, uint64_t *out_consumed);
+
+/* ---- two mate texts paired on the device: replaces PairedInputReader.getFragments (S/kmers/input/InputReader.scala:105-131) while
+ * both files list their mates in the same order.  The reference inner-joins the two files' records on the header with
+ * one trailing "/1" removed in file 1 and one trailing "/2" in file 2; this is the lockstep walk of that join.  With R1, R2 the records
+ * the parser above takes from text1 / text2 (each with its own format and final flag) and M = min(R1, R2):
+ *   key1(i)   the title of record i of text 1 without ONE trailing "/1" ("a/1/1" -> "a/1", "/1" -> ""); key2(i) the same with "/2".
+ *             A "/2" in text 1 or a "/1" in text 2 stays.  Keys are equal iff their lengths and bytes are.
+ *   pairs     P = the number of leading i < M with key1(i) == key2(i); mismatch = (P < M).  Fragments 0 .. P-1 are record i of text 1
+ *             as the read and record i of text 2 as its mate.
+ *   consumed  where the next chunk of either text starts: R_i > P -- the byte that opens record P of text i (title_pos_i[P] - 1, or 0
+ *             for a FASTA record that opens the text without '>'); R_i == P -- the single-text parser's consumed.  Both record rules
+ *             are local, so parsing on from a record's opener yields the same records.  P == 0 without a mismatch: a side has no
+ *             record; if it is not final its chunk must grow, if it is final the file pair is finished (the inner join drops what the
+ *             other file still holds).
+ * slk_pair_record is also the layout of the eight uint64 the device writes.  With SLK_E_CAPACITY records1 / records2 / bases1 / bases2
+ * say what the capacities would have to be and the rest is 0.
+ *   slk_pair_device        every pointer on the stream's device, asynchronous on st (InputReader.scala:105-131): the compare and
+ *                          finish passes over the outputs of two slk_parse_device calls that did not overflow; R1, R2 are their
+ *                          record counts, d_counts1 / d_counts2 their counts records, d_pair eight uint64.  d_title_len1 is
+ *                          rewritten: every record of text 1 loses its "/1".  Nothing outside text1[0, n1), text2[0, n2) is read.
+ *   slk_parse_text_paired  from and to host memory, synchronous (InputReader.scala:105-131): the two parses and the pairing alone.
+ *                          out_bases / out_offsets[P+1] and out_mate_bases / out_mate_offsets[P+1] hold the P pairs, out_title_pos /
+ *                          out_title_len the (stripped) titles of all R1 records of text 1 -- the caller needs those beyond P when
+ *                          text 2 is exhausted.  More records or bases than a capacity on either side: SLK_E_CAPACITY, no output
+ *                          array is written.
+ *   slk_classify_text_paired  uploads both texts, parses, pairs and classifies the P fragments where they lie, mates included, by
+ *                          the route of slk_classify_text (InputReader.scala:105-131): what slk_classify_text returns for P records
+ *                          (stride P) plus out_mate_offsets[P+1], the titles of all R1 records and the pair record.  records_capacity
+ *                          bounds the records of EITHER text.  A mismatch is not an error: SLK_OK, the flag set, P pairs classified.
+ *                          Synchronous on every return; SLK_E_CAPACITY, SLK_E_UNSUPPORTED and SLK_E_INVALID as slk_classify_text. */
+typedef struct slk_pair_record {
+  uint64_t pairs, mismatch, consumed1, consumed2, records1, records2;
+  uint64_t bases1, bases2;   /* offsets1[pairs], offsets2[pairs]: the bases of the reads and of the mates */
+} slk_pair_record;
+int32_t slk_pair_device(slk_stream *st, const uint8_t *d_text1, uint64_t n1, const uint64_t *d_title_pos1, uint32_t *d_title_len1,
+                        const uint64_t *d_offsets1, const uint64_t *d_counts1, uint64_t R1, const uint8_t *d_text2, uint64_t n2,
+                        const uint64_t *d_title_pos2, const uint32_t *d_title_len2, const uint64_t *d_offsets2, const uint64_t *d_counts2,
+                        uint64_t R2, uint64_t *d_pair);
+int32_t slk_parse_text_paired(slk_stream *st, const uint8_t *text1, uint64_t n1, int32_t format1, int32_t final1, const uint8_t *text2,
+                              uint64_t n2, int32_t format2, int32_t final2, uint8_t *out_bases, uint64_t *out_offsets,
+                              uint8_t *out_mate_bases, uint64_t *out_mate_offsets, uint64_t *out_title_pos, uint32_t *out_title_len,
+                              uint64_t bases_capacity1, uint64_t records_capacity1, uint64_t bases_capacity2, uint64_t records_capacity2,
+                              slk_pair_record *out_pair);
+int32_t slk_classify_text_paired(slk_index *ix, slk_stream *st, const uint8_t *text1, uint64_t n1, int32_t format1, int32_t final1,
+                                 const uint8_t *text2, uint64_t n2, int32_t format2, int32_t final2, int32_t min_hit_groups,
+                                 const double *thresholds, int32_t C, int32_t *out_taxon, uint8_t *out_classified, int32_t *out_num_distinct,
+                                 int32_t *out_total_kmers, uint64_t *out_offsets, uint64_t *out_mate_offsets, uint64_t *out_title_pos,
+                                 uint32_t *out_title_len, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t records_capacity,
+                                 uint64_t hits_capacity, slk_pair_record *out_pair);
 
 /* ---- kernel-3-only entry: Classifier.classify (object, S/slacken/Classifier.scala:439-454) on hit lists the caller holds
  * (host pointers; synchronous): TaxonCounts.toMap/totalKmers + resolveTree + the minHitGroups test for R lists of un-merged

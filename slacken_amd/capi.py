@@ -84,7 +84,10 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_coverage_create", "slk_coverage_add", "slk_coverage_fold", "slk_coverage_result", "slk_coverage_totals", "slk_coverage_budget",
            "slk_coverage_destroy",
            "slk_support_create", "slk_support_add", "slk_support_result", "slk_support_totals", "slk_support_destroy",
-           "slk_parse_tile_bytes", "slk_parse_device", "slk_parse_text", "slk_classify_text"]
+           "slk_parse_tile_bytes", "slk_parse_device", "slk_parse_text", "slk_classify_text",
+           "slk_pair_device", "slk_parse_text_paired", "slk_classify_text_paired"]
+
+PAIR_FIELDS = ("P", "mismatch", "consumed1", "consumed2", "R1", "R2", "n_bases", "n_mate_bases")   # slk_pair_record, in order
 
 FORMAT_FASTA, FORMAT_FASTQ = 0, 1   # SLK_FORMAT_* of the header
 
@@ -218,6 +221,12 @@ def lib():
     L.slk_classify_text.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, i32p, u8p,
                                     i32p, i32p, u64p, u64p, vp, u64p, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint64)]
+    L.slk_pair_device.argtypes = [vp, u8p, C.c_uint64, u64p, vp, u64p, u64p, C.c_uint64, u8p, C.c_uint64, u64p, vp, u64p, u64p, C.c_uint64, u64p]
+    L.slk_parse_text_paired.argtypes = [vp, u8p, C.c_uint64, C.c_int32, C.c_int32, u8p, C.c_uint64, C.c_int32, C.c_int32, u8p, u64p, u8p, u64p,
+                                        u64p, vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, u64p]
+    L.slk_classify_text_paired.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.c_int32, u8p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_double), C.c_int32, i32p, u8p, i32p, i32p, u64p, u64p, u64p, vp, u64p, vp,
+                                           C.c_uint64, C.c_uint64, u64p]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -909,6 +918,87 @@ class Stream:
             out["hit_offsets"] = hit_off[:R + 1]
             out["hits"] = hits[:int(hit_off[R])]
             out["num_hits"] = np.diff(hit_off[:R + 1].astype(np.int64)).astype(np.int32)
+        return out
+
+    def parse_text_paired_raw(self, data1, fmt1, final1, data2, fmt2, final2, bases_capacity=(None, None), records_capacity=(None, None), guard=0):
+        """slk_parse_text_paired as it stands: -> dict(bases, offsets, mate_bases, mate_offsets, title_pos, title_len and the fields of the
+        pair record: P, mismatch, consumed1, consumed2, R1, R2, n_bases, n_mate_bases).  The output arrays are allocated with `guard`
+        extra elements behind the capacities, filled with 0xA5 bytes, and returned whole under the keys raw_*."""
+        d1 = np.frombuffer(bytes(data1), np.uint8)
+        d2 = np.frombuffer(bytes(data2), np.uint8)
+        bcap = [d.size if c is None else int(c) for d, c in zip((d1, d2), bases_capacity)]
+        rcap = [d.size // 2 + 2 if c is None else int(c) for d, c in zip((d1, d2), records_capacity)]
+        A5 = 0xA5A5A5A5A5A5A5A5
+        bases, mbases = np.full(bcap[0] + guard, 0xA5, np.uint8), np.full(bcap[1] + guard, 0xA5, np.uint8)
+        offsets, moffsets = np.full(rcap[0] + 1 + guard, A5, np.uint64), np.full(rcap[1] + 1 + guard, A5, np.uint64)
+        tpos, tlen = np.full(rcap[0] + guard, A5, np.uint64), np.full(rcap[0] + guard, 0xA5A5A5A5, np.uint32)
+        pair = np.zeros(8, np.uint64)
+        rc = lib().slk_parse_text_paired(self.h, _ptr(d1), d1.size, _format(fmt1), 1 if final1 else 0, _ptr(d2), d2.size, _format(fmt2),
+                                         1 if final2 else 0, _ptr(bases), _ptr(offsets), _ptr(mbases), _ptr(moffsets), _ptr(tpos), _ptr(tlen),
+                                         bcap[0], rcap[0], bcap[1], rcap[1], _ptr(pair))
+        out = dict(raw_bases=bases, raw_offsets=offsets, raw_mate_bases=mbases, raw_mate_offsets=moffsets, raw_title_pos=tpos, raw_title_len=tlen,
+                   bases_capacity=tuple(bcap), records_capacity=tuple(rcap))
+        out.update({k: int(v) for k, v in zip(PAIR_FIELDS, pair)})
+        out["mismatch"] = bool(out["mismatch"])
+        if rc != 0:
+            err = SlackenError(rc, lib().slk_last_error().decode())
+            err.partial = out
+            raise err
+        P = out["P"]
+        out.update(bases=bases[:out["n_bases"]], offsets=offsets[:P + 1], mate_bases=mbases[:out["n_mate_bases"]], mate_offsets=moffsets[:P + 1],
+                   title_pos=tpos[:out["R1"]], title_len=tlen[:out["R1"]])
+        return out
+
+    def parse_text_paired(self, data1, fmt1, final1, data2, fmt2, final2):
+        """Two mate texts parsed and paired in lockstep on the device (slk_parse_text_paired) -> dict(titles: the stripped titles of ALL R1
+        records of text 1 -- the first P are the pairs' --, seqs, mate_seqs: lists of str for the P pairs, P, mismatch, consumed1,
+        consumed2, R1, R2)."""
+        data1 = bytes(data1)
+        o = self.parse_text_paired_raw(data1, fmt1, final1, data2, fmt2, final2)
+        off, moff = o["offsets"], o["mate_offsets"]
+        out = {k: o[k] for k in ("P", "mismatch", "consumed1", "consumed2", "R1", "R2")}
+        out["seqs"] = [o["bases"][int(off[r]):int(off[r + 1])].tobytes().decode("latin-1") for r in range(o["P"])]
+        out["mate_seqs"] = [o["mate_bases"][int(moff[r]):int(moff[r + 1])].tobytes().decode("latin-1") for r in range(o["P"])]
+        out["titles"] = [data1[int(p):int(p) + int(l)].decode("latin-1") for p, l in zip(o["title_pos"], o["title_len"])]
+        return out
+
+    def classify_text_paired(self, data1, fmt1, final1, data2, fmt2, final2, min_hit_groups=2, thresholds=(0.0,), with_hits=True,
+                             records_capacity=None, hits_capacity=None):
+        """classify_batch with mates on the pairs of two mate texts that are parsed and paired on the device (slk_classify_text_paired): the
+        result dict of classify_batch for the P pairs plus offsets, mate_offsets [P+1], title_pos, title_len, titles (all R1 records of
+        text 1, stripped) and the fields of the pair record."""
+        data1, data2 = bytes(data1), bytes(data2)
+        t1, t2 = np.frombuffer(data1, np.uint8), np.frombuffer(data2, np.uint8)
+        rcap = max(t1.size, t2.size) // 2 + 2 if records_capacity is None else int(records_capacity)
+        Cn = len(thresholds)
+        thr = (C.c_double * Cn)(*thresholds)
+        taxon, cls = np.zeros(Cn * rcap, np.int32), np.zeros(Cn * rcap, np.uint8)
+        nd, tk = np.zeros(rcap, np.int32), np.zeros(rcap, np.int32)
+        offsets, moffsets = np.zeros(rcap + 1, np.uint64), np.zeros(rcap + 1, np.uint64)
+        tpos, tlen = np.zeros(rcap, np.uint64), np.zeros(rcap, np.uint32)
+        hit_off = hits = None
+        cap = 0
+        if with_hits:
+            cap = hits_capacity if hits_capacity is not None else t1.size + t2.size + rcap + 1
+            hit_off, hits = np.zeros(rcap + 1, np.uint64), np.zeros(cap, HIT_DTYPE)
+        pair = np.zeros(8, np.uint64)
+        rc = lib().slk_classify_text_paired(self.index.h, self.h, _ptr(t1), t1.size, _format(fmt1), 1 if final1 else 0, _ptr(t2), t2.size,
+                                            _format(fmt2), 1 if final2 else 0, min_hit_groups, thr, Cn, _ptr(taxon), _ptr(cls), _ptr(nd), _ptr(tk),
+                                            _ptr(offsets), _ptr(moffsets), _ptr(tpos), _ptr(tlen), _ptr(hit_off), _ptr(hits), rcap, cap, _ptr(pair))
+        out = {k: int(v) for k, v in zip(PAIR_FIELDS, pair)}
+        out["mismatch"] = bool(out["mismatch"])
+        if rc != 0:
+            err = SlackenError(rc, lib().slk_last_error().decode())
+            err.partial = out
+            raise err
+        P, R1 = out["P"], out["R1"]
+        out.update(taxon=taxon[:Cn * P].reshape(Cn, P), classified=cls[:Cn * P].reshape(Cn, P), num_distinct=nd[:P], total_kmers=tk[:P],
+                   offsets=offsets[:P + 1], mate_offsets=moffsets[:P + 1], title_pos=tpos[:R1], title_len=tlen[:R1])
+        out["titles"] = [data1[int(p):int(p) + int(l)].decode("latin-1") for p, l in zip(out["title_pos"], out["title_len"])]
+        if with_hits:
+            out["hit_offsets"] = hit_off[:P + 1]
+            out["hits"] = hits[:int(hit_off[P])]
+            out["num_hits"] = np.diff(hit_off[:P + 1].astype(np.int64)).astype(np.int32)
         return out
 
     def classify_hits(self, hit_offsets, hits, distinct=None, min_hit_groups=2, thresholds=(0.0,)):

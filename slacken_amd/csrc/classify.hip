@@ -1044,3 +1044,65 @@ int32_t slk_classify_text(slk_index *ix, slk_stream *st, const uint8_t *text, ui
   HIPCHK(hipStreamSynchronize(st->s));
   return check_status(st);
 }
+
+// slk_classify_text for two mate files: both texts go up, textparse.hip parses text 1 into the stream's read buffers and text 2 into
+// its mate buffers and pairs them in lockstep; the first P records of either side are the batch (offsets[P] ends the reads of the
+// pairs, so the arrays serve as they lie), classified with mates as slk_classify_batch_device would.
+int32_t slk_classify_text_paired(slk_index *ix, slk_stream *st, const uint8_t *text1, uint64_t n1, int32_t format1, int32_t final1,
+                                 const uint8_t *text2, uint64_t n2, int32_t format2, int32_t final2, int32_t min_hit_groups,
+                                 const double *thresholds, int32_t C, int32_t *out_taxon, uint8_t *out_classified, int32_t *out_num_distinct,
+                                 int32_t *out_total_kmers, uint64_t *out_offsets, uint64_t *out_mate_offsets, uint64_t *out_title_pos,
+                                 uint32_t *out_title_len, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t records_capacity,
+                                 uint64_t hits_capacity, slk_pair_record *out_pair) {
+  int32_t rc = check_ready(ix, st, true);
+  if (rc) return rc;
+  if (!out_pair || !out_offsets || !out_mate_offsets || (n1 && !text1) || (n2 && !text2) ||
+      (records_capacity && (!out_taxon || !out_classified || !out_title_pos || !out_title_len)))
+    return fail(SLK_E_INVALID, "null argument");
+  uint64_t pair[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  memcpy(out_pair, pair, sizeof(pair));
+  if ((rc = check_thresholds(thresholds, C))) return rc;
+  if ((rc = check_parse_args(n1, format1))) return rc;
+  if ((rc = check_parse_args(n2, format2))) return rc;
+  if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "slk_classify_text_paired supports minimizers of up to 32 nt (one id column)");
+  rc = set_device(ix);
+  if (rc) return rc;
+  out_offsets[0] = out_mate_offsets[0] = 0;
+  if (out_hit_offsets) out_hit_offsets[0] = 0;
+  DrainOnExit drain(st);
+  rc = parse_pair_uploaded(st, PairText{text1, n1, format1, final1 != 0, n1, records_capacity},
+                           PairText{text2, n2, format2, final2 != 0, n2, records_capacity}, pair);
+  memcpy(out_pair, pair, sizeof(pair));   // (with SLK_E_CAPACITY too: the records_capacity the texts need)
+  if (rc) return rc;
+  const uint64_t P = pair[0], R1 = pair[4];
+  rc = copy_out(st, out_title_pos, st->parse_title_pos.p, R1 * 8);
+  if (!rc) rc = copy_out(st, out_title_len, st->parse_title_len.p, R1 * 4);
+  if (rc) return rc;
+  if (P == 0) return SLK_OK;
+  rc = copy_out(st, out_offsets, st->offsets.p, (P + 1) * 8);
+  if (!rc) rc = copy_out(st, out_mate_offsets, st->mate_offsets.p, (P + 1) * 8);
+  if (!rc) rc = validate_reads(out_offsets, out_mate_offsets, P);
+  if (!rc) rc = ensure_outputs(st, P, C);
+  if (rc) return rc;
+  const bool want_hits = out_hit_offsets != nullptr && out_hits != nullptr;
+  ClassifyCall whole;
+  whole.in = {st->bases.as<uint8_t>(), st->offsets.as<uint64_t>(), st->mate_bases.as<uint8_t>(), st->mate_offsets.as<uint64_t>(), P, pair[6], pair[7]};
+  whole.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
+               st->out_nh.as<int32_t>(), nullptr, P};
+  whole.thr = thresholds_of(thresholds, C); whole.C = C; whole.min_hit_groups = min_hit_groups; whole.want_hits = want_hits;
+  st->reran = false;
+  rc = run_classify(ix, st, whole);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(st->s));
+  rc = check_status(st);  // (re-runs the batch through the unbounded path if a taxon map overflowed)
+  if (rc) return rc;
+  rc = download_rows(st, HostRows{out_taxon, out_classified, out_num_distinct, out_total_kmers}, P, C);
+  if (rc) return rc;
+  if (out_hit_offsets) {
+    double th[3] = {0, 0, 0};
+    rc = assemble_hits(st, whole.in, want_hits, out_hit_offsets, out_hits, hits_capacity, false, th);
+    if (rc) return rc;
+  }
+  HIPCHK(hipStreamSynchronize(st->s));
+  return check_status(st);
+}

@@ -295,6 +295,7 @@ struct slk_stream {
   DevBuf pk_codes, pk_valid, pk_mate_codes, pk_mate_valid;   // slk_classify_batch_packed: the reads as they arrive (3 bits per base)
   Event ev_unpack;
   DevBuf parse_text, parse_scratch, parse_title_pos, parse_title_len, parse_counts;   // textparse.hip: the raw text, the passes' scratch, what comes back beside bases / offsets
+  DevBuf parse_text2, parse_title_pos2, parse_title_len2, parse_pair;   // paired text: the mates' text and titles (their bases / offsets are mate_bases / mate_offsets), the pair record
   Stream s2;                               // the segment pass and the wave pass run here, beside the long-lane pass on s
   Event ev_fork, ev_join;
   DevPtr<int32_t> d_status;        // device error bits of the fused kernels
@@ -438,6 +439,10 @@ int32_t download_rows(slk_stream *st, const HostRows &out, uint64_t R, int32_t C
 int32_t check_parse_args(uint64_t n, int32_t format);
 int32_t parse_uploaded(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, bool final, uint64_t bases_capacity,
                        uint64_t records_capacity, uint64_t counts[4]);
+// two texts parsed (text 1 into bases / offsets, text 2 into mate_bases / mate_offsets) and paired in lockstep; pair: the pair record
+// (slk_pair_record as eight words).  Synchronises st->s.  SLK_E_CAPACITY: pair holds the sizes both sides need.
+struct PairText { const uint8_t *text; uint64_t n; int32_t format; bool final; uint64_t bases_capacity, records_capacity; };
+int32_t parse_pair_uploaded(slk_stream *st, const PairText &t1, const PairText &t2, uint64_t pair[8]);
 
 inline int ceil_log2_u64(uint64_t x) {
   int b = 0;

@@ -26,6 +26,9 @@
 // space, one lane per record.
 // Scratch is sized from n alone (FASTQ: 8 bytes per byte of text for the line starts and the lines' destinations, every byte may be
 // a line; FASTA: 20 bytes per tile), kept on the stream and grown like its other buffers.
+// Two mate texts (slk_pair_device, slk_parse_text_paired): both are parsed as above, text 2 into the stream's mate
+// buffers, then a compare pass (one lane per record: titles stripped of "/1" and "/2" and compared, a ballot and one atomicMin per wave)
+// and a one-lane finish pass leave the pair record: how many leading records are mates and where either text's next chunk starts.
 #include "hostside.h"
 
 namespace {
@@ -390,6 +393,82 @@ __global__ void tp_empty_kernel(uint64_t *offsets, uint64_t *counts) {
   counts[0] = counts[1] = counts[2] = counts[3] = 0;
 }
 
+// ---- pairs ----------------------------------------------------------------------------------------------------------------------
+// Two parsed texts paired in lockstep (PairedInputReader.getFragments, S/kmers/input/InputReader.scala:105-131, while both files list
+// their mates in the same order): record i of text 1 and record i of text 2 are mates iff their titles are equal once ONE trailing
+// "/1" is taken off the first and ONE trailing "/2" off the second.  P = the leading records for which that holds.
+struct PairArgs {
+  const uint8_t *text1, *text2;
+  uint64_t n1, n2;
+  const uint64_t *title_pos1, *title_pos2;
+  uint32_t *title_len1;          // rewritten: every record of text 1 loses its "/1"
+  const uint32_t *title_len2;
+  const uint64_t *offsets1, *offsets2, *counts1, *counts2;
+  uint64_t R1, R2;
+  unsigned long long *pair;      // the pair record; word 0 is the first differing index while the compare pass runs
+};
+
+// a title as the parser left it, held inside text[0, n); without one trailing '/' d
+__device__ __forceinline__ void pt_title(const uint8_t *text, uint64_t n, uint64_t pos, uint32_t len, uint8_t d, uint64_t &p, uint32_t &l) {
+  p = umin64(pos, n);
+  l = (uint32_t)umin64(len, n - p);
+  if (l >= 2 && text[p + l - 2] == '/' && text[p + l - 1] == d) l -= 2;
+}
+// Titles lie at any alignment in two buffers: eight bytes at a time while eight are left INSIDE the title, single bytes for the rest --
+// no load reaches past the title's last byte, so none reaches past the text.
+__device__ __forceinline__ bool pt_equal(const uint8_t *a, const uint8_t *b, uint32_t len) {
+  uint32_t k = 0;
+  for (; k + 8 <= len; k += 8) {
+    uint64_t x, y;
+    __builtin_memcpy(&x, a + k, 8);
+    __builtin_memcpy(&y, b + k, 8);
+    if (x != y) return false;
+  }
+  for (; k < len; k++)
+    if (a[k] != b[k]) return false;
+  return true;
+}
+
+// One lane per record of text 1: it strips its title and, below min(R1, R2), compares it with its mate's.  A wave finds its first
+// differing lane with a ballot and sends one atomicMin.
+__global__ void __launch_bounds__(TP_BLOCK) pt_compare_kernel(PairArgs A) {
+  const uint64_t M = umin64(A.R1, A.R2);
+  for (uint64_t base = (uint64_t)blockIdx.x * TP_BLOCK; base < A.R1; base += (uint64_t)gridDim.x * TP_BLOCK) {
+    const uint64_t i = base + threadIdx.x;
+    bool differ = false;
+    if (i < A.R1) {
+      const uint32_t len1 = A.title_len1[i];
+      uint64_t p1;
+      uint32_t l1;
+      pt_title(A.text1, A.n1, A.title_pos1[i], len1, '1', p1, l1);
+      if (i < M) {
+        uint64_t p2;
+        uint32_t l2;
+        pt_title(A.text2, A.n2, A.title_pos2[i], A.title_len2[i], '2', p2, l2);
+        differ = l1 != l2 || !pt_equal(A.text1 + p1, A.text2 + p2, l1);
+      }
+      if (l1 != len1) A.title_len1[i] = l1;
+    }
+    const unsigned long long ballot = __ballot(differ);
+    if (ballot && (threadIdx.x & 63) == 0) atomicMin(A.pair, (unsigned long long)(i + (__ffsll(ballot) - 1)));
+  }
+}
+
+// the byte that opens the record whose title starts at pos: the '@' or '>' before it, or 0 for a FASTA record that opens the text bare
+__device__ __forceinline__ uint64_t pt_opener(uint64_t pos) { return pos ? pos - 1 : 0; }
+
+__global__ void pt_finish_kernel(PairArgs A) {
+  const uint64_t M = umin64(A.R1, A.R2), P = umin64(A.pair[0], M);
+  A.pair[0] = P;
+  A.pair[1] = P < M ? 1 : 0;
+  A.pair[2] = A.R1 > P ? pt_opener(A.title_pos1[P]) : A.counts1[2];
+  A.pair[3] = A.R2 > P ? pt_opener(A.title_pos2[P]) : A.counts2[2];
+  A.pair[4] = A.R1;
+  A.pair[5] = A.R2;
+  A.pair[6] = A.offsets1[P];
+  A.pair[7] = A.offsets2[P];
+}
+
 }  // namespace
 
 namespace slk {
@@ -475,6 +554,75 @@ int32_t parse_uploaded(slk_stream *st, const uint8_t *text, uint64_t n, int32_t 
   return SLK_OK;
 }
 
+// the compare and finish passes over the outputs of two parses, queued on the stream
+static int32_t launch_pair(slk_stream *st, const PairArgs &A) {
+  hipStream_t s = st->s;
+  HIPCHK(hipMemsetAsync(A.pair, 0xFF, 8, s));   // (no differing index yet: the finish pass takes the smaller of this word and min(R1, R2))
+  if (A.R1) {
+    const unsigned blocks = (unsigned)std::min<uint64_t>((A.R1 + TP_BLOCK - 1) / TP_BLOCK, TP_MAX_GRID);
+    hipLaunchKernelGGL(pt_compare_kernel, dim3(blocks), dim3(TP_BLOCK), 0, s, A);
+  }
+  hipLaunchKernelGGL(pt_finish_kernel, dim3(1), dim3(1), 0, s, A);
+  HIPCHK(hipGetLastError());
+  return SLK_OK;
+}
+
+static uint64_t parse_scratch_bytes(uint64_t n, int32_t format, bool final) {   // what launch_parse will ask of parse_scratch
+  const bool fastq = format == SLK_FORMAT_FASTQ;
+  const uint64_t ntiles = ((fastq || !final ? n : n + 1) + TP_TILE - 1) / TP_TILE, nlt_max = n / TP_BLOCK + 1;
+  return 4 * ((fastq ? 1 : 5) * (ntiles + 1) + (fastq ? 2 * (n + 2) + 2 * (nlt_max + 1) : 0));
+}
+
+int32_t parse_pair_uploaded(slk_stream *st, const PairText &t1, const PairText &t2, uint64_t pair[8]) {
+  // every buffer at its size before the first launch: growing one frees it, and that waits for the device
+  HIPCHK(st->parse_text.ensure(std::max<uint64_t>(t1.n, 16)));
+  HIPCHK(st->parse_text2.ensure(std::max<uint64_t>(t2.n, 16)));
+  HIPCHK(st->bases.ensure(std::max<uint64_t>((t1.bases_capacity + 15) / 16 * 16, 16)));
+  HIPCHK(st->mate_bases.ensure(std::max<uint64_t>((t2.bases_capacity + 15) / 16 * 16, 16)));
+  HIPCHK(st->offsets.ensure((t1.records_capacity + 1) * 8));
+  HIPCHK(st->mate_offsets.ensure((t2.records_capacity + 1) * 8));
+  HIPCHK(st->parse_title_pos.ensure(std::max<uint64_t>(t1.records_capacity, 1) * 8));
+  HIPCHK(st->parse_title_len.ensure(std::max<uint64_t>(t1.records_capacity, 1) * 4));
+  HIPCHK(st->parse_title_pos2.ensure(std::max<uint64_t>(t2.records_capacity, 1) * 8));
+  HIPCHK(st->parse_title_len2.ensure(std::max<uint64_t>(t2.records_capacity, 1) * 4));
+  HIPCHK(st->parse_counts.ensure(8 * 8));
+  HIPCHK(st->parse_pair.ensure(8 * 8));
+  HIPCHK(st->parse_scratch.ensure(std::max(parse_scratch_bytes(t1.n, t1.format, t1.final), parse_scratch_bytes(t2.n, t2.format, t2.final))));
+  uint64_t *const d_counts = st->parse_counts.as<uint64_t>();
+  int32_t rc = copy_in(st, st->parse_text.p, t1.text, t1.n);
+  if (!rc) rc = copy_in(st, st->parse_text2.p, t2.text, t2.n);
+  // (the two parses share parse_scratch: one after the other on the stream)
+  if (!rc)
+    rc = launch_parse(st, st->parse_text.as<uint8_t>(), t1.n, t1.format, t1.final, st->bases.as<uint8_t>(), t1.bases_capacity, st->offsets.as<uint64_t>(),
+                      st->parse_title_pos.as<uint64_t>(), st->parse_title_len.as<uint32_t>(), t1.records_capacity, d_counts);
+  if (!rc)
+    rc = launch_parse(st, st->parse_text2.as<uint8_t>(), t2.n, t2.format, t2.final, st->mate_bases.as<uint8_t>(), t2.bases_capacity,
+                      st->mate_offsets.as<uint64_t>(), st->parse_title_pos2.as<uint64_t>(), st->parse_title_len2.as<uint32_t>(), t2.records_capacity,
+                      d_counts + 4);
+  uint64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (!rc) rc = copy_out(st, counts, d_counts, 8 * 8);
+  if (rc) return rc;
+  if (counts[3] || counts[7]) {
+    pair[4] = counts[0]; pair[5] = counts[4]; pair[6] = counts[1]; pair[7] = counts[5];
+    return fail(SLK_E_CAPACITY, "the texts hold %llu records of %llu bases and %llu records of %llu bases, the capacities are %llu, %llu and %llu, %llu",
+                (unsigned long long)counts[0], (unsigned long long)counts[1], (unsigned long long)counts[4], (unsigned long long)counts[5],
+                (unsigned long long)t1.records_capacity, (unsigned long long)t1.bases_capacity, (unsigned long long)t2.records_capacity,
+                (unsigned long long)t2.bases_capacity);
+  }
+  PairArgs A{};
+  A.text1 = st->parse_text.as<uint8_t>(); A.text2 = st->parse_text2.as<uint8_t>();
+  A.n1 = t1.n; A.n2 = t2.n;
+  A.title_pos1 = st->parse_title_pos.as<uint64_t>(); A.title_pos2 = st->parse_title_pos2.as<uint64_t>();
+  A.title_len1 = st->parse_title_len.as<uint32_t>(); A.title_len2 = st->parse_title_len2.as<uint32_t>();
+  A.offsets1 = st->offsets.as<uint64_t>(); A.offsets2 = st->mate_offsets.as<uint64_t>();
+  A.counts1 = d_counts; A.counts2 = d_counts + 4;
+  A.R1 = counts[0]; A.R2 = counts[4];
+  A.pair = st->parse_pair.as<unsigned long long>();
+  rc = launch_pair(st, A);
+  if (!rc) rc = copy_out(st, pair, st->parse_pair.p, 8 * 8);
+  return rc;
+}
+
 }  // namespace slk
 
 extern "C" uint32_t slk_parse_tile_bytes(void) { return TP_TILE; }
@@ -513,6 +661,56 @@ extern "C" int32_t slk_parse_text(slk_stream *st, const uint8_t *text, uint64_t 
   if (!rc) rc = copy_out(st, out_bases, st->bases.p, counts[1]);
   if (!rc) rc = copy_out(st, out_title_pos, st->parse_title_pos.p, R * 8);
   if (!rc) rc = copy_out(st, out_title_len, st->parse_title_len.p, R * 4);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(st->s));
+  return SLK_OK;
+}
+
+extern "C" int32_t slk_pair_device(slk_stream *st, const uint8_t *d_text1, uint64_t n1, const uint64_t *d_title_pos1, uint32_t *d_title_len1,
+                                   const uint64_t *d_offsets1, const uint64_t *d_counts1, uint64_t R1, const uint8_t *d_text2, uint64_t n2,
+                                   const uint64_t *d_title_pos2, const uint32_t *d_title_len2, const uint64_t *d_offsets2,
+                                   const uint64_t *d_counts2, uint64_t R2, uint64_t *d_pair) {
+  if (!st || !d_offsets1 || !d_offsets2 || !d_counts1 || !d_counts2 || !d_pair || (R1 && (!d_text1 || !d_title_pos1 || !d_title_len1)) ||
+      (R2 && (!d_text2 || !d_title_pos2 || !d_title_len2)))
+    return fail(SLK_E_INVALID, "null argument");
+  if (n1 >= (1ULL << 32) || n2 >= (1ULL << 32)) return fail(SLK_E_INVALID, "a paired call takes less than 2^32 bytes of either text");
+  int32_t rc = set_device(st->ix);
+  if (rc) return rc;
+  PairArgs A{};
+  A.text1 = d_text1; A.text2 = d_text2; A.n1 = n1; A.n2 = n2;
+  A.title_pos1 = d_title_pos1; A.title_pos2 = d_title_pos2; A.title_len1 = d_title_len1; A.title_len2 = d_title_len2;
+  A.offsets1 = d_offsets1; A.offsets2 = d_offsets2; A.counts1 = d_counts1; A.counts2 = d_counts2;
+  A.R1 = R1; A.R2 = R2;
+  A.pair = (unsigned long long *)d_pair;
+  return launch_pair(st, A);
+}
+
+extern "C" int32_t slk_parse_text_paired(slk_stream *st, const uint8_t *text1, uint64_t n1, int32_t format1, int32_t final1, const uint8_t *text2,
+                                         uint64_t n2, int32_t format2, int32_t final2, uint8_t *out_bases, uint64_t *out_offsets,
+                                         uint8_t *out_mate_bases, uint64_t *out_mate_offsets, uint64_t *out_title_pos, uint32_t *out_title_len,
+                                         uint64_t bases_capacity1, uint64_t records_capacity1, uint64_t bases_capacity2,
+                                         uint64_t records_capacity2, slk_pair_record *out_pair) {
+  if (!st || !out_offsets || !out_mate_offsets || !out_pair || (n1 && !text1) || (n2 && !text2) || (bases_capacity1 && !out_bases) ||
+      (bases_capacity2 && !out_mate_bases) || (records_capacity1 && (!out_title_pos || !out_title_len)))
+    return fail(SLK_E_INVALID, "null argument");
+  uint64_t pair[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  memcpy(out_pair, pair, sizeof(pair));
+  int32_t rc = check_parse_args(n1, format1);
+  if (!rc) rc = check_parse_args(n2, format2);
+  if (rc) return rc;
+  if ((rc = set_device(st->ix))) return rc;
+  DrainOnExit drain(st);
+  rc = parse_pair_uploaded(st, PairText{text1, n1, format1, final1 != 0, bases_capacity1, records_capacity1},
+                           PairText{text2, n2, format2, final2 != 0, bases_capacity2, records_capacity2}, pair);
+  memcpy(out_pair, pair, sizeof(pair));   // (with SLK_E_CAPACITY too: what the capacities would have to be)
+  if (rc) return rc;
+  const uint64_t P = pair[0], R1 = pair[4];
+  rc = copy_out(st, out_offsets, st->offsets.p, (P + 1) * 8);
+  if (!rc) rc = copy_out(st, out_mate_offsets, st->mate_offsets.p, (P + 1) * 8);
+  if (!rc) rc = copy_out(st, out_bases, st->bases.p, pair[6]);
+  if (!rc) rc = copy_out(st, out_mate_bases, st->mate_bases.p, pair[7]);
+  if (!rc) rc = copy_out(st, out_title_pos, st->parse_title_pos.p, R1 * 8);
+  if (!rc) rc = copy_out(st, out_title_len, st->parse_title_len.p, R1 * 4);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(st->s));
   return SLK_OK;

@@ -286,6 +286,7 @@ class TextChunks {
   const char *map_ = nullptr;   // the plain file being read, or null
   size_t map_len_ = 0, map_pos_ = 0;
 
+  friend class PairedTextChunks;
   static bool plain_file(const std::string &file) {
     if (!ByteSource::regular_file(file) || ends_with(file, ".gz") || ends_with(file, ".bz2")) return false;
     FILE *f = fopen(file.c_str(), "rb");
@@ -444,6 +445,263 @@ void classify_text_stream(DeviceIndex &dev, const std::vector<std::string> &file
   (void)slk_stream_set_merged_hits(dev.st, 0);
   order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_batches << " chunks parsed on the device by " << lanes.size() << " classify thread(s)" << std::endl;
+  std::cerr << total << " fragments" << std::endl;
+}
+
+// ---- --device-pairs: the device finds the records of both mate files and pairs them (slk_classify_text_paired) ----------
+// Where the next chunk of either file starts is the device's answer -- it depends on how many leading records of the two chunks are
+// mates --, so the calls of one file pair follow each other; several file pairs run side by side on different workers.
+
+// The two texts of one file pair.  A plain file is mapped and advanced in place; a compressed file or a pipe goes through ByteSource
+// into a pinned buffer, with what the call before left over in front.  A side takes new bytes only while it holds less than its
+// target (the chunk size; doubled while a record does not fit), so the side that runs ahead in records does not grow without bound.
+class PairedTextChunks {
+ public:
+  static constexpr size_t MAX_CHUNK = TextChunks::MAX_CHUNK;
+  struct Side {
+    std::string file;
+    bool fastq = false, final = false;
+    const char *p = nullptr;   // the chunk of the next call
+    size_t n = 0;
+   private:
+    friend class PairedTextChunks;
+    const char *map = nullptr;
+    size_t map_len = 0, map_pos = 0, target = 0;
+    bool mapped = false, eof = false;
+    std::unique_ptr<ByteSource> src;
+    PinnedText buf;
+    size_t held = 0;   // bytes of buf in use
+  };
+ private:
+  Side side_[2];
+  const size_t chunk_ = io_chunk_bytes();
+
+  void open(Side &s, const std::string &file) {
+    s.file = file;
+    s.fastq = RecordStream::is_fastq_name(file);
+    s.target = chunk_;
+    if (!TextChunks::plain_file(file)) { s.src = std::make_unique<ByteSource>(file); return; }
+    s.mapped = true;
+    const int fd = ::open(file.c_str(), O_RDONLY);
+    struct stat sb;
+    if (fd < 0 || fstat(fd, &sb) != 0) die("cannot open " + file);
+    s.map_len = (size_t)sb.st_size;
+    void *m = s.map_len ? mmap(nullptr, s.map_len, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+    close(fd);
+    if (s.map_len && m == MAP_FAILED) die("cannot map " + file);
+    if (s.map_len) madvise(m, s.map_len, MADV_SEQUENTIAL);
+    s.map = (const char *)m;
+  }
+  void fill(Side &s) {
+    if (s.mapped) {
+      const size_t left = s.map_len - s.map_pos;
+      s.n = std::min(s.target, left);
+      s.final = s.n == left;
+      static const char empty = 0;
+      s.p = s.map ? s.map + s.map_pos : &empty;
+      return;
+    }
+    while (!s.eof && s.held < s.target) {
+      s.buf.ensure(s.target, s.held);
+      const size_t got = s.src->read(s.buf.p + s.held, s.target - s.held);
+      if (got == 0) s.eof = true;
+      s.held += got;
+    }
+    s.buf.ensure(1, 0);
+    s.p = s.buf.p;
+    s.n = s.held;
+    s.final = s.eof;
+  }
+ public:
+  PairedTextChunks(const std::string &file1, const std::string &file2) { open(side_[0], file1); open(side_[1], file2); }
+  PairedTextChunks(const PairedTextChunks &) = delete;
+  ~PairedTextChunks() { for (Side &s : side_) if (s.map) munmap((void *)s.map, s.map_len); }
+  Side &operator[](int i) { return side_[i]; }
+  void fill() { fill(side_[0]); fill(side_[1]); }
+  // after a call: side i starts `consumed` bytes further on; grow: no record of it fitted its chunk
+  void advance(int i, size_t consumed, bool grow) {
+    Side &s = side_[i];
+    if (grow) {
+      if (s.n >= MAX_CHUNK)
+        die("a record of " + s.file + " does not fit the largest chunk the device parser takes (1 GiB): classify this input without --device-pairs");
+      s.target = std::min(2 * std::max(s.n, chunk_), MAX_CHUNK);
+    } else {
+      s.target = chunk_;
+    }
+    if (s.mapped) { s.map_pos += consumed; return; }
+    if (consumed) memmove(s.buf.p, s.buf.p + consumed, s.held - consumed);
+    s.held -= consumed;
+  }
+};
+
+// Results are handed on in a fixed rotation over the workers' slots, whichever worker is done first: slot 0's next batch, slot 1's
+// next batch, ...; a slot whose file pairs are through leaves the rotation when its turn comes.  The order of the output follows from
+// the input alone.
+class RotatingHandOver {
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::vector<char> alive_;
+  size_t turn_ = 0;
+  std::exception_ptr failure_;
+  std::atomic<bool> failed_{false};
+  void pass_on() {
+    for (size_t k = 1; k <= alive_.size(); k++) {
+      const size_t t = (turn_ + k) % alive_.size();
+      if (alive_[t]) { turn_ = t; break; }
+    }
+    cv_.notify_all();
+  }
+ public:
+  explicit RotatingHandOver(size_t slots) : alive_(slots, 1) {}
+  bool failed() const { return failed_; }
+  template <class Hand> void deliver(size_t slot, Hand hand) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return turn_ == slot || failure_; });
+    if (!failure_) hand();
+    pass_on();
+  }
+  void retire(size_t slot) {
+    std::unique_lock<std::mutex> lk(mu_);
+    cv_.wait(lk, [&] { return turn_ == slot || failure_; });
+    alive_[slot] = 0;
+    pass_on();
+  }
+  void fail(std::exception_ptr e) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!failure_) failure_ = e;
+    failed_ = true;
+    cv_.notify_all();
+  }
+  void rethrow_failure() { if (failure_) std::rethrow_exception(failure_); }
+};
+
+// the title of the record that opens at text[at] (its '@' or '>', or a FASTA title at the very start of the text), for messages
+inline std::string title_at(const char *text, size_t n, size_t at) {
+  size_t a = at < n && (text[at] == '@' || text[at] == '>') ? at + 1 : at, b = a;
+  while (b < n && text[b] != ' ' && text[b] != '\n' && text[b] != '\r') b++;
+  return std::string(text + a, b - a);
+}
+
+// classify_stream for pairs of mate files with the records found and paired on the device: a replicated table, one id column (the
+// command line refuses the rest).  A batch is what one call paired; its FragmentBatch holds offsets, mate offsets and the stripped
+// titles, no bases.  The device route is the lockstep walk only: mates out of order end the run.
+template <class F>
+void classify_paired_text_stream(DeviceIndex &dev, const std::vector<std::string> &files, int min_hits, const std::vector<double> &thresholds,
+                                 bool want_hits, F f, RepeatedTitles *rep = nullptr, bool merged_hits = false) {
+  if (dev.sharded) die("internal: classify_paired_text_stream runs on a replicated table");
+  const size_t npairs = files.size() / 2;
+  const int C = (int)thresholds.size();
+  std::atomic<size_t> total{0}, n_calls{0};
+  struct Lane { slk_index *ix = nullptr; slk_stream *st = nullptr; };
+  const char *wenv = getenv("SLK_CLASSIFY_THREADS");
+  const size_t per_dev = std::max<size_t>(1, std::min<size_t>(8, wenv ? (size_t)atol(wenv) : 2));
+  std::vector<Lane> lanes(std::max<size_t>(1, std::min(per_dev * dev.ixs.size(), npairs)));
+  RotatingHandOver order(lanes.size());
+
+  // file 2 is through: what file 1 still holds has no partner -- the inner join drops it, and its titles are kept in case one of them
+  // is also a fragment's (seqio.hpp: FragmentSource, titles.hpp)
+  auto drain_file1 = [&](const Lane &lane, PairedTextChunks &in) {
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> offs, tpos;
+    std::vector<uint32_t> tlen;
+    for (;;) {
+      in.fill();
+      PairedTextChunks::Side &a = in[0];
+      if (a.n == 0 && a.final) return;
+      uint64_t R = 0, nb = 0, consumed = 0;
+      size_t rcap = a.n / 64 + 1024;
+      bases.resize(a.n);
+      for (int attempt = 0;; attempt++) {
+        offs.resize(rcap + 1); tpos.resize(rcap); tlen.resize(rcap);
+        const int32_t rc = slk_parse_text(lane.st, (const uint8_t *)a.p, a.n, a.fastq ? SLK_FORMAT_FASTQ : SLK_FORMAT_FASTA, a.final ? 1 : 0, bases.data(),
+                                          offs.data(), tpos.data(), tlen.data(), bases.size(), rcap, &R, &nb, &consumed);
+        if (rc == SLK_E_CAPACITY && attempt == 0 && R > rcap) { rcap = R; continue; }
+        if (rc != SLK_OK) die(std::string("slk_parse_text: ") + slk_last_error());
+        break;
+      }
+      if (rep) for (uint64_t r = 0; r < R; r++) rep->add_unmatched(title_hash(remove_suffix(std::string_view(a.p + tpos[r], tlen[r]), "/1")));
+      in.advance(0, consumed, consumed == 0 && !a.final);
+    }
+  };
+
+  auto one_pair = [&](const Lane &lane, size_t slot, const std::string &file1, const std::string &file2) {
+    PairedTextChunks in(file1, file2);
+    std::vector<int32_t> nd, tk;
+    std::vector<uint64_t> tpos;
+    std::vector<uint32_t> tlen;
+    uint64_t done = 0;   // pairs of this file pair so far
+    while (!order.failed()) {
+      in.fill();
+      PairedTextChunks::Side &a = in[0], &b2 = in[1];
+      if (a.n == 0 && a.final) return;   // file 1 is through: what file 2 still holds is dropped
+      if (b2.n == 0 && b2.final) { drain_file1(lane, in); return; }
+      n_calls++;
+      auto out = new_classified_batch();
+      ClassifiedBatch &b = *out;
+      b.frags = new_fragment_batch(1);
+      b.C = C;
+      FragmentBatch &fb = *b.frags;
+      fb.paired = true;
+      if (want_hits) b.reserve_hits(a.n + b2.n + 1);   // (a span per base at most, and a border per pair)
+      slk_pair_record pr{};
+      size_t rcap = std::max(a.n, b2.n) / 64 + 1024;   // records the arrays hold: a guess, and what the call asks for if the guess was short
+      for (int attempt = 0;; attempt++) {
+        b.taxon.resize((size_t)C * rcap); b.classified.resize((size_t)C * rcap); nd.resize(rcap); tk.resize(rcap);
+        fb.offs.resize(rcap + 1); fb.mate_offs.resize(rcap + 1); tpos.resize(rcap); tlen.resize(rcap); b.hit_offs.resize(rcap + 1);
+        const int32_t rc = slk_classify_text_paired(lane.ix, lane.st, (const uint8_t *)a.p, a.n, a.fastq ? SLK_FORMAT_FASTQ : SLK_FORMAT_FASTA, a.final ? 1 : 0,
+                                                    (const uint8_t *)b2.p, b2.n, b2.fastq ? SLK_FORMAT_FASTQ : SLK_FORMAT_FASTA, b2.final ? 1 : 0, min_hits,
+                                                    thresholds.data(), C, b.taxon.data(), b.classified.data(), nd.data(), tk.data(), fb.offs.data(),
+                                                    fb.mate_offs.data(), tpos.data(), tlen.data(), b.hit_offs.data(), want_hits ? b.hits.get() : nullptr, rcap,
+                                                    a.n + b2.n + 1, &pr);
+        if (rc == SLK_E_CAPACITY && attempt == 0 && std::max(pr.records1, pr.records2) > rcap) { rcap = std::max(pr.records1, pr.records2); continue; }
+        if (rc != SLK_OK) die(std::string("slk_classify_text_paired: ") + slk_last_error());
+        break;
+      }
+      const uint64_t P = pr.pairs;
+      if (pr.mismatch)
+        die("mates out of order in " + a.file + " and " + b2.file + ": pair " + std::to_string(done + P + 1) + " has the titles '" +
+            std::string(a.p + tpos[P], tlen[P]) + "' and '" + std::string(remove_suffix(title_at(b2.p, b2.n, pr.consumed2), "/2")) +
+            "'; run without --device-pairs (the host route joins mates that are out of order)");
+      if (pr.consumed1 > a.n || pr.consumed2 > b2.n) die("internal: the device consumed more than a chunk holds");
+      if (P) {
+        b.taxon.resize((size_t)C * P); b.classified.resize((size_t)C * P);
+        fb.offs.resize(P + 1); fb.mate_offs.resize(P + 1); b.hit_offs.resize(P + 1);
+        fb.title_off.resize(P + 1);
+        fb.title_off[0] = 0;
+        for (uint64_t r = 0; r < P; r++) fb.title_off[r + 1] = fb.title_off[r] + tlen[r];
+        fb.titles.resize(fb.title_off[P]);
+        for (uint64_t r = 0; r < P; r++) memcpy(&fb.titles[fb.title_off[r]], a.p + tpos[r], tlen[r]);
+        total += P;
+        done += P;
+        order.deliver(slot, [&] { f(std::shared_ptr<const ClassifiedBatch>(std::move(out))); });
+      }
+      // a side without a record and without a consumed byte must grow, unless it is final (then it is through: the checks above)
+      in.advance(0, pr.consumed1, pr.records1 == 0 && pr.consumed1 == 0 && !a.final);
+      in.advance(1, pr.consumed2, pr.records2 == 0 && pr.consumed2 == 0 && !b2.final);
+    }
+  };
+  auto work = [&](size_t slot) {
+    try {
+      for (size_t k = slot; k < npairs && !order.failed(); k += lanes.size()) one_pair(lanes[slot], slot, files[2 * k], files[2 * k + 1]);
+      order.retire(slot);
+    } catch (...) {
+      order.fail(std::current_exception());
+    }
+  };
+  for (size_t i = 0; i < lanes.size(); i++) {
+    lanes[i].ix = dev.ixs[i % dev.ixs.size()];
+    lanes[i].st = dev.st;
+    if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
+    SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merged_hits && want_hits ? 1 : 0));
+  }
+  std::vector<std::thread> workers;
+  for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&work, i] { work(i); });
+  work(0);
+  for (auto &t : workers) t.join();
+  for (size_t i = 1; i < lanes.size(); i++) slk_stream_destroy(lanes[i].st);
+  (void)slk_stream_set_merged_hits(dev.st, 0);
+  order.rethrow_failure();
+  if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_calls << " paired calls on " << lanes.size() << " classify thread(s)" << std::endl;
   std::cerr << total << " fragments" << std::endl;
 }
 

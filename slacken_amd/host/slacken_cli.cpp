@@ -231,6 +231,7 @@ struct ClassifyOpts {
   std::vector<int> devices{0};  // --devices: the GPUs that share the reads (table replicated on each)
   bool shard_table = false;     // --shard-table: the table is spread over the devices instead (a library beyond one GPU's memory)
   bool device_parse = false;    // --device-parse: the raw text goes to the device, which finds the records (classify_text_stream)
+  bool device_pairs = false;    // --device-pairs: both mate files' text goes to the device, which finds and pairs the records (classify_paired_text_stream)
   // classify2 (Slacken.scala:199-260)
   std::string library, rank = "species";
   int min_count = -1, min_distinct = -1, reads = -1;
@@ -264,6 +265,10 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
       if (two_step) die("--device-parse is for classify (classify2 reads its input through the host parser)");
       o.device_parse = true;
     }
+    else if (a == "--device-pairs") {
+      if (two_step) die("--device-pairs is for classify (classify2 reads its input through the host parser)");
+      o.device_pairs = true;
+    }
     else if (two_step && (a == "-l" || a == "--library")) o.library = a.next();
     else if (two_step && a == "--rank") o.rank = a.next();
     else if (two_step && (a == "-C" || a == "--min-count")) o.min_count = std::stoi(a.next());
@@ -288,6 +293,9 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
                  : "usage: classify -i INDEX -o OUTPUT [-p] [-c T...] [--min-hits N] [--sample-regex RE] FILES");
   if (two_step && o.gold_set.empty() && (o.classify_with_gold || !o.promote_rank.empty()))
     die("--classify-with-gold and --promote-gold-set qualify a gold set: give one with -g FILE");
+  if (o.device_pairs && o.device_parse) die("--device-pairs and --device-parse exclude each other: --device-pairs is the device route for paired input (-p), --device-parse the one for unpaired input");
+  if (o.device_pairs && !o.paired) die("--device-pairs pairs the records of two mate files: give -p and pairs of files (--device-parse is the device route for unpaired input)");
+  if (o.device_pairs && o.shard_table) die("--device-pairs needs the whole table on the device that parses (not --shard-table)");
   if (o.device_parse && o.paired) die("--device-parse takes unpaired input (the mates of paired reads are joined by title, on the host)");
   if (o.device_parse && o.shard_table) die("--device-parse needs the whole table on the device that parses (not --shard-table)");
   if (o.thresholds.empty()) o.thresholds.push_back(0.0);
@@ -336,7 +344,10 @@ static void classify_and_write(DeviceIndex &dev, const IndexParams &ip, const Ta
   oo.with_unclassified = o.with_unclassified; oo.detailed = o.detailed; oo.k = ip.k;
   Timer t("Classify reads");
   OutputSink sink(oo, tax, host_threads());
-  if (o.device_parse)
+  if (o.device_pairs)
+    classify_paired_text_stream(dev, o.files, o.min_hits, o.thresholds, o.detailed, [&](std::shared_ptr<const ClassifiedBatch> b) { sink.submit(std::move(b)); },
+                                &sink.repeated(), true);
+  else if (o.device_parse)
     classify_text_stream(dev, o.files, o.min_hits, o.thresholds, o.detailed, [&](std::shared_ptr<const ClassifiedBatch> b) { sink.submit(std::move(b)); }, true);
   else
     classify_stream(dev, o.files, o.paired, o.min_hits, o.thresholds, false, o.detailed,   // (hit lists only feed the per-read lines)
@@ -351,6 +362,8 @@ static int cmd_classify(int argc, char **argv) {
   ClassifyOpts o = parse_classify_opts(argc, argv, false);
   if (o.device_parse && read_index_params(o.index).m > 32)
     die("--device-parse supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
+  if (o.device_pairs && read_index_params(o.index).m > 32)
+    die("--device-pairs supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
   LoadedIndex lib(o.index, o.devices, o.shard_table);
   classify_and_write(lib.dev, lib.ip, lib.tax, o);
   return 0;
@@ -1265,6 +1278,8 @@ static const char *HELP =
     "                         minimizers travel to their owners and taxa back): for a library beyond one GPU's memory\n"
     "      --device-parse     classify: send the files' text to the device as it is and find the records there (unpaired input, a\n"
     "                         replicated table, m <= 32; `parse --device FILE` shows what the device finds); the default parses on the host\n"
+    "      --device-pairs     classify -p: send both mate files' text to the device, which finds the records and pairs them in lockstep\n"
+    "                         (a replicated table, m <= 32); mates that are out of order end the run -- the default joins them on the host\n"
     "  FILES                  FASTA / FASTQ, plain, .gz or .bz2; @list.txt names a file of file names\n"
     "options of classify2 (Slacken.scala:199-260): --library DIR (DIR/library/**/*.fna, DIR/seqid2taxid.map), --rank RANK (species),\n"
     "  -R, --reads N (100) | -C, --min-count N | -D, --min-distinct N, --init-confidence X (0.15)\n"
