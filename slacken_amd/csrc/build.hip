@@ -9,11 +9,12 @@
 //
 // Work decomposition: the host cuts every sequence into chunks of CHUNK_WINDOWS k-mer windows that overlap by k-1 bases (the
 // same overlap the reference's indexed-FASTA reader uses, FileInputs.scala:240-262): the SET of window minimizers is unchanged.
-// One lane per chunk, 64 chunks per wave in lockstep; minimizers go to a wave-shared LDS queue and are inserted 64 at a time,
-// one lane per record, so that the latency of the atomics is paid once per 64 records.
+// One lane per chunk, 64 chunks per wave in lockstep (chunkscan.h, without priming); minimizers go to a wave-shared LDS queue
+// (wavetools.h: WaveQueue) and are inserted 64 at a time, one lane per record, so that the latency of the atomics is paid once per
+// 64 records.
 #include <hip/hip_runtime.h>
 
-#include "engine.h"
+#include "chunkscan.h"
 #include "tablebuild.h"
 
 namespace slk {
@@ -37,97 +38,31 @@ __global__ void __launch_bounds__(BW * 64) build_kernel(ScanParams P, TableBuild
   const uint32_t tid = threadIdx.x, lane = tid & 63;
   const uint32_t wib = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t stride = BW * 64;
-  const int w = P.w, k = P.k, m = P.m;
+  const int w = P.w;
   const uint64_t c = (uint64_t)blockIdx.x * stride + tid;
   const uint32_t len = c < nchunks ? chunk_len[c] : 0;
   const uint64_t start = c < nchunks ? chunk_start[c] : 0;
   const int32_t taxon = c < nchunks ? chunk_taxon[c] : 0;
-  uint32_t maxlen = len;
-  for (int o = 32; o > 0; o >>= 1) maxlen = max(maxlen, (uint32_t)__shfl_xor((int)maxlen, o));
-  maxlen = __builtin_amdgcn_readfirstlane(maxlen);
+  const uint32_t maxlen = wave_max32(len);
 
-  uint64_t fwd = 0, rc = 0, minv = ~0ULL, cur_val = 0, lo = 0, hi = 0;
-  uint32_t nvalid = 0;
-  int head = w - 1, minage = 0;
-  bool have_cur = false;
-  uint32_t qhead = 0, qn = 0;             // wave-uniform
+  ChunkScan S(w);
+  WaveQueue<int32_t> Q(L.q_key[wib], L.q_tax[wib], lane);
   int created = 0, failed = 0, max_d = 0;  // per lane
 
-  auto flush = [&](uint32_t cnt) {        // insert cnt (<= 64) queued records, one per lane
-    if (lane < cnt) {
-      uint32_t e = (qhead + lane) & 127;
-      int r = insert_merge(T, parents, ntax, L.q_key[wib][e], L.q_tax[wib][e], max_d);
-      created += (r == 1);
-      failed += (r < 0);
-    }
-    qhead = (qhead + cnt) & 127;
-    qn -= cnt;
+  auto insert = [&](uint32_t e, bool active) {   // the queued records, one per lane
+    if (!active) return;
+    int r = insert_merge(T, parents, ntax, L.q_key[wib][e], L.q_tax[wib][e], max_d);
+    created += (r == 1);
+    failed += (r < 0);
   };
 
-  for (uint32_t step = 0; step < maxlen; step++) {
-    if ((step & 15) == 0) {  // 16 bytes per lane every 16 steps (the buffer's last block: byte loads, engine.h)
-      uint4 v = make_uint4(0, 0, 0, 0);
-      if (step < len) v = load_block16(bases + start + step, clamp_room(total_bases - start - step));
-      lo = ((uint64_t)v.y << 32) | v.x;
-      hi = ((uint64_t)v.w << 32) | v.z;
-    }
-    uint32_t ch = (uint32_t)(lo & 0xff);
-    lo = (lo >> 8) | (hi << 56);
-    hi >>= 8;
-    int t = (step < len) ? base_code(ch) : 5;
-    bool emit = false;
-    if (t >= 4) {  // InputReader.removeInvalid (InputReader.scala:60-72): sequences are split around anything else
-      nvalid = 0; fwd = 0; rc = 0; head = w - 1; minage = 0; minv = ~0ULL; have_cur = false;
-    } else {
-      nvalid++;
-      fwd = (fwd << 2) | ((uint64_t)t << P.sh);
-      rc = ((rc >> 2) | ((uint64_t)(3 - t) << 62)) & P.keep;
-      if (nvalid >= (uint32_t)m) {
-        uint64_t canon = (P.canonical && rc < fwd) ? rc : fwd;
-        uint64_t key = (canon ^ P.xmask) & P.smask;
-        head = (head + 1 == w) ? 0 : head + 1;
-        ring[(uint32_t)head * stride + tid] = key;
-        if (key <= minv) { minv = key; minage = 0; }
-        else if (++minage >= w) {
-          int slot = (head + 1 == w) ? 0 : head + 1;
-          minv = ~0ULL;
-          for (int a = w - 1; a >= 0; a--) {
-            uint64_t v = ring[(uint32_t)slot * stride + tid];
-            if (v <= minv) { minv = v; minage = a; }
-            slot = (slot + 1 == w) ? 0 : slot + 1;
-          }
-        }
-        if (nvalid >= (uint32_t)k && (!have_cur || minv != cur_val)) {  // a new super-mer starts: one record candidate
-          have_cur = true;
-          cur_val = minv;
-          emit = true;
-        }
-      }
-    }
-    uint64_t mask = __ballot(emit);
-    if (mask) {
-      uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-      if (emit) {
-        uint32_t e = (qhead + qn + before) & 127;
-        L.q_key[wib][e] = cur_val;
-        L.q_tax[wib][e] = taxon;
-      }
-      qn += (uint32_t)__popcll(mask);
-      if (qn >= 64) flush(64);
-    }
+  for (uint32_t step = 0; step < maxlen; step++) {   // a new super-mer starts: one record candidate
+    const bool emit = S.step(P, ring, stride, tid, bases, start, total_bases, step, len, false) == ChunkScan::FRESH;
+    Q.push(emit, S.cur_val, taxon, insert);
   }
-  if (qn) flush(qn);  // qn < 64 here
+  Q.drain(insert);
 
-  for (int o = 32; o > 0; o >>= 1) {
-    created += __shfl_xor(created, o);
-    failed += __shfl_xor(failed, o);
-    max_d = max(max_d, __shfl_xor(max_d, o));
-  }
-  if (lane == 0) {
-    if (created) atomicAdd(T.n_inserted, (unsigned long long)created);
-    if (failed) atomicAdd(T.n_overflow, (unsigned long long)failed);
-    if (max_d) atomicMax(T.max_disp, max_d);
-  }
+  report_inserts(T, lane, created, failed, max_d);
 }
 
 // Every occupied cell back to its (key, taxon) record: the cell holds the hash remainder and its displacement, the bucket
@@ -142,16 +77,8 @@ __global__ void __launch_bounds__(256) export_kernel(TableView T, uint64_t cell0
     i = base + threadIdx.x;
     uint64_t cell = i < ncells ? T.cells[i] : 0;
     const bool has = cell != 0;
-    const uint64_t mask = __ballot(has);
-    if (mask == 0) continue;
-    // one atomic per wave: the lanes' output slots are consecutive
-    unsigned long long first = 0;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-    if (has && before == 0) first = atomicAdd(counter, (unsigned long long)__popcll(mask));
-    const int leader = __ffsll((long long)mask) - 1;
-    first = ((unsigned long long)(uint32_t)__shfl((int)(first >> 32), leader) << 32) | (uint32_t)__shfl((int)first, leader);
+    const unsigned long long slot = wave_alloc_slots(has, counter);   // one atomic per wave: the lanes' output slots are consecutive
     if (!has) continue;
-    unsigned long long slot = first + before;
     if (slot < capacity) {
       keys[slot] = (int64_t)cell_key(T.g, i, cell);
       taxa[slot] = ext_taxon(T, (int32_t)(cell & tmask));

@@ -1,15 +1,18 @@
-// chunkscan.h -- the lane-per-chunk scan that coverage.hip and support.hip share: one lane walks a chunk of a sequence base by base,
+// chunkscan.h -- the lane-per-chunk scan that build.hip, coverage.hip and support.hip share: one lane walks a chunk of a sequence base by base,
 // keeps the last w m-mer keys in its column of an LDS ring and the window's minimum beside them, and tells its caller at every base
 // whether a k-mer window of the chunk ends there and whether that window starts a new super-mer.  What is done with a super-mer --
-// looked up when it starts (coverage.hip), or when it closes and its windows are known (support.hip) -- is the caller's.
-// (build.hip's scan is this one without the exact seams: it only needs the SET of minimizers and overlaps its chunks by k - 1.)
+// inserted (build.hip) or looked up (coverage.hip) when it starts, or looked up when it closes and its windows are known
+// (support.hip) -- is the caller's.
 //
-// Seams.  A chunk that is not the first of its sequence starts ONE base early (`prime`; an overlap of k with the chunk before): the
+// Seams.  build.hip only needs the SET of minimizers: its chunks overlap by k - 1 bases, a super-mer that straddles a seam is found
+// twice, and it never primes.  Where that would be counted twice (coverage.hip, support.hip), a chunk that is not the first of its
+// sequence starts ONE base early (`prime`; an overlap of k with the chunk before): the
 // window that ends at its step k - 1 is the last window of the chunk before, and it only primes cur_val / have_cur -- it is not
 // reported.  If that window holds an invalid base, nvalid does not reach k there, nothing is primed, and the chunk's first own
 // window rightly starts a new segment.
 #pragma once
 #include "engine.h"
+#include "wavetools.h"
 
 namespace slk {
 
@@ -67,19 +70,5 @@ struct ChunkScan {
     return fresh ? FRESH : SAME;
   }
 };
-
-__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return (uint32_t)__builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-  return v;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-  for (int o = 32; o > 0; o >>= 1)
-    v += ((uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), o) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)v, o);
-  return v;
-}
 
 }  // namespace slk

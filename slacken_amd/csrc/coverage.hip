@@ -4,21 +4,19 @@
 // taxon) row per super-mer, with repetitions), groups the rows by (minimizer, source) into countAll and countDistinct = 1 (:91),
 // inner-joins them with the records (:99-100) and groups again by (source, depth(record's LCA taxon)) into sumAll and sumDistinct
 // (:101-102).  Here:
-//   scan   coverage_scan_kernel, build_kernel's scan (build.hip) with exact seams (chunkscan.h, shared with support.hip): one lane per chunk of BUILD_CHUNK_WINDOWS windows,
+//   scan   coverage_scan_kernel, the lane-per-chunk scan of chunkscan.h with exact seams: one lane per chunk of BUILD_CHUNK_WINDOWS windows,
 //          every super-mer's minimizer looked up in the table (the one random HBM request per super-mer); a hit adds 1 to a
 //          device-wide pair map (pairmap.h) under (cell of the record << 28 | source ordinal) -- the first group-by and the join.
 //          The record's position stands for the minimizer: a 32-nt minimizer fills all 64 bits, the cell index needs 36.
 //   fold   coverage_fold_kernel, one streaming pass over the pair map's slots: the cell's taxon (one 8-byte random load), its depth,
 //          and (all += count, distinct += 1) under (source ordinal, depth) in a second, small map -- the second group-by.  The slots
 //          are emptied as they are read: after a fold the pair map is empty, the (source, depth) sums stay.
-// Seams.  build_kernel overlaps its chunks by k - 1 bases because it only needs the SET of minimizers: a super-mer that straddles
-// a seam is found twice there.  Here that would be counted twice, so a chunk that is not the first of its sequence starts ONE base
-// earlier (an overlap of k): the window that ends at its step k - 1 is the last window of the chunk before, and it only primes
-// cur_val / have_cur -- it is neither emitted nor counted as a k-mer.  If that window holds an invalid base, nvalid does not reach k
-// there, nothing is primed, and the chunk's first own window rightly starts a new segment and is emitted.
-// The fold counts on the three levels of migration_kernel (migration.hip), in that order -- wave ballot, LDS map, device map -- since
+// Seams.  A super-mer found twice would be counted twice, so the chunks are cut with exact seams (chunkcut.h, chunkscan.h): the
+// priming window of a chunk is neither emitted nor counted as a k-mer.
+// The fold counts on the three levels of wavetools.h -- wave ballot, LDS map, device map -- since
 // a genome's slots nearly all land on two or three (source, depth) pairs; the scan's per-source totals are combined by the wave
 // before they reach the device arrays, since the chunks of a wave mostly belong to one sequence.
+#include "chunkcut.h"
 #include "chunkscan.h"
 #include "hostside.h"
 #include "pairmap.h"
@@ -27,7 +25,7 @@
 
 namespace {
 
-constexpr int CV_W = 4;                               // waves per block of the scan (build_kernel's)
+constexpr int CV_W = 4;                               // waves per block of the scan (as build.hip's)
 constexpr uint32_t CV_PRIME = 1u << 31;               // chunk_src: the chunk starts one base early, its first window only primes
 constexpr int CV_ORD_BITS = 28;
 constexpr uint32_t CV_ORD_MASK = (1u << CV_ORD_BITS) - 1;
@@ -78,53 +76,37 @@ __global__ void __launch_bounds__(CV_W * 64) coverage_scan_kernel(CovArgs A) {
   const uint32_t ord = src & CV_ORD_MASK;
   const uint32_t maxlen = wave_max32(len);
   ChunkScan S(P.w);
-  uint32_t qhead = 0, qn = 0;          // wave-uniform
+  WaveQueue<uint32_t> Q(L.q_key[wib], L.q_ord[wib], lane);
   uint32_t n_kmers = 0, n_supermers = 0;   // of this lane's chunk: its own windows, matched or not
 
-  auto flush = [&](uint32_t cnt) {     // look up cnt (<= 64) queued minimizers, one per lane
-    if (lane < cnt) {
-      const uint32_t e = (qhead + lane) & 127;
-      uint64_t cell = 0;
-      const bool hit = table_lookup_cell(A.T, L.q_key[wib][e], &cell) != 0;    // a miss leaves the join (:99-100)
-      if (hit && !pair_map_add(A.map_keys, A.map_counts, A.map_mask, (cell << CV_ORD_BITS) | L.q_ord[wib][e], 1ULL, A.counters + 1))
-        atomicOr(A.status, 2);
-    }
-    qhead = (qhead + cnt) & 127;
-    qn -= cnt;
+  auto lookup = [&](uint32_t e, bool active) {   // the queued minimizers, one per lane
+    if (!active) return;
+    uint64_t cell = 0;
+    const bool hit = table_lookup_cell(A.T, L.q_key[wib][e], &cell) != 0;    // a miss leaves the join (:99-100)
+    if (hit && !pair_map_add(A.map_keys, A.map_counts, A.map_mask, (cell << CV_ORD_BITS) | L.q_ord[wib][e], 1ULL, A.counters + 1))
+      atomicOr(A.status, 2);
   };
 
   for (uint32_t step = 0; step < maxlen; step++) {
     const int window = S.step(P, ring, stride, tid, A.bases, start, A.total_bases, step, len, prime);
     const bool emit = window == ChunkScan::FRESH;
     if (window != ChunkScan::NO_WINDOW) { n_kmers++; if (emit) n_supermers++; }
-    uint64_t mask = __ballot(emit);
-    if (mask) {
-      uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-      if (emit) {
-        uint32_t e = (qhead + qn + before) & 127;
-        L.q_key[wib][e] = S.cur_val;
-        L.q_ord[wib][e] = ord;
-      }
-      qn += (uint32_t)__popcll(mask);
-      if (qn >= 64) flush(64);
-    }
+    Q.push(emit, S.cur_val, ord, lookup);
   }
-  if (qn) flush(qn);  // qn < 64 here
+  Q.drain(lookup);
 
   // the chunks' totals: the lanes that share the leader's source hand theirs to it, the rest add their own
   bool have = mine;
   for (int round = 0; round < CV_LEADER_ROUNDS; round++) {
-    const uint64_t holding = __ballot(have);
-    if (holding == 0) break;
-    const int leader = __ffsll((unsigned long long)holding) - 1;
-    const uint32_t lo_ord = (uint32_t)__shfl((int)ord, leader);
-    const bool same = have && ord == lo_ord;
-    const uint32_t ks = wave_sum32(same ? n_kmers : 0u), ss = wave_sum32(same ? n_supermers : 0u);
-    if ((int)lane == leader) {
-      if (ks) atomicAdd(&A.kmers[lo_ord], (unsigned long long)ks);
-      if (ss) atomicAdd(&A.supermers[lo_ord], (unsigned long long)ss);
-    }
-    have = have && !same;
+    const bool any = leader_round(have, ord, [&](int leader, uint32_t lo_ord, bool same) {
+      const uint32_t ks = wave_sum32(same ? n_kmers : 0u), ss = wave_sum32(same ? n_supermers : 0u);
+      if ((int)lane == leader) {
+        if (ks) atomicAdd(&A.kmers[lo_ord], (unsigned long long)ks);
+        if (ss) atomicAdd(&A.supermers[lo_ord], (unsigned long long)ss);
+      }
+      have = have && !same;
+    });
+    if (!any) break;
   }
   if (have) {
     if (n_kmers) atomicAdd(&A.kmers[ord], (unsigned long long)n_kmers);
@@ -149,23 +131,17 @@ __device__ __forceinline__ void fd_global_add(const FoldArgs &A, unsigned long l
   if (!pair_map_add2(A.rkeys, A.rall, A.rdistinct, A.rmask, pair, all, distinct, A.counters + 2)) atomicOr(A.status, 2);
 }
 
-__device__ __forceinline__ void fd_block_add(const FoldArgs &A, unsigned long long *lkeys, unsigned long long *lall, unsigned int *ldistinct,
-                                             unsigned long long pair, unsigned long long all, unsigned int distinct) {
-  uint32_t h = (uint32_t)fmix64(pair) & (FD_SLOTS - 1);
-  for (int probe = 0; probe < FD_PROBES; probe++) {
-    const unsigned long long prev = atomicCAS(&lkeys[h], (unsigned long long)PAIR_EMPTY, pair);
-    if (prev == PAIR_EMPTY || prev == pair) { atomicAdd(&lall[h], all); atomicAdd(&ldistinct[h], distinct); return; }
-    h = (h + 1) & (FD_SLOTS - 1);
-  }
-  fd_global_add(A, pair, all, (unsigned long long)distinct);
-}
+using FoldMap = LdsCountMap<unsigned long long, PAIR_EMPTY, FD_SLOTS, FD_PROBES, false>;
 
 __global__ void __launch_bounds__(FD_BLOCK) coverage_fold_kernel(FoldArgs A) {
-  __shared__ unsigned long long lkeys[FD_SLOTS];
+  __shared__ FoldMap M;
   __shared__ unsigned long long lall[FD_SLOTS];
   __shared__ unsigned int ldistinct[FD_SLOTS];
-  for (uint32_t s = threadIdx.x; s < FD_SLOTS; s += FD_BLOCK) { lkeys[s] = PAIR_EMPTY; lall[s] = 0; ldistinct[s] = 0; }
-  __syncthreads();
+  M.clear(threadIdx.x, FD_BLOCK, [&](uint32_t s) { lall[s] = 0; ldistinct[s] = 0; });
+  auto block_add = [&](unsigned long long pair, unsigned long long all, unsigned int distinct) {
+    M.add(pair, (uint32_t)fmix64(pair), [&](uint32_t h) { atomicAdd(&lall[h], all); atomicAdd(&ldistinct[h], distinct); },
+          [&] { fd_global_add(A, pair, all, (unsigned long long)distinct); });
+  };
   const int lane = threadIdx.x & 63;
   const uint64_t stride = (uint64_t)gridDim.x * FD_BLOCK;
   for (uint64_t base = (uint64_t)blockIdx.x * FD_BLOCK; base < A.n; base += stride) {   // block-uniform: the ballots see whole waves
@@ -186,36 +162,17 @@ __global__ void __launch_bounds__(FD_BLOCK) coverage_fold_kernel(FoldArgs A) {
       }
     }
     for (int round = 0; round < CV_LEADER_ROUNDS; round++) {
-      const uint64_t holding = __ballot(have);
-      if (holding == 0) break;
-      const int leader = __ffsll((unsigned long long)holding) - 1;
-      const unsigned long long lp = ((unsigned long long)(uint32_t)__shfl((int)(pair >> 32), leader) << 32) |
-                                    (uint32_t)__shfl((int)(uint32_t)pair, leader);
-      const bool same = have && pair == lp;
-      const uint64_t group = __ballot(same);
-      const uint64_t all = wave_sum64(same ? count : 0ULL);
-      if (lane == leader) fd_block_add(A, lkeys, lall, ldistinct, lp, all, (unsigned int)__popcll(group));
-      have = have && !same;
+      const bool any = leader_round(have, pair, [&](int leader, unsigned long long lp, bool same) {
+        const uint64_t group = __ballot(same);
+        const uint64_t all = wave_sum64(same ? count : 0ULL);
+        if (lane == leader) block_add(lp, all, (unsigned int)__popcll(group));
+        have = have && !same;
+      });
+      if (!any) break;
     }
-    if (have) fd_block_add(A, lkeys, lall, ldistinct, pair, count, 1u);
+    if (have) block_add(pair, count, 1u);
   }
-  __syncthreads();
-  for (uint32_t s = threadIdx.x; s < FD_SLOTS; s += FD_BLOCK)
-    if (lkeys[s] != PAIR_EMPTY) fd_global_add(A, lkeys[s], lall[s], (unsigned long long)ldistinct[s]);
-}
-
-// every pair of the old map into the new one (the new one has room: it is larger); second / new_second null: one counter
-__global__ void __launch_bounds__(256) coverage_rehash_kernel(const unsigned long long *old_keys, const unsigned long long *old_first,
-                                                              const unsigned long long *old_second, uint64_t old_cap,
-                                                              unsigned long long *keys, unsigned long long *first,
-                                                              unsigned long long *second, uint64_t mask, int32_t *status) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap; i += stride) {
-    if (old_keys[i] == PAIR_EMPTY) continue;
-    const bool ok = second != nullptr ? pair_map_add2(keys, first, second, mask, old_keys[i], old_first[i], old_second[i], nullptr)
-                                      : pair_map_add(keys, first, mask, old_keys[i], old_first[i], nullptr);
-    if (!ok) atomicOr(status, 2);
-  }
+  M.drain(threadIdx.x, FD_BLOCK, [&](unsigned long long pair, uint32_t s) { fd_global_add(A, pair, lall[s], (unsigned long long)ldistinct[s]); });
 }
 
 }  // namespace
@@ -237,25 +194,12 @@ struct slk_coverage {
   DevBuf rows_distinct;               //                          -> sumDistinct
   DevBuf counters, status;            // CovArgs.counters (4 x uint64), CovArgs.status
   DevBuf d_bases, d_start, d_len, d_src;
-  unsigned fold_blocks = 256 * FD_BLOCKS_PER_CU;
+  unsigned fold_blocks = 0;
   bool spent = false;
 };
 
-static int32_t cv_check_spent(const slk_coverage *c) {
-  if (c->spent) return fail(SLK_E_STATE, "coverage: an earlier call on this handle failed, its counts are incomplete");
-  return SLK_OK;
-}
 static unsigned long long *cv_kmers(const slk_coverage *c) { return c->totals.as<unsigned long long>(); }
 static unsigned long long *cv_supermers(const slk_coverage *c) { return c->totals.as<unsigned long long>() + c->totals_cap; }
-
-static int32_t cv_rehash(hipStream_t s, const PairMap &old, const DevBuf *old_second, PairMap &now, DevBuf *second, int32_t *status) {
-  hipLaunchKernelGGL(coverage_rehash_kernel, dim3((unsigned)std::min<uint64_t>((old.cap + 255) / 256, 4096)), dim3(256), 0, s, old.k(), old.c(),
-                     old_second ? old_second->as<unsigned long long>() : nullptr, old.cap, now.k(), now.c(),
-                     second ? second->as<unsigned long long>() : nullptr, now.cap - 1, status);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));   // (the caller frees the old map)
-  return SLK_OK;
-}
 
 // Waits for what was queued on s, reports a full map or a spent budget, and moves the pair map to a larger one while it is more than
 // half full -- or, within the budget, has less room than the launch that comes next would like (`want` windows, at most
@@ -281,7 +225,7 @@ static int32_t cv_settle(slk_coverage *c, hipStream_t s, uint64_t want) {
   c->map = PairMap();
   int32_t rc = c->map.reset(s, cap);
   if (rc) return rc;
-  return c->n_pairs ? cv_rehash(s, old, nullptr, c->map, nullptr, c->status.as<int32_t>()) : SLK_OK;
+  return c->n_pairs ? old.grow_into<false>(s, c->map, nullptr, nullptr, c->status.as<int32_t>()) : SLK_OK;
 }
 
 // room for every source's totals and every (source, depth) row
@@ -312,7 +256,7 @@ static int32_t cv_ensure_sources(slk_coverage *c, hipStream_t s) {
   if (rc) return rc;
   HIPCHK(c->rows_distinct.ensure(cap * 8));
   HIPCHK(hipMemsetAsync(c->rows_distinct.p, 0, cap * 8, s));
-  return old.cap ? cv_rehash(s, old, &old_distinct, c->rows, &c->rows_distinct, c->status.as<int32_t>()) : SLK_OK;
+  return old.cap ? old.grow_into<true>(s, c->rows, &old_distinct, &c->rows_distinct, c->status.as<int32_t>()) : SLK_OK;
 }
 
 // the pair map into the (source, depth) rows; synchronises s
@@ -359,27 +303,18 @@ static int32_t cv_add(slk_coverage *c, slk_stream *st, const uint8_t *bases, con
   if (rc) return rc;
   std::vector<uint64_t> cstart;
   std::vector<uint32_t> clen, csrc;
-  uint64_t i = 0;
-  while (i < R) {   // groups of whole sequences of about 1 GiB, cut into chunks of CW windows
-    uint64_t j = i;
-    const uint64_t g0 = offsets[i];
-    while (j < R && (j == i || offsets[j + 1] - g0 <= CV_GROUP_BYTES)) j++;
-    const uint64_t gbytes = offsets[j] - g0;
+  for (uint64_t i = 0, j; i < R; i = j) {   // groups of whole sequences of about 1 GiB, cut into chunks of CW windows
+    j = group_end(offsets, i, R, CV_GROUP_BYTES);
+    const uint64_t g0 = offsets[i], gbytes = offsets[j] - g0;
     cstart.clear(); clen.clear(); csrc.clear();
-    for (uint64_t q = i; q < j; q++) {
-      const uint64_t len = offsets[q + 1] - offsets[q];
-      if (source_taxa[q] == 0 || len < k) continue;
-      const uint32_t ord = c->ord_of[source_taxa[q]];
-      const uint64_t windows = len - k + 1;
-      for (uint64_t w0 = 0; w0 < windows; w0 += CW) {
-        const uint64_t nw = std::min<uint64_t>(CW, windows - w0);
-        const uint64_t early = w0 ? 1 : 0;   // (one base of the chunk before: its last window primes this one)
-        cstart.push_back(offsets[q] - g0 + w0 - early);
-        clen.push_back((uint32_t)(nw + k - 1 + early));
-        csrc.push_back(ord | (early ? CV_PRIME : 0u));
-      }
-    }
-    i = j;
+    uint32_t ord = 0;   // of the sequence whose chunks are coming: looked up at its first chunk, which is not early
+    cut_chunks(offsets, i, j, k, CW, true, [&](uint64_t q) { return source_taxa[q] == 0; },
+               [&](uint64_t q, uint64_t start, uint32_t len, uint32_t early) {
+                 if (!early) ord = c->ord_of[source_taxa[q]];
+                 cstart.push_back(start);
+                 clen.push_back(len);
+                 csrc.push_back(ord | (early ? CV_PRIME : 0u));
+               });
     const uint64_t nc = cstart.size();
     if (nc == 0) continue;
     HIPCHK(c->d_bases.ensure(gbytes));
@@ -434,16 +369,10 @@ static int32_t cv_add(slk_coverage *c, slk_stream *st, const uint8_t *bases, con
 }
 
 static int32_t cv_enter(slk_coverage *c) {
-  if (!c) return fail(SLK_E_INVALID, "null handle");
-  int32_t rc = cv_check_spent(c);
-  if (rc) return rc;
-  return set_device(c->ix);
+  return enter_handle(c, "coverage: an earlier call on this handle failed, its counts are incomplete");
 }
 // SLK_E_CAPACITY and SLK_E_HIP leave the counts incomplete
-static int32_t cv_leave(slk_coverage *c, int32_t rc) {
-  if (rc == SLK_E_CAPACITY || rc == SLK_E_HIP) c->spent = true;
-  return rc;
-}
+static int32_t cv_leave(slk_coverage *c, int32_t rc) { return leave_handle(c, rc, rc == SLK_E_CAPACITY || rc == SLK_E_HIP); }
 
 extern "C" {
 
@@ -452,12 +381,9 @@ int32_t slk_coverage_create(slk_index *ix, const int32_t *depths, int32_t T, uin
   *out = nullptr;
   if (!ix) return fail(SLK_E_INVALID, "null handle");
   if (T < 0 || (T > 0 && !depths)) return fail(SLK_E_INVALID, "depths must hold T >= 0 entries");
-  if (!ix->finalized) return fail(SLK_E_STATE, "index is not finalized");
-  if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "genome coverage supports minimizers of up to 32 nt (one id column)");
-  if (ix->n_shards > 1) return fail(SLK_E_UNSUPPORTED, "genome coverage needs the whole table on one GPU (the index is a shard)");
-  if (ix->sp.w > BUILD_MAX_W)
-    return fail(SLK_E_UNSUPPORTED, "genome coverage supports windows of up to %d m-mers (k - m + 1 = %d)", BUILD_MAX_W, ix->sp.w);
-  int32_t rc = set_device(ix);
+  int32_t rc = check_whole_narrow_index(ix, "genome coverage", "table", true);
+  if (rc) return rc;
+  rc = set_device(ix);
   if (rc) return rc;
   std::unique_ptr<slk_coverage> c(new slk_coverage());   // (released into *out on success only)
   c->ix = ix;
@@ -467,13 +393,8 @@ int32_t slk_coverage_create(slk_index *ix, const int32_t *depths, int32_t T, uin
   distinct.push_back(-1);
   std::sort(distinct.begin(), distinct.end());
   c->n_depths = (uint64_t)(std::unique(distinct.begin(), distinct.end()) - distinct.begin());
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device) == hipSuccess && cus > 0)
-    c->fold_blocks = (unsigned)cus * FD_BLOCKS_PER_CU;
-  else (void)hipGetLastError();
   // SLK_COVERAGE_FOLD_BLOCKS: the fold's grid (tests: a few blocks; measurements: occupancy)
-  const long env_blocks = env_long("SLK_COVERAGE_FOLD_BLOCKS", 0);
-  if (env_blocks > 0) c->fold_blocks = (unsigned)std::min(env_blocks, 65535L);
+  c->fold_blocks = grid_for(ix->device, FD_BLOCKS_PER_CU, "SLK_COVERAGE_FOLD_BLOCKS");
   if (max_pairs == 0) {
     // half of the memory free now, at 16 bytes per slot and load 0.5 (a choice, not a measurement): the largest power of two within it
     size_t free_b = 0, total_b = 0;

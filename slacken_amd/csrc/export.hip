@@ -205,13 +205,8 @@ extern "C" int32_t slk_index_export_range(const slk_index *ix, uint64_t bucket0,
     A.e0 = bucket0 * LPB;
     A.n = (bucket1 - bucket0) * LPB;
     A.n_groups = (uint32_t)n_groups;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device) != hipSuccess || cus <= 0) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
     const uint64_t tile = (uint64_t)XR_BLOCK * XR_UNROLL;
-    const unsigned grid = (unsigned)std::min<uint64_t>((A.n + tile - 1) / tile, (uint64_t)cus * XR_BLOCKS_PER_CU);   // both passes: the same
+    const unsigned grid = (unsigned)std::min<uint64_t>((A.n + tile - 1) / tile, (uint64_t)grid_for(ix->device, XR_BLOCKS_PER_CU, nullptr));   // both passes: the same
     const bool lds = (long)n_groups <= xr_lds_groups();
     const size_t G = (size_t)n_groups, lds_bytes = lds ? G * 4 : 0;
     // the group counters: counts [G], offsets [G + 1], cursors [G], and on the LDS route the blocks' histograms

@@ -23,6 +23,7 @@
 // characters one after the other (RUNS) when it holds others -> NEXT mate) fills the LDS span buffer; ONE flush site probes and
 // folds whatever is buffered; repeat until the fragment is exhausted.
 #include "engine.h"
+#include "wavetools.h"
 
 #include <cstdlib>
 
@@ -74,9 +75,6 @@ __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
   return v;
-}
-__device__ __forceinline__ int lanes_below(uint64_t mask) {  // popcount(mask & lanes lower than this one)
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
 
 // the next unit of a hand-on list for this wave (one atomic per wave; every lane gets the value)
@@ -384,7 +382,7 @@ __device__ __forceinline__ void resolve_map(WaveLds *L, const FusedArgs &A, uint
     int32_t kk = L->map_key[slot];
     bool occ = kk != MAP_EMPTY;
     uint64_t mask = __ballot(occ);
-    if (occ) dense[D + lanes_below(mask)] = make_int2(kk, L->map_cnt[slot]);
+    if (occ) dense[D + lane_rank(mask)] = make_int2(kk, L->map_cnt[slot]);
     D += __popcll(mask);
   }
   wave_sync();
@@ -587,7 +585,7 @@ __global__ void FUSED_BOUNDS fused_kernel(FusedArgs A) {
           if (is_start && lane != lastl) {
             int d = __builtin_ctzll(S >> (lane + 1)) + 1;
             bool dist = (seg_first && lane == firstl) ? (special || res != last_key) : true;
-            put_span(L, nbuf + nclose + lanes_below(S), res, d, 1, dist);
+            put_span(L, nbuf + nclose + lane_rank(S), res, d, 1, dist);
           }
           int emitted = nclose + __popcll(S) - 1;
           if (emitted > 0) { seg_first = false; first = false; }
@@ -947,7 +945,7 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
         const uint64_t E = __ballot(push);
         if (E != 0) {
           if (push) {
-            const int slot = nbuf + lanes_below(E);
+            const int slot = nbuf + lane_rank(E);
             if (emit) put_span(L, slot, ekey, ekmers, 1, distinct);
             else put_span(L, slot, 0, amb_kmers, 2, false);
             if constexpr (HITS) Q->span_dst[slot] = ((uint32_t)lane << 26) | lcount;     // whose span, and its number there (a lane has fewer than 2^25 windows)

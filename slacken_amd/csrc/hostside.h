@@ -409,6 +409,42 @@ inline int32_t set_device(const slk_index *ix) {
   return SLK_OK;
 }
 
+// The grid of a persistent-block pass: blocks_per_cu blocks for every CU of `device` (< 0: the current one; 256 CUs where the
+// runtime does not say), or what the environment variable `env_name` (may be null) gives: the tests' way to a few blocks.
+inline unsigned grid_for(int device, int blocks_per_cu, const char *env_name) {
+  int cus = 0;
+  if ((device < 0 && hipGetDevice(&device) != hipSuccess) ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) {
+    (void)hipGetLastError();
+    cus = 256;
+  }
+  const long env_blocks = env_name ? env_long(env_name, 0) : 0;
+  return env_blocks > 0 ? (unsigned)std::min(env_blocks, 65535L) : (unsigned)cus * (unsigned)blocks_per_cu;
+}
+
+// What the analyses that look a library's or a sample's minimizers up in a resident table refuse at create: `what` names the
+// analysis, `table` the table in its words; need_scan: it scans sequences with the lane-per-chunk scan (chunkscan.h).
+inline int32_t check_whole_narrow_index(const slk_index *ix, const char *what, const char *table, bool need_scan) {
+  if (!ix->finalized) return fail(SLK_E_STATE, "index is not finalized");
+  if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "%s supports minimizers of up to 32 nt (one id column)", what);
+  if (ix->n_shards > 1) return fail(SLK_E_UNSUPPORTED, "%s needs the whole %s on one GPU (the index is a shard)", what, table);
+  if (need_scan && ix->sp.w > BUILD_MAX_W)
+    return fail(SLK_E_UNSUPPORTED, "%s supports windows of up to %d m-mers (k - m + 1 = %d)", what, BUILD_MAX_W, ix->sp.w);
+  return SLK_OK;
+}
+
+// A handle whose counts an earlier failure left incomplete (`spent`) takes no further call.  Every entry of such a handle starts
+// with enter_handle and returns through leave_handle; which codes spend the handle is the handle's choice.
+template <class H> inline int32_t enter_handle(const H *h, const char *spent_text) {
+  if (!h) return fail(SLK_E_INVALID, "null handle");
+  if (h->spent) return fail(SLK_E_STATE, "%s", spent_text);
+  return set_device(h->ix);
+}
+template <class H> inline int32_t leave_handle(H *h, int32_t rc, bool spends) {
+  if (spends) h->spent = true;
+  return rc;
+}
+
 // A synchronous host entry leaves with nothing queued that reads or writes the caller's memory: from the first copy it queues, every
 // return -- the failing ones too, after which the caller may free its buffers -- passes through this.
 struct DrainOnExit {

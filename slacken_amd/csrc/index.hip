@@ -2,6 +2,7 @@
 // table that grows, the taxonomy and its Euler tours, library construction from sequences, export, respace, finalize.
 // Host-side only: the kernels it launches are in kernels.hip, build.hip, wide.hip and respace.hip.  (slk_index_export_range lives
 // beside its kernels in export.hip, as slk_index_taxon_counts does in taxstats.hip.)
+#include "chunkcut.h"
 #include "hostside.h"
 
 // Geometry of the record table.  Any number of buckets (engine.h: the multiply-shift range reduction); a cell holds
@@ -603,23 +604,15 @@ static int32_t add_sequences(slk_index *ix, const uint8_t *bases, const uint64_t
   std::vector<uint64_t> cstart;
   std::vector<uint32_t> clen;
   std::vector<int32_t> ctax;
-  uint64_t i = 0;
-  while (i < S) {
-    uint64_t j = i, g0 = offsets[i];
-    while (j < S && (j == i || offsets[j + 1] - g0 <= GROUP)) j++;
-    uint64_t gbytes = offsets[j] - g0;
+  for (uint64_t i = 0, j; i < S; i = j) {
+    j = group_end(offsets, i, S, GROUP);
+    const uint64_t g0 = offsets[i], gbytes = offsets[j] - g0;
     cstart.clear(); clen.clear(); ctax.clear();
-    for (uint64_t q = i; q < j; q++) {
-      uint64_t len = offsets[q + 1] - offsets[q];
-      if (taxa[q] == 0 || len < k) continue;
-      uint64_t windows = len - k + 1;
-      for (uint64_t w0 = 0; w0 < windows; w0 += CW) {
-        uint64_t nw = std::min<uint64_t>(CW, windows - w0);
-        cstart.push_back(offsets[q] - g0 + w0);
-        clen.push_back((uint32_t)(nw + k - 1));
-        ctax.push_back(taxa[q]);
-      }
-    }
+    cut_chunks(offsets, i, j, k, CW, false, [&](uint64_t q) { return taxa[q] == 0; }, [&](uint64_t q, uint64_t start, uint32_t len, uint32_t) {
+      cstart.push_back(start);
+      clen.push_back(len);
+      ctax.push_back(taxa[q]);
+    });
     if (!cstart.empty()) {
       uint64_t nc = cstart.size();
       HIPCHK(d_start.ensure(nc * 8));
@@ -645,7 +638,6 @@ static int32_t add_sequences(slk_index *ix, const uint8_t *bases, const uint64_t
       });
       if (rc) return rc;
     }
-    i = j;
   }
   return read_build_counters(ix);
 }

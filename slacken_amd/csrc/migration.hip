@@ -4,17 +4,14 @@
 // subject's records stream through one kernel that looks each key up (the only random access per record) and counts the (t1, t2)
 // pairs; steps is a function of the pair, computed per distinct pair on the host (slk_migration_result).
 //
-// The count has three levels, so that the few hot pairs of a real library (t1 == t2 for a few thousand species) do not serialise on
-// a handful of HBM addresses:
-//   wave    MG_LEADER_ROUNDS times, the first lane still holding a pair names it; the lanes holding the same pair are counted with a
-//           ballot and leave, and the leader alone adds their number
-//   block   an open-addressing map pair -> uint32 in LDS (MG_SLOTS slots, at most MG_PROBES probes) takes those sums and the lanes left
-//   device  at the end of the block every occupied LDS slot goes to the device-wide map (pairmap.h) with one 64-bit atomic
-// A lane that finds no LDS slot within MG_PROBES adds to the device-wide map itself.  Every route is an addition: the result does
-// not depend on which one a record took.  A block's LDS counters are 32-bit; a launch covers at most MG_LAUNCH_MAX = 2^30 records
+// The count has the three levels of wavetools.h, so that the few hot pairs of a real library (t1 == t2 for a few thousand species)
+// do not serialise on a handful of HBM addresses: MG_LEADER_ROUNDS rounds in the wave, the lanes under the leader's pair counted
+// with a ballot; a map pair -> uint32 in LDS (MG_SLOTS slots, at most MG_PROBES probes); the device-wide map (pairmap.h), one
+// 64-bit atomic per occupied LDS slot at the end of the block.  A block's LDS counters are 32-bit; a launch covers at most MG_LAUNCH_MAX = 2^30 records
 // (the host cuts longer calls), so no block can see as many as 2^32 between two flushes.
 #include "hostside.h"
 #include "pairmap.h"
+#include "wavetools.h"
 
 namespace {
 
@@ -43,22 +40,15 @@ __device__ __forceinline__ void mg_global_add(const MgArgs &A, unsigned long lon
   if (!pair_map_add(A.map_keys, A.map_counts, A.map_mask, pair, c, A.counters + 2)) atomicOr(A.status, 2);
 }
 
-__device__ __forceinline__ void mg_block_add(const MgArgs &A, unsigned long long *lkeys, unsigned int *lcounts, unsigned long long pair,
-                                             unsigned int c) {
-  uint32_t h = (uint32_t)fmix64(pair) & (MG_SLOTS - 1);
-  for (int probe = 0; probe < MG_PROBES; probe++) {
-    const unsigned long long prev = atomicCAS(&lkeys[h], (unsigned long long)PAIR_EMPTY, pair);
-    if (prev == PAIR_EMPTY || prev == pair) { atomicAdd(&lcounts[h], c); return; }
-    h = (h + 1) & (MG_SLOTS - 1);
-  }
-  mg_global_add(A, pair, c);
-}
+using MgMap = LdsCountMap<unsigned long long, PAIR_EMPTY, MG_SLOTS, MG_PROBES, false>;
 
 __global__ void __launch_bounds__(MG_BLOCK) migration_kernel(MgArgs A) {
-  __shared__ unsigned long long lkeys[MG_SLOTS];
+  __shared__ MgMap M;
   __shared__ unsigned int lcounts[MG_SLOTS];
-  for (uint32_t s = threadIdx.x; s < MG_SLOTS; s += MG_BLOCK) { lkeys[s] = PAIR_EMPTY; lcounts[s] = 0; }
-  __syncthreads();
+  M.clear(threadIdx.x, MG_BLOCK, [&](uint32_t s) { lcounts[s] = 0; });
+  auto block_add = [&](unsigned long long pair, unsigned int c) {
+    M.add(pair, (uint32_t)fmix64(pair), [&](uint32_t h) { atomicAdd(&lcounts[h], c); }, [&] { mg_global_add(A, pair, c); });
+  };
   const int lane = threadIdx.x & 63;
   uint64_t n_matched = 0, n_unmatched = 0;   // of this wave (every lane keeps the same numbers)
   const uint64_t stride = (uint64_t)gridDim.x * MG_BLOCK;
@@ -74,34 +64,20 @@ __global__ void __launch_bounds__(MG_BLOCK) migration_kernel(MgArgs A) {
     n_unmatched += (uint64_t)__popcll(__ballot(act && !have));
     const unsigned long long pair = ((unsigned long long)(uint32_t)t1 << 32) | (uint32_t)t2;
     for (int round = 0; round < MG_LEADER_ROUNDS; round++) {
-      const uint64_t holding = __ballot(have);
-      if (holding == 0) break;
-      const int leader = __ffsll((unsigned long long)holding) - 1;
-      const unsigned long long lp = ((unsigned long long)(uint32_t)__shfl((int)(pair >> 32), leader) << 32) |
-                                    (uint32_t)__shfl((int)(uint32_t)pair, leader);
-      const bool same = have && pair == lp;
-      const uint64_t group = __ballot(same);
-      if (lane == leader) mg_block_add(A, lkeys, lcounts, lp, (unsigned int)__popcll(group));
-      have = have && !same;
+      const bool any = leader_round(have, pair, [&](int leader, unsigned long long lp, bool same) {
+        const uint64_t group = __ballot(same);
+        if (lane == leader) block_add(lp, (unsigned int)__popcll(group));
+        have = have && !same;
+      });
+      if (!any) break;
     }
-    if (have) mg_block_add(A, lkeys, lcounts, pair, 1u);
+    if (have) block_add(pair, 1u);
   }
   if (lane == 0) {
     if (n_matched) atomicAdd(A.counters + 0, (unsigned long long)n_matched);
     if (n_unmatched) atomicAdd(A.counters + 1, (unsigned long long)n_unmatched);
   }
-  __syncthreads();
-  for (uint32_t s = threadIdx.x; s < MG_SLOTS; s += MG_BLOCK)
-    if (lkeys[s] != PAIR_EMPTY) mg_global_add(A, lkeys[s], (unsigned long long)lcounts[s]);
-}
-
-// every pair of the old map into the new one (the new one has room: it is larger)
-__global__ void __launch_bounds__(256) migration_rehash_kernel(const unsigned long long *old_keys, const unsigned long long *old_counts,
-                                                               uint64_t old_cap, MgArgs A) {
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap; i += stride)
-    if (old_keys[i] != PAIR_EMPTY && !pair_map_add(A.map_keys, A.map_counts, A.map_mask, old_keys[i], old_counts[i], nullptr))
-      atomicOr(A.status, 2);
+  M.drain(threadIdx.x, MG_BLOCK, [&](unsigned long long pair, uint32_t s) { mg_global_add(A, pair, (unsigned long long)lcounts[s]); });
 }
 
 }  // namespace
@@ -115,7 +91,7 @@ struct slk_migration {
   DevBuf counters, status;       // MgArgs.counters (3 x uint64), MgArgs.status
   DevBuf d_keys, d_taxa;         // a chunk of a host call
   int max_log2 = 32;
-  unsigned blocks = 256 * MG_BLOCKS_PER_CU;
+  unsigned blocks = 0;
   bool spent = false;            // an add failed: the map holds part of it
 };
 
@@ -151,11 +127,7 @@ static int32_t mg_settle(slk_migration *m, hipStream_t s) {
   m->map = PairMap();
   const int32_t rc = m->map.reset(s, cap);
   if (rc) return rc;
-  hipLaunchKernelGGL(migration_rehash_kernel, dim3((unsigned)std::min<uint64_t>((old.cap + 255) / 256, 4096)), dim3(256), 0, s, old.k(),
-                     old.c(), old.cap, mg_args(m));
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(s));   // (old is freed on return)
-  return SLK_OK;
+  return old.grow_into<false>(s, m->map, nullptr, nullptr, m->status.as<int32_t>());   // (old is freed on return)
 }
 
 static int32_t mg_launch(slk_migration *m, hipStream_t s, const int64_t *d_keys, const int32_t *d_taxa, uint64_t n) {
@@ -186,23 +158,17 @@ int32_t slk_migration_create(slk_index *reference, const int32_t *depths, int32_
   *out = nullptr;
   if (!reference) return fail(SLK_E_INVALID, "null handle");
   if (T < 0 || (T > 0 && !depths)) return fail(SLK_E_INVALID, "depths must hold T >= 0 entries");
-  if (!reference->finalized) return fail(SLK_E_STATE, "index is not finalized");
-  if (reference->W > 1) return fail(SLK_E_UNSUPPORTED, "minimizer migration supports minimizers of up to 32 nt (one id column)");
-  if (reference->n_shards > 1) return fail(SLK_E_UNSUPPORTED, "minimizer migration needs the whole reference table on one GPU (the index is a shard)");
-  int32_t rc = set_device(reference);
+  int32_t rc = check_whole_narrow_index(reference, "minimizer migration", "reference table", false);
+  if (rc) return rc;
+  rc = set_device(reference);
   if (rc) return rc;
   std::unique_ptr<slk_migration> m(new slk_migration());   // (released into *out on success only)
   m->ix = reference;
   m->device = reference->device;
   m->have_depths = depths != nullptr;
   if (depths) m->depths.assign(depths, depths + T);
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, reference->device) == hipSuccess && cus > 0)
-    m->blocks = (unsigned)cus * MG_BLOCKS_PER_CU;
-  else (void)hipGetLastError();
   // SLK_MIGRATION_BLOCKS: the grid (tests: a few blocks see more pairs than their LDS maps hold; measurements: occupancy)
-  const long env_blocks = env_long("SLK_MIGRATION_BLOCKS", 0);
-  if (env_blocks > 0) m->blocks = (unsigned)std::min(env_blocks, 65535L);
+  m->blocks = grid_for(reference->device, MG_BLOCKS_PER_CU, "SLK_MIGRATION_BLOCKS");
   hipError_t e = m->counters.ensure(24);
   if (e == hipSuccess) e = m->status.ensure(8);
   if (e == hipSuccess) e = hipMemset(m->counters.p, 0, 24);

@@ -1,5 +1,7 @@
 // pairmap.h -- the device-wide (a << 32 | b) -> uint64 count map that bracken.hip (source, dest) and migration.hip (t1, t2) add
-// into, and that coverage.hip keys by (cell << 28 | source) and by (source << 32 | depth): open addressing with linear probing over a power-of-two number of slots, two parallel arrays in HBM.  Internal.
+// into, and that coverage.hip keys by (cell << 28 | source) and by (source << 32 | depth): open addressing with linear probing over
+// a power-of-two number of slots, two parallel arrays in HBM (coverage.hip keeps a third beside them), moved to a larger map by
+// PairMap::grow_into.  Internal.
 #pragma once
 #include "hostside.h"
 
@@ -39,6 +41,22 @@ __device__ __forceinline__ bool pair_map_add2(unsigned long long *keys, unsigned
   return false;
 }
 
+// every pair of an old map into a new one (which has room: it is larger); TWO: a second counter per key (old_second, second).
+// A template, so that only the translation units that grow a map hold the kernel.
+template <bool TWO>
+__global__ void __launch_bounds__(256) pair_map_rehash_kernel(const unsigned long long *old_keys, const unsigned long long *old_first,
+                                                              const unsigned long long *old_second, uint64_t old_cap,
+                                                              unsigned long long *keys, unsigned long long *first,
+                                                              unsigned long long *second, uint64_t mask, int32_t *status) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap; i += stride) {
+    if (old_keys[i] == PAIR_EMPTY) continue;
+    const bool ok = TWO ? pair_map_add2(keys, first, second, mask, old_keys[i], old_first[i], old_second[i], nullptr)
+                        : pair_map_add(keys, first, mask, old_keys[i], old_first[i], nullptr);
+    if (!ok) atomicOr(status, 2);
+  }
+}
+
 struct PairMap {
   DevBuf keys, counts;
   uint64_t cap = 0;   // slots, a power of two
@@ -51,6 +69,18 @@ struct PairMap {
     HIPCHK(hipMemsetAsync(keys.p, 0xff, slots * 8, s));
     HIPCHK(hipMemsetAsync(counts.p, 0, slots * 8, s));
     cap = slots;
+    return SLK_OK;
+  }
+  // Every pair of this map into `now`, a larger one that the caller has reset; TWO: with the second counters beside the two maps
+  // (second, now_second; null otherwise).  A pair that finds no room sets bit 1 of *status (device memory).  Synchronises s: this
+  // map can be freed.
+  template <bool TWO>
+  int32_t grow_into(hipStream_t s, PairMap &now, const DevBuf *second, DevBuf *now_second, int32_t *status) const {
+    hipLaunchKernelGGL(pair_map_rehash_kernel<TWO>, dim3((unsigned)std::min<uint64_t>((cap + 255) / 256, 4096)), dim3(256), 0, s, k(), c(),
+                       TWO ? second->as<unsigned long long>() : nullptr, cap, now.k(), now.c(),
+                       TWO ? now_second->as<unsigned long long>() : nullptr, now.cap - 1, status);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
     return SLK_OK;
   }
   // the pairs with their counts, unordered; synchronises s

@@ -6,17 +6,17 @@
 //
 // The stream: persistent blocks, a grid-stride loop over 16-byte elements (two cells) with RS_UNROLL loads in flight per lane, as
 // taxon_counts_kernel reads them.  About half the cells of a table are empty and insert_merge diverges, so the occupied cells of a
-// wave are compacted first: they go to a wave-shared LDS queue (as build_kernel's minimizers do) and are inserted 64 at a time, one
+// wave are compacted first: they go to a wave-shared LDS queue (wavetools.h: WaveQueue) and are inserted 64 at a time, one
 // lane per record.  What bounds the pass is the random traffic to the destination -- one bucket read and one CAS per record, parent
 // walks where the taxa of a group differ -- not the stream.  Records that share a masked key are scattered over the source by fmix64,
-// so merging them inside a wave or a block first (taxstats.hip's levels) would find next to nothing to merge.
+// so merging them inside a wave or a block first (wavetools.h: the three levels) would find next to nothing to merge.
 //
 // The taxon travels as the cell holds it (the dense id on an index that slk_index_finalize renumbered): the destination is given the
 // same taxon field and the same id tables.  The source is only read; LCA is associative, commutative and idempotent, so the pass can
 // be repeated into a fresh table from scratch (index.hip does when a record finds no cell within the displacement limit).
 #include <hip/hip_runtime.h>
 
-#include "engine.h"
+#include "hostside.h"
 #include "tablebuild.h"
 
 namespace slk {
@@ -40,31 +40,18 @@ __global__ void __launch_bounds__(RS_BLOCK) respace_kernel(TableView S, TableBui
   const uint32_t wib = __builtin_amdgcn_readfirstlane(tid >> 6);
   const ulonglong2 *__restrict__ cells = (const ulonglong2 *)S.cells;
   const uint64_t tmask = (1ULL << S.g.taxon_bits) - 1;
-  uint32_t qhead = 0, qn = 0;              // wave-uniform
+  WaveQueue<int32_t> Q(L.q_key[wib], L.q_tax[wib], lane);
   int created = 0, failed = 0, max_d = 0;  // per lane
 
-  auto flush = [&](uint32_t cnt) {         // insert cnt (<= 64) queued records, one per lane
-    if (lane < cnt) {
-      const uint32_t e = (qhead + lane) & 127;
-      const int r = insert_merge(D, parents, ntax, L.q_key[wib][e], L.q_tax[wib][e], max_d);
-      created += (r == 1);
-      failed += (r < 0);
-    }
-    qhead = (qhead + cnt) & 127;
-    qn -= cnt;
+  auto insert = [&](uint32_t e, bool active) {   // the queued records, one per lane
+    if (!active) return;
+    const int r = insert_merge(D, parents, ntax, L.q_key[wib][e], L.q_tax[wib][e], max_d);
+    created += (r == 1);
+    failed += (r < 0);
   };
   auto push = [&](uint64_t i, uint64_t cell) {   // cell i of the source, from every lane of the wave at once
     const bool has = (cell & tmask) != 0;
-    const uint64_t mask = __ballot(has);
-    if (mask == 0) return;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-    if (has) {
-      const uint32_t e = (qhead + qn + before) & 127;
-      L.q_key[wib][e] = cell_key(S.g, i, cell) & new_smask;
-      L.q_tax[wib][e] = (int32_t)(cell & tmask);
-    }
-    qn += (uint32_t)__popcll(mask);
-    if (qn >= 64) flush(64);   // (qn < 64 before the push and at most 64 came: the queue of 128 never wraps onto itself)
+    Q.push(has, has ? cell_key(S.g, i, cell) & new_smask : 0, (int32_t)(cell & tmask), insert);
   };
 
   const uint64_t tile = (uint64_t)RS_BLOCK * RS_UNROLL, stride = (uint64_t)gridDim.x * tile;
@@ -82,18 +69,8 @@ __global__ void __launch_bounds__(RS_BLOCK) respace_kernel(TableView S, TableBui
       push(2 * i + 1, v[u].y);
     }
   }
-  if (qn) flush(qn);  // qn < 64 here
-
-  for (int o = 32; o > 0; o >>= 1) {
-    created += __shfl_xor(created, o);
-    failed += __shfl_xor(failed, o);
-    max_d = max(max_d, __shfl_xor(max_d, o));
-  }
-  if (lane == 0) {
-    if (created) atomicAdd(D.n_inserted, (unsigned long long)created);
-    if (failed) atomicAdd(D.n_overflow, (unsigned long long)failed);
-    if (max_d) atomicMax(D.max_disp, max_d);
-  }
+  Q.drain(insert);
+  report_inserts(D, lane, created, failed, max_d);
 }
 
 }  // namespace
@@ -101,13 +78,8 @@ __global__ void __launch_bounds__(RS_BLOCK) respace_kernel(TableView S, TableBui
 void launch_respace(const TableView &src, const TableBuild &dst, uint64_t new_smask, const int32_t *parents, int32_t ntax, hipStream_t s) {
   const uint64_t n = src.g.nbuckets * LPB;   // 16-byte elements of the source
   if (n == 0) return;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) {
-    (void)hipGetLastError();
-    cus = 256;
-  }
   const uint64_t tile = (uint64_t)RS_BLOCK * RS_UNROLL;
-  const unsigned grid = (unsigned)std::min<uint64_t>((n + tile - 1) / tile, (uint64_t)cus * RS_BLOCKS_PER_CU);
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + tile - 1) / tile, (uint64_t)grid_for(-1, RS_BLOCKS_PER_CU, nullptr));
   hipLaunchKernelGGL(respace_kernel, dim3(grid), dim3(RS_BLOCK), 0, s, src, dst, new_smask, parents, ntax, n);
 }
 

@@ -2,7 +2,7 @@
 // (S/slacken/Dynamic.scala:95-117: -C's count(minimizer) and -D's count_distinct(minimizer) per taxon) and Dynamic.multiStatsPerTaxon
 // (:152-180: totalKmerCount, distinctMinimizerCount, totalMinimizerCount of the support reports).  The reference joins every SEQUENCE
 // super-mer of every read with the records, keeps the hits whose taxon has depth(taxon) >= rank.depth and groups them by taxon.  Here:
-//   scan    support_scan_kernel, the lane-per-chunk scan of chunkscan.h (coverage.hip's, with its exact seams): one lane per chunk of
+//   scan    support_scan_kernel, the lane-per-chunk scan of chunkscan.h with exact seams: one lane per chunk of
 //           BUILD_CHUNK_WINDOWS windows -- a 150-base read is one chunk, a long read several.  A super-mer is queued when it CLOSES
 //           (at the next fresh minimizer -- an invalid base makes the next window fresh -- or at the end of the chunk), so that its
 //           queue entry (key, k-mer windows, starts_here) holds its window count.  A super-mer that runs on from the chunk before
@@ -15,13 +15,10 @@
 //           one bit per table cell in a bitmap owned by the handle, no pair map, no budget, no sort.  The word is read first and
 //           atomicOr is issued only where the bit is clear (a deep sample repeats most of its minimizers); the lane whose atomicOr
 //           returns the bit clear owns the increment.
-// The three sums go through the three levels of taxstats.hip, because a sample's hits pile onto a handful of taxa:
-//   wave    SP_LEADER_ROUNDS times the first lane still holding a hit names its taxon, the lanes with the same taxon hand their three
-//           numbers to it and leave
-//   block   an open-addressing map taxon -> 3 x uint32 in LDS (SP_SLOTS slots, at most SP_PROBES probes)
-//   device  three uint64 arrays indexed by the taxon the cells hold (the dense internal id of a finalized index); at the end of the
-//           block every occupied LDS slot goes there.  A lane that finds no LDS slot within SP_PROBES adds to the arrays itself.
-// Every route is an addition: the result does not depend on the route.  A lane owns ONE chunk (the grid is not strided), so all that
+// The three sums go through the three levels of wavetools.h, because a sample's hits pile onto a handful of taxa: SP_LEADER_ROUNDS
+// rounds in the wave, the lanes under the leader's taxon handing it their three numbers (wave sums); a map taxon -> 3 x uint32 in LDS
+// (SP_SLOTS slots, at most SP_PROBES probes); three uint64 arrays indexed by the taxon the cells hold (the dense internal id of a
+// finalized index).  A lane owns ONE chunk (the grid is not strided), so all that
 // a block can add to its LDS counters are the windows of its own chunks: at most SP_W * 64 chunks of BUILD_CHUNK_WINDOWS windows
 // = 2^17 per launch, whatever the launch's size -- no 32-bit LDS counter can wrap (static_assert below).
 //
@@ -32,6 +29,7 @@
 // VGPRs: the scan's state and one 64-byte bucket per lane during the probe: the compiler reports 79 per lane and no scratch, which
 // allows six waves per SIMD -- one more than the five (20 waves per CU) that the LDS admits at k = 35, m = 31 (coverage_scan_kernel has 75
 // registers and 22 KiB less LDS).  The kernel waits for the random table requests; nothing here was tuned against a measurement.
+#include "chunkcut.h"
 #include "chunkscan.h"
 #include "hostside.h"
 
@@ -52,7 +50,7 @@ enum { SP_ROWS = 0, SP_SUPERMERS = 1, SP_MATCHED = 2, SP_KEPT = 3, SP_CURSOR = 4
 struct SupLds {
   uint64_t q_key[SP_W][128];
   uint32_t q_meta[SP_W][128];       // windows | SP_FLAG
-  uint32_t keys[SP_SLOTS];          // 0: free (no record has taxon 0)
+  LdsCountMap<unsigned int, 0u, SP_SLOTS, SP_PROBES, true> map;   // by taxon; 0: free (no record has taxon 0)
   uint32_t kmers[SP_SLOTS], minimizers[SP_SLOTS], distinct[SP_SLOTS];
 };
 
@@ -79,33 +77,25 @@ __device__ __forceinline__ void sp_global_add(const SupArgs &A, uint32_t taxon, 
 }
 
 __device__ __forceinline__ void sp_block_add(const SupArgs &A, SupLds &L, uint32_t taxon, uint32_t k, uint32_t m, uint32_t d) {
-  uint32_t h = (taxon * 0x9E3779B1u) >> 22 & (SP_SLOTS - 1);
-  for (int probe = 0; probe < SP_PROBES; probe++) {
-    unsigned int prev = __atomic_load_n(&L.keys[h], __ATOMIC_RELAXED);   // (a slot never changes owner: a read that finds the taxon saves the CAS)
-    if (prev == 0) prev = atomicCAS(&L.keys[h], 0u, taxon);
-    if (prev == 0 || prev == taxon) {
-      atomicAdd(&L.kmers[h], k);
-      if (m) atomicAdd(&L.minimizers[h], m);
-      if (d) atomicAdd(&L.distinct[h], d);
-      return;
-    }
-    h = (h + 1) & (SP_SLOTS - 1);
-  }
-  sp_global_add(A, taxon, k, m, d);
+  L.map.add(taxon, (taxon * 0x9E3779B1u) >> 22,
+            [&](uint32_t h) {
+              atomicAdd(&L.kmers[h], k);
+              if (m) atomicAdd(&L.minimizers[h], m);
+              if (d) atomicAdd(&L.distinct[h], d);
+            },
+            [&] { sp_global_add(A, taxon, k, m, d); });
 }
 
 // the wave's lanes hand in one counted hit each (taxon 0: none); called by whole waves
 __device__ __forceinline__ void sp_wave_add(const SupArgs &A, SupLds &L, uint32_t lane, uint32_t taxon, uint32_t k, uint32_t m, uint32_t d) {
   bool have = taxon != 0;
   for (int round = 0; round < SP_LEADER_ROUNDS; round++) {
-    const uint64_t holding = __ballot(have);
-    if (holding == 0) return;
-    const uint32_t leader = (uint32_t)__ffsll((unsigned long long)holding) - 1;
-    const uint32_t lt = (uint32_t)__shfl((int)taxon, (int)leader);
-    const bool same = have && taxon == lt;
-    const uint32_t ks = wave_sum32(same ? k : 0u), ms = wave_sum32(same ? m : 0u), ds = wave_sum32(same ? d : 0u);
-    if (lane == leader) sp_block_add(A, L, lt, ks, ms, ds);
-    have = have && !same;
+    const bool any = leader_round(have, taxon, [&](int leader, uint32_t lt, bool same) {
+      const uint32_t ks = wave_sum32(same ? k : 0u), ms = wave_sum32(same ? m : 0u), ds = wave_sum32(same ? d : 0u);
+      if ((int)lane == leader) sp_block_add(A, L, lt, ks, ms, ds);
+      have = have && !same;
+    });
+    if (!any) return;
   }
   if (have) sp_block_add(A, L, taxon, k, m, d);
 }
@@ -116,8 +106,7 @@ __global__ void __launch_bounds__(SP_W * 64) support_scan_kernel(SupArgs A) {
   const ScanParams &P = A.P;
   const uint32_t tid = threadIdx.x, lane = tid & 63, stride = blockDim.x;
   const uint32_t wib = __builtin_amdgcn_readfirstlane(tid >> 6);
-  for (uint32_t s = tid; s < SP_SLOTS; s += stride) { L.keys[s] = 0; L.kmers[s] = 0; L.minimizers[s] = 0; L.distinct[s] = 0; }
-  __syncthreads();
+  L.map.clear(tid, stride, [&](uint32_t s) { L.kmers[s] = 0; L.minimizers[s] = 0; L.distinct[s] = 0; });
   const uint64_t c = (uint64_t)blockIdx.x * stride + tid;
   const bool mine = c < A.nchunks;
   const uint32_t packed = mine ? A.chunk_len[c] : 0;
@@ -130,13 +119,12 @@ __global__ void __launch_bounds__(SP_W * 64) support_scan_kernel(SupArgs A) {
   uint64_t open_key = 0;               // the super-mer that has not closed yet: its minimizer, its windows so far (0: none is open),
   uint32_t open_kmers = 0;             // and whether it started in this chunk
   bool open_starts = false;
-  uint32_t qhead = 0, qn = 0;          // wave-uniform
+  WaveQueue<uint32_t> Q(L.q_key[wib], L.q_meta[wib], lane);
   uint32_t n_supermers = 0, n_matched = 0, n_kept = 0;   // of the entries this lane looked up: those that start a super-mer
 
-  auto flush = [&](uint32_t cnt) {     // look up cnt (<= 64) queued minimizers, one per lane, and count them
+  auto count = [&](uint32_t e, bool active) {   // look the queued minimizers up, one per lane, and count them (whole waves)
     uint32_t taxon = 0, k = 0, m = 0, d = 0;
-    if (lane < cnt) {
-      const uint32_t e = (qhead + lane) & 127;
+    if (active) {
       const uint32_t meta = L.q_meta[wib][e], starts = meta >> 31;
       uint64_t cell = 0;
       const uint32_t t = (uint32_t)table_lookup_cell(A.T, L.q_key[wib][e], &cell);   // a miss (NONE) is never counted
@@ -156,20 +144,6 @@ __global__ void __launch_bounds__(SP_W * 64) support_scan_kernel(SupArgs A) {
       }
     }
     sp_wave_add(A, L, lane, taxon, k, m, d);
-    qhead = (qhead + cnt) & 127;
-    qn -= cnt;
-  };
-  auto enqueue = [&](bool emit, uint64_t key, uint32_t meta) {   // (whole waves)
-    const uint64_t mask = __ballot(emit);
-    if (mask == 0) return;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-    if (emit) {
-      const uint32_t e = (qhead + qn + before) & 127;   // (qn < 64 on entry: at most 127 entries)
-      L.q_key[wib][e] = key;
-      L.q_meta[wib][e] = meta;
-    }
-    qn += (uint32_t)__popcll(mask);
-    if (qn >= 64) flush(64);
   };
 
   for (uint32_t step = 0; step < maxlen; step++) {
@@ -186,10 +160,10 @@ __global__ void __launch_bounds__(SP_W * 64) support_scan_kernel(SupArgs A) {
       if (open_kmers == 0) { open_key = S.cur_val; open_starts = false; }   // (it runs on from the chunk before: the priming window had it)
       open_kmers++;
     }
-    enqueue(emit, key, meta);
+    Q.push(emit, key, meta, count);
   }
-  enqueue(open_kmers != 0, open_key, open_kmers | (open_starts ? SP_FLAG : 0u));   // the end of the chunk closes what is open
-  if (qn) flush(qn);  // qn < 64 here
+  Q.push(open_kmers != 0, open_key, open_kmers | (open_starts ? SP_FLAG : 0u), count);   // the end of the chunk closes what is open
+  Q.drain(count);
 
   const uint32_t ws = wave_sum32(n_supermers), wm = wave_sum32(n_matched), wk = wave_sum32(n_kept);
   if (lane == 0) {
@@ -197,9 +171,7 @@ __global__ void __launch_bounds__(SP_W * 64) support_scan_kernel(SupArgs A) {
     if (wm) atomicAdd(A.small + SP_MATCHED, (unsigned long long)wm);
     if (wk) atomicAdd(A.small + SP_KEPT, (unsigned long long)wk);
   }
-  __syncthreads();
-  for (uint32_t s = tid; s < SP_SLOTS; s += stride)
-    if (L.keys[s] != 0) sp_global_add(A, L.keys[s], L.kmers[s], L.minimizers[s], L.distinct[s]);
+  L.map.drain(tid, stride, [&](uint32_t taxon, uint32_t s) { sp_global_add(A, taxon, L.kmers[s], L.minimizers[s], L.distinct[s]); });
 }
 
 // keep[t] = the taxon that the cells hold as t has depth >= min_depth in the caller's depths (an id outside [0, n): depth -1)
@@ -214,7 +186,7 @@ __global__ void __launch_bounds__(256) support_keep_kernel(TableView T, const in
 }
 
 // The rows with k-mers (every counted hit has at least one) as (taxon in the caller's ids, kmers, minimizers, distinct), in any
-// order: their number is known (SP_ROWS) and the host sorts them.  One atomic per wave, as taxon_pairs_kernel (taxstats.hip).
+// order: their number is known (SP_ROWS) and the host sorts them.  One atomic per wave (wavetools.h: wave_alloc_slots).
 __global__ void __launch_bounds__(256) support_rows_kernel(TableView T, const unsigned long long *__restrict__ kmers,
                                                            const unsigned long long *__restrict__ minimizers,
                                                            const unsigned long long *__restrict__ distinct, uint64_t domain,
@@ -225,14 +197,7 @@ __global__ void __launch_bounds__(256) support_rows_kernel(TableView T, const un
     const uint64_t t = base + threadIdx.x;
     const unsigned long long k = t < domain ? kmers[t] : 0;
     const bool has = k != 0;
-    const uint64_t mask = __ballot(has);
-    if (mask == 0) continue;
-    unsigned long long first = 0;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-    if (has && before == 0) first = atomicAdd(cursor, (unsigned long long)__popcll(mask));
-    const int leader = __ffsll((long long)mask) - 1;
-    first = ((unsigned long long)(uint32_t)__shfl((int)(first >> 32), leader) << 32) | (uint32_t)__shfl((int)first, leader);
-    const unsigned long long slot = first + before;
+    const unsigned long long slot = wave_alloc_slots(has, cursor);
     if (has && slot < capacity) {
       taxa[slot] = ext_taxon(T, (int32_t)t);
       out[slot] = k;
@@ -260,14 +225,9 @@ struct slk_support {
 };
 
 static int32_t sp_enter(slk_support *s) {
-  if (!s) return fail(SLK_E_INVALID, "null handle");
-  if (s->spent) return fail(SLK_E_STATE, "support: an earlier call on this handle failed, its counts are incomplete");
-  return set_device(s->ix);
+  return enter_handle(s, "support: an earlier call on this handle failed, its counts are incomplete");
 }
-static int32_t sp_leave(slk_support *s, int32_t rc) {   // SLK_E_HIP leaves the counts incomplete
-  if (rc == SLK_E_HIP) s->spent = true;
-  return rc;
-}
+static int32_t sp_leave(slk_support *s, int32_t rc) { return leave_handle(s, rc, rc == SLK_E_HIP); }   // SLK_E_HIP leaves the counts incomplete
 
 static int32_t sp_add(slk_support *sp, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, uint64_t R) {
   slk_index *ix = sp->ix;
@@ -275,26 +235,15 @@ static int32_t sp_add(slk_support *sp, slk_stream *st, const uint8_t *bases, con
   const uint32_t k = (uint32_t)ix->sp.k, CW = BUILD_CHUNK_WINDOWS;
   std::vector<uint64_t> cstart;
   std::vector<uint32_t> clen;
-  uint64_t i = 0;
-  while (i < R) {   // groups of whole sequences of about 1 GiB, cut into chunks of CW windows
-    uint64_t j = i;
-    const uint64_t g0 = offsets[i];
-    while (j < R && (j == i || offsets[j + 1] - g0 <= SP_GROUP_BYTES)) j++;
-    const uint64_t gbytes = offsets[j] - g0;
+  for (uint64_t i = 0, j; i < R; i = j) {   // groups of whole sequences of about 1 GiB, cut into chunks of CW windows
+    j = group_end(offsets, i, R, SP_GROUP_BYTES);
+    const uint64_t g0 = offsets[i], gbytes = offsets[j] - g0;
     cstart.clear(); clen.clear();
     cstart.reserve((j - i) + gbytes / CW); clen.reserve((j - i) + gbytes / CW);   // (a chunk per sequence and one more per CW windows at most)
-    for (uint64_t q = i; q < j; q++) {
-      const uint64_t len = offsets[q + 1] - offsets[q];
-      if (len < k) continue;
-      const uint64_t windows = len - k + 1;
-      for (uint64_t w0 = 0; w0 < windows; w0 += CW) {
-        const uint64_t nw = std::min<uint64_t>(CW, windows - w0);
-        const uint64_t early = w0 ? 1 : 0;   // (one base of the chunk before: its last window primes this one)
-        cstart.push_back(offsets[q] - g0 + w0 - early);
-        clen.push_back((uint32_t)(nw + k - 1 + early) | (early ? SP_FLAG : 0u));
-      }
-    }
-    i = j;
+    cut_chunks(offsets, i, j, k, CW, true, [](uint64_t) { return false; }, [&](uint64_t, uint64_t start, uint32_t len, uint32_t early) {
+      cstart.push_back(start);
+      clen.push_back(len | (early ? SP_FLAG : 0u));
+    });
     const uint64_t nc = cstart.size();
     if (nc == 0) continue;
     HIPCHK(sp->d_bases.ensure(gbytes));
@@ -338,12 +287,9 @@ int32_t slk_support_create(slk_index *ix, const int32_t *depths, int32_t T, int3
   if (!ix) return fail(SLK_E_INVALID, "null handle");
   if (T < 0 || (T > 0 && !depths)) return fail(SLK_E_INVALID, "depths must hold T >= 0 entries");
   if (min_depth < 0) return fail(SLK_E_INVALID, "min_depth must not be negative");
-  if (!ix->finalized) return fail(SLK_E_STATE, "index is not finalized");
-  if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "sample support supports minimizers of up to 32 nt (one id column)");
-  if (ix->n_shards > 1) return fail(SLK_E_UNSUPPORTED, "sample support needs the whole table on one GPU (the index is a shard)");
-  if (ix->sp.w > BUILD_MAX_W)
-    return fail(SLK_E_UNSUPPORTED, "sample support supports windows of up to %d m-mers (k - m + 1 = %d)", BUILD_MAX_W, ix->sp.w);
-  int32_t rc = set_device(ix);
+  int32_t rc = check_whole_narrow_index(ix, "sample support", "table", true);
+  if (rc) return rc;
+  rc = set_device(ix);
   if (rc) return rc;
   std::unique_ptr<slk_support> s(new slk_support());   // (released into *out on success only)
   s->ix = ix;

@@ -2,6 +2,7 @@
 // export; respace.hip: a table derived from a resident one): the insert-or-merge of one record, and a cell back to its key.
 #pragma once
 #include "engine.h"
+#include "wavetools.h"
 
 namespace slk {
 
@@ -46,6 +47,16 @@ __device__ inline int insert_merge(const TableBuild &t, const int32_t *parents, 
     if (t.g.flag && !(first & t.g.flag)) atomicOr(&bucket[0], (unsigned long long)t.g.flag);
   }
   return -1;
+}
+
+// What a wave's lanes counted over their insert_merge calls, to the table's counters: one lane adds the wave's sums.
+__device__ __forceinline__ void report_inserts(const TableBuild &t, uint32_t lane, int created, int failed, int max_d) {
+  const uint32_t wc = wave_sum32((uint32_t)created), wf = wave_sum32((uint32_t)failed), wd = wave_max32((uint32_t)max_d);
+  if (lane == 0) {
+    if (wc) atomicAdd(t.n_inserted, (unsigned long long)wc);
+    if (wf) atomicAdd(t.n_overflow, (unsigned long long)wf);
+    if (wd) atomicMax(t.max_disp, (int)wd);
+  }
 }
 
 __host__ __device__ inline uint64_t fmix64_inverse(uint64_t x) {

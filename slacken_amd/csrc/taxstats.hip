@@ -4,14 +4,10 @@
 // buckets are read coalesced, 16 B (two cells) per lane, as table_lookup reads them; a cell whose taxon field is 0 is empty (an
 // occupied cell has taxon != 0, and the top bit of a bucket's first cell -- TableGeom.flag -- lies outside the field).
 //
-// The count has the three levels of migration.hip, so that the few high LCAs that hold a large share of a real library's records do
-// not serialise on a handful of HBM addresses:
-//   wave    TS_LEADER_ROUNDS times, the first lane still holding a taxon names it; the lanes holding the same taxon are counted
-//           with a ballot and leave, and the leader alone adds their number
-//   block   an open-addressing map taxon -> uint32 in LDS (TS_SLOTS slots, at most TS_PROBES probes) takes those sums and the lanes left
-//   device  at the end of the block every occupied LDS slot goes to the device-wide counters with one 64-bit atomic
-// A lane that finds no LDS slot within TS_PROBES adds to the device-wide counters itself.  Every route is an addition: the result
-// does not depend on which one a record took.  A block's LDS counters are 32-bit; a launch covers at most TS_LAUNCH_MAX = 2^30
+// The count has the three levels of wavetools.h, so that the few high LCAs that hold a large share of a real library's records do
+// not serialise on a handful of HBM addresses: TS_LEADER_ROUNDS rounds in the wave, the lanes under the leader's taxon counted with
+// a ballot; a map taxon -> uint32 in LDS (TS_SLOTS slots, at most TS_PROBES probes); the device-wide counters, one 64-bit atomic
+// per occupied LDS slot at the end of the block.  A block's LDS counters are 32-bit; a launch covers at most TS_LAUNCH_MAX = 2^30
 // 16-byte loads = 2^31 cells (the host cuts larger tables into several launches), so no block can see as many as 2^32 records
 // between two flushes.
 //
@@ -22,6 +18,7 @@
 // so it can be repeated).
 #include "hostside.h"
 #include "pairmap.h"
+#include "wavetools.h"
 
 namespace {
 
@@ -57,38 +54,30 @@ __device__ __forceinline__ void ts_global_add(const TsArgs &A, uint32_t taxon, u
   }
 }
 
-__device__ __forceinline__ void ts_block_add(const TsArgs &A, unsigned int *lkeys, unsigned int *lcounts, uint32_t taxon, unsigned int c) {
-  uint32_t h = (taxon * 0x9E3779B1u) >> 20 & (TS_SLOTS - 1);
-  for (int probe = 0; probe < TS_PROBES; probe++) {
-    unsigned int prev = __atomic_load_n(&lkeys[h], __ATOMIC_RELAXED);   // (a slot never changes owner: a read that finds the taxon saves the CAS)
-    if (prev == 0) prev = atomicCAS(&lkeys[h], 0u, taxon);
-    if (prev == 0 || prev == taxon) { atomicAdd(&lcounts[h], c); return; }
-    h = (h + 1) & (TS_SLOTS - 1);
-  }
-  ts_global_add(A, taxon, c);
+using TsMap = LdsCountMap<unsigned int, 0u, TS_SLOTS, TS_PROBES, true>;   // by taxon; 0: free (no record has taxon 0)
+
+__device__ __forceinline__ void ts_block_add(const TsArgs &A, TsMap &M, unsigned int *lcounts, uint32_t taxon, unsigned int c) {
+  M.add(taxon, (taxon * 0x9E3779B1u) >> 20, [&](uint32_t h) { atomicAdd(&lcounts[h], c); }, [&] { ts_global_add(A, taxon, c); });
 }
 
 // the wave's lanes hand in one taxon each (0: none)
-__device__ __forceinline__ void ts_wave_add(const TsArgs &A, unsigned int *lkeys, unsigned int *lcounts, int lane, uint32_t taxon) {
+__device__ __forceinline__ void ts_wave_add(const TsArgs &A, TsMap &M, unsigned int *lcounts, int lane, uint32_t taxon) {
   bool have = taxon != 0;
   for (int round = 0; round < TS_LEADER_ROUNDS; round++) {
-    const uint64_t holding = __ballot(have);
-    if (holding == 0) return;
-    const int leader = __ffsll((unsigned long long)holding) - 1;
-    const uint32_t lt = (uint32_t)__shfl((int)taxon, leader);
-    const bool same = have && taxon == lt;
-    const uint64_t group = __ballot(same);
-    if (lane == leader) ts_block_add(A, lkeys, lcounts, lt, (unsigned int)__popcll(group));
-    have = have && !same;
+    const bool any = leader_round(have, taxon, [&](int leader, uint32_t lt, bool same) {
+      const uint64_t group = __ballot(same);
+      if (lane == leader) ts_block_add(A, M, lcounts, lt, (unsigned int)__popcll(group));
+      have = have && !same;
+    });
+    if (!any) return;
   }
-  if (have) ts_block_add(A, lkeys, lcounts, taxon, 1u);
+  if (have) ts_block_add(A, M, lcounts, taxon, 1u);
 }
 
 __global__ void __launch_bounds__(TS_BLOCK) taxon_counts_kernel(TsArgs A) {
-  __shared__ unsigned int lkeys[TS_SLOTS];   // 0: free (no record has taxon 0)
+  __shared__ TsMap M;
   __shared__ unsigned int lcounts[TS_SLOTS];
-  for (uint32_t s = threadIdx.x; s < TS_SLOTS; s += TS_BLOCK) { lkeys[s] = 0; lcounts[s] = 0; }
-  __syncthreads();
+  M.clear(threadIdx.x, TS_BLOCK, [&](uint32_t s) { lcounts[s] = 0; });
   const int lane = threadIdx.x & 63;
   uint64_t n_records = 0;   // of this wave (every lane keeps the same number)
   const uint64_t tile = (uint64_t)TS_BLOCK * TS_UNROLL, stride = (uint64_t)gridDim.x * tile;
@@ -103,14 +92,12 @@ __global__ void __launch_bounds__(TS_BLOCK) taxon_counts_kernel(TsArgs A) {
     for (int u = 0; u < TS_UNROLL; u++) {
       const uint32_t t0 = (uint32_t)(v[u].x & A.tmask), t1 = (uint32_t)(v[u].y & A.tmask);
       n_records += (uint64_t)__popcll(__ballot(t0 != 0)) + (uint64_t)__popcll(__ballot(t1 != 0));
-      ts_wave_add(A, lkeys, lcounts, lane, t0);
-      ts_wave_add(A, lkeys, lcounts, lane, t1);
+      ts_wave_add(A, M, lcounts, lane, t0);
+      ts_wave_add(A, M, lcounts, lane, t1);
     }
   }
   if (lane == 0 && n_records) atomicAdd(A.totals + 1, (unsigned long long)n_records);
-  __syncthreads();
-  for (uint32_t s = threadIdx.x; s < TS_SLOTS; s += TS_BLOCK)
-    if (lkeys[s] != 0) ts_global_add(A, lkeys[s], (unsigned long long)lcounts[s]);
+  M.drain(threadIdx.x, TS_BLOCK, [&](uint32_t taxon, uint32_t s) { ts_global_add(A, taxon, (unsigned long long)lcounts[s]); });
 }
 
 // The non-zero counters as (taxon, count) pairs, the taxon in the caller's ids (ext_taxon).  The pairs leave in any order -- their
@@ -123,15 +110,7 @@ __global__ void __launch_bounds__(256) taxon_pairs_kernel(TableView T, const uns
     const uint64_t t = base + threadIdx.x;
     const unsigned long long c = t < domain ? counts[t] : 0;
     const bool has = c != 0;
-    const uint64_t mask = __ballot(has);
-    if (mask == 0) continue;
-    // one atomic per wave: the lanes' output slots are consecutive
-    unsigned long long first = 0;
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-    if (has && before == 0) first = atomicAdd(cursor, (unsigned long long)__popcll(mask));
-    const int leader = __ffsll((long long)mask) - 1;
-    first = ((unsigned long long)(uint32_t)__shfl((int)(first >> 32), leader) << 32) | (uint32_t)__shfl((int)first, leader);
-    const unsigned long long slot = first + before;
+    const unsigned long long slot = wave_alloc_slots(has, cursor);   // one atomic per wave: the lanes' output slots are consecutive
     if (has && slot < capacity) {
       taxa[slot] = ext_taxon(T, (int32_t)t);
       out[slot] = c;
@@ -183,14 +162,8 @@ extern "C" int32_t slk_index_taxon_counts(const slk_index *ix, int32_t *taxa, ui
   if (rc) return rc;
   if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "taxon counts support minimizers of up to 32 nt (one id column)");
   hipStream_t s = ix->build_stream;   // the stream the records were inserted on: the pass sees them all
-  unsigned blocks = 256 * TS_BLOCKS_PER_CU;
-  int cus = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ix->device) == hipSuccess && cus > 0)
-    blocks = (unsigned)cus * TS_BLOCKS_PER_CU;
-  else (void)hipGetLastError();
   // SLK_TAXSTATS_BLOCKS: the grid (tests: a grid whose stride does not divide the table; measurements: occupancy)
-  const long env_blocks = env_long("SLK_TAXSTATS_BLOCKS", 0);
-  if (env_blocks > 0) blocks = (unsigned)std::min(env_blocks, 65535L);
+  const unsigned blocks = grid_for(ix->device, TS_BLOCKS_PER_CU, "SLK_TAXSTATS_BLOCKS");
 
   // the ids the cells hold: dense ranks 1 .. D, or the caller's ids below 2^taxon_bits
   const uint64_t ids = ix->D ? (uint64_t)ix->D + 1 : 1ULL << ix->taxon_bits;

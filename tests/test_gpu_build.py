@@ -230,3 +230,26 @@ def test_real_contig_with_long_n_runs(orc):
         assert [(int(t), int(c)) for t, c in zip(g["taxon"], g["count"])] == hits
         if i == 0:
             assert any(t == -1 and c > 1000 for t, c in hits)       # an ambiguous span of thousands of k-mers
+
+
+def test_wave_queue_edges(orc):
+    """The per-wave queue of build_kernel at its two ends.  64 sequences of exactly k bases are 64 one-window chunks of one wave, and
+    every lane starts its only super-mer at step k - 1: one push brings exactly 64 records.  One sequence of k + 510 bases is one
+    chunk in a wave of its own with more super-mers than the queue's 128 entries: the ring's index wraps, and the tail flush takes
+    fewer than 64."""
+    import slacken_amd
+    rng = np.random.default_rng(64)
+    parents = taxgen.taxonomy(8 * 16, rng)
+    p = orc.params()
+    k = 35
+    taxa = np.array(taxgen.defined_taxa(parents))
+    for seqs in ([synth.random_dna(k, rng).tobytes().decode() for _ in range(64)], [synth.random_dna(k + 510, rng).tobytes().decode()]):
+        tx = [int(taxa[1 + i % (len(taxa) - 1)]) for i in range(len(seqs))]
+        bases, offsets = pack(seqs)
+        want_k, want_t = orc.build_records(p, parents, bases, offsets, tx)
+        assert len(want_k) == 64 if len(seqs) == 64 else len(want_k) > 128
+        ix = slacken_amd.Index(expected_records=4096, max_taxon=len(parents) - 1)
+        ix.set_taxonomy(parents)
+        ix.add_sequences(bases, offsets, tx)
+        got_k, got_t = ix.export()
+        assert np.array_equal(got_k, want_k) and np.array_equal(got_t, want_t)

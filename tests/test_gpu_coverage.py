@@ -273,3 +273,29 @@ def test_refusals(base):
     rows, _ = got_of(cov)
     assert rows and {d for _, d, _, _ in rows} == {-1} and sum(a for _, _, a, _ in rows) == sum(a for _, _, a, _ in want[0])
     cov.close()
+
+
+@pytest.mark.parametrize("distinct", [1, 2, 3, 64])
+def test_a_small_pair_map_of_few_sources(orc, monkeypatch, distinct):
+    """448 one-window sequences under 1, 2, 3 or 64 sources against an index that holds them all under one taxon, in a pair map of
+    1024 slots (SLK_COVERAGE_MAP_LOG2=10; 448 pairs do not make it grow): every wave of the fold reads 64 slots with some 28 pairs
+    under that many (source, depth) keys -- with three, lanes are left over after the two leader rounds.  The first 64 sequences are
+    one wave of the scan whose lanes all start their super-mer at step k - 1: one push brings its queue exactly 64 entries."""
+    import slacken_amd
+    k = 35
+    monkeypatch.setenv("SLK_COVERAGE_MAP_LOG2", "10")
+    rng = np.random.default_rng(90 + distinct)
+    p = orc.params()
+    parents = np.array([0, 0, 1, 2], np.int32)
+    seqs = [dna(k, rng) for _ in range(448)]
+    source = np.array([100 + i % distinct for i in range(len(seqs))], np.int32)
+    keys, taxa = orc.build_records(p, parents, *cm.pack(seqs), [3] * len(seqs))
+    assert len(keys) == len(seqs)
+    ix = slacken_amd.Index(expected_records=len(keys), max_taxon=3, device=0)
+    ix.append(keys, taxa)
+    ix.set_taxonomy(parents)
+    ix.finalize()
+    depths = np.array([-1, 0, 1, 2], np.int32)
+    want = cm.coverage(orc, p, orc.Index(1, keys, taxa), lambda t: int(depths[t]), seqs, source.tolist())
+    got = run(dict(ix=ix, depths=depths, st=ix.stream(), seqs=seqs, source=source))
+    assert got == want[:2] and len(got[0]) == distinct and sum(a for _, _, a, _ in got[0]) == len(seqs)

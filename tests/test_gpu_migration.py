@@ -366,3 +366,17 @@ def test_lifetimes_and_a_shared_classify_stream(orc):
     assert np.array_equal(t1, t2) and int(count.sum()) == matched and not steps.any()
     st.close()
     ix.close()
+
+
+@pytest.mark.parametrize("distinct", [1, 2, 3, 64])
+def test_one_wave_of_few_pairs(big, distinct):
+    """64 matched records, one wave, with 1, 2, 3 or 64 distinct (t1, t2) pairs: with three, lanes are left over after the two
+    leader rounds and go to the block's map one by one"""
+    import slacken_amd
+    sk = big["rk"][:64].copy()                                    # all of them records of taxon 77
+    st1 = (1 + np.arange(64) % distinct).astype(np.int32)
+    mig = slacken_amd.capi.MinimizerMigration(big["ix"], None, stream=big["st"])
+    mig.add(sk, st1)
+    want = check(mig, sk, st1, big["ref"], None, with_depths=False)
+    assert [(a, b) for a, b, _, _ in want] == [(t, 77) for t in range(1, distinct + 1)]
+    mig.close()

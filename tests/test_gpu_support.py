@@ -352,3 +352,42 @@ def test_a_dynamic_library(base, orc):
     sd = W["species_depth"]
     assert run(W, W["reads"], sd, ix=dyn, st=dyn.stream()) == (model.rows(sd), model.totals(sd)) and model.rows(sd)
     assert model.totals(sd)[2] < W["model"].totals(sd)[2]                                           # fewer genomes, fewer hits
+
+
+@pytest.mark.parametrize("distinct", [1, 2, 3, 64])
+def test_one_wave_of_few_taxa(orc, distinct):
+    """64 reads of exactly k bases, every one its own indexed sequence: one wave of 64 one-window chunks whose super-mers all close
+    at the end of the chunk, so one push brings the queue exactly 64 entries, and the 64 hits of the flush name 1, 2, 3 (lanes are
+    left over after the two leader rounds) or 64 taxa.  The taxa are 63 and up: with 64 of them the rows straddle the border between
+    two waves of the result kernel, and with 2 or 3 a wave of it has few holders."""
+    k = 35
+    rng = np.random.default_rng(70 + distinct)
+    p = orc.params()
+    parents = np.concatenate([[0, 0], np.ones(126, np.int32)]).astype(np.int32)
+    reads = [dna(k, rng) for _ in range(64)]
+    node = [63 + i % distinct for i in range(64)]
+    keys, taxa = orc.build_records(p, parents, *cm.pack(reads), node)
+    assert len(keys) == 64
+    depths = np.ones(128, np.int32)
+    depths[0], depths[1] = -1, 0
+    model = sm.support(orc, p, orc.Index(1, keys, taxa), lambda t: int(depths[t]), reads)
+    ix = make_index((35, 31, 7), keys, taxa, parents)
+    rows, totals = run(dict(ix=ix, st=ix.stream(), depths=depths), reads, 1)
+    assert (rows, totals) == (model.rows(1), model.totals(1))
+    assert [t for t, _, _, _ in rows] == list(range(63, 63 + distinct)) and totals == (64, 64, 64, 64)
+
+
+def test_one_lane_fills_the_queue_twice(orc):
+    """one read of one chunk (k + 510 bases) with more super-mers than the queue's 128 entries, alone in its wave: the ring's index
+    wraps, and the tail flush takes fewer than 64"""
+    k = 35
+    rng = np.random.default_rng(9)
+    p = orc.params()
+    parents = np.array([0, 0, 1, 2], np.int32)
+    read = dna(k + 510, rng)
+    keys, taxa = orc.build_records(p, parents, *cm.pack([read]), [3])
+    depths = np.array([-1, 0, 1, 2], np.int32)
+    model = sm.support(orc, p, orc.Index(1, keys, taxa), lambda t: int(depths[t]), [read])
+    assert model.totals(0)[1] > 128
+    ix = make_index((35, 31, 7), keys, taxa, parents)
+    assert run(dict(ix=ix, st=ix.stream(), depths=depths), [read], 0) == (model.rows(0), model.totals(0))

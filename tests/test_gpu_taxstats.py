@@ -313,3 +313,18 @@ def test_index_is_unchanged_and_counts_are_deterministic():
     want = np.array([r[f"c{g['thresholds'][0]}"] for r in g["reads"]])
     assert np.array_equal(after["taxon"][0], want[:, 0])
     assert np.array_equal(exported[0], exported2[0]) and np.array_equal(exported[1], exported2[1])
+
+
+@pytest.mark.parametrize("distinct", [1, 2, 3, 64])
+def test_waves_of_few_taxa(distinct):
+    """8 000 records in the smallest table that seven taxon bits allow (2 048 buckets: half full, so a wave's 128 cells hold some 64
+    records) with 1, 2, 3 or 64 distinct taxa: with three, lanes are left over after the two leader rounds of nearly every wave.
+    The taxa are 63 and up in a domain of 128 ids: with 64 of them the pairs straddle the border between the two waves of the pairs
+    kernel, with 2 the second of these waves has a single holder (id 64) and the first one other (id 63)."""
+    rng = np.random.default_rng(50 + distinct)
+    keys = distinct_keys(8000, rng)
+    taxa = (63 + np.arange(len(keys)) % distinct).astype(np.int32)
+    ix = make(keys, taxa, 127)
+    assert ix.info().buckets == 2048
+    t, c = check(ix, taxa)
+    assert t.tolist() == list(range(63, 63 + distinct)) and int(c.sum()) == len(keys)
