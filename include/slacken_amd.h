@@ -321,6 +321,67 @@ int32_t slk_classify_batch_packed(slk_index *ix, slk_stream *st, const uint32_t 
                                   uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity);
 int32_t slk_pack_bases(const uint8_t *bases, uint64_t n, uint32_t *codes, uint16_t *valid);
 
+/* ---- batches in flight: a submit call and a collect call, so that ONE caller thread (a Spark task thread behind a JNI shim has no
+ * callbacks) keeps several batches of Classifier.classify on the device at once -- the reads of batch i+1 go up and the rows of
+ * batch i-1 come down while batch i is classified -- and a wire form that carries only what holds information.
+ *
+ * slk_reads: one side (the reads, or their mates) of a batch.
+ *   the bases    exactly one of `bases` (ASCII, as slk_classify_batch; no validity arrays then) and `codes` (slk_pack_bases' words).
+ *   validity     with codes: `valid`, the dense words of slk_classify_batch_packed; or valid == NULL: every base is valid except in
+ *                the n_exc words exc_word[] (strictly ascending, each < ceil(total / 16)), whose validity bits are exc_bits[] -- the
+ *                bits of a last, partial word past the side's last base are ignored.  n_exc == 0 takes NULL for both.  `valid`
+ *                together with exceptions is SLK_E_INVALID.  slk_pack_bases_sparse makes this form.
+ *   the lengths  exactly one of `offsets` ([R + 1], as slk_classify_batch), `lengths` ([R]) and uniform_len > 0 (every read has that
+ *                many bases; nothing is sent).  The device turns lengths into offsets.
+ * A side in a compact form (lengths, uniform_len or exceptions) holds fewer than 2^32 bases and the batch fewer than 2^32 reads:
+ * SLK_E_INVALID beyond, before anything is queued or allocated.
+ *
+ * slk_pipe_create   `depth` slots (1..8), each with everything an slk_stream owns; a slot's buffers keep their size from ticket to
+ *                   ticket.  One thread at a time uses a pipe; several pipes on one finalized index may be used from several threads.
+ * slk_pipe_submit   queues the upload, the expansion of the compact forms, the classify kernels and the download of the result rows
+ *                   into memory of the pipe, and returns WITHOUT waiting for the device; *ticket names the batch.  hits: 0 = none,
+ *                   1 = the number of spans per read only, 2 = the hit lists (as slk_pipe_set_merged_hits stood at the submit).  It
+ *                   writes no result buffer of the caller's -- it takes none.  With `depth` tickets uncollected it returns SLK_E_STATE,
+ *                   changes nothing and does not wait for a slot.  A refused submit (SLK_E_INVALID, SLK_E_STATE) has queued nothing.
+ *   input lifetime  PAGEABLE input is free again when submit returns: it has been copied into pinned staging of the pipe (a batch
+ *                   larger than that staging waits for its own earlier pieces' DMA, never for a kernel).  Memory of slk_host_alloc /
+ *                   slk_host_register is read by DMA, later: it must stay UNCHANGED until slk_pipe_collect of that ticket returns.
+ * slk_pipe_collect  waits for that ticket only, classifies the batch again where slk_classify_batch would (a taxon map that
+ *                   overflowed), builds the hit lists if they were asked for, copies everything out and frees the slot.  Tickets may
+ *                   be collected in any order.  Results: those of slk_classify_batch on the same reads, thresholds and
+ *                   min_hit_groups, bit for bit (out_taxon[C*R] .. as there; out_num_distinct, out_total_kmers, out_hit_offsets and
+ *                   out_hits nullable).  A collected or unknown ticket: SLK_E_STATE.  hits_capacity too small: SLK_E_CAPACITY with
+ *                   out_hit_offsets filled -- the ticket STAYS collectable, come back with a larger buffer.  A device-side failure
+ *                   of the batch (SLK_E_HIP; SLK_E_INVALID: lengths that no longer sum to what submit saw) is reported here, and the
+ *                   slot is freed.
+ * slk_pipe_pending  the number of uncollected tickets.
+ * slk_pipe_destroy  drains what is pending and frees everything. */
+typedef struct slk_pipe slk_pipe;
+typedef struct {
+  const uint8_t *bases;
+  const uint32_t *codes;
+  const uint16_t *valid;
+  const uint32_t *exc_word;
+  const uint16_t *exc_bits;
+  uint64_t n_exc;
+  const uint64_t *offsets;
+  const uint32_t *lengths;
+  uint32_t uniform_len;
+} slk_reads;
+int32_t slk_pipe_create(slk_index *ix, int32_t depth, slk_pipe **out);
+int32_t slk_pipe_set_merged_hits(slk_pipe *p, int32_t on); /* as slk_stream_set_merged_hits, for the tickets submitted from now on */
+int32_t slk_pipe_submit(slk_pipe *p, uint64_t R, const slk_reads *reads, const slk_reads *mates /* nullable */, int32_t min_hit_groups,
+                        const double *thresholds, int32_t C, int32_t hits, uint64_t *ticket);
+int32_t slk_pipe_collect(slk_pipe *p, uint64_t ticket, int32_t *out_taxon, uint8_t *out_classified, int32_t *out_num_distinct,
+                         int32_t *out_total_kmers, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity);
+int32_t slk_pipe_pending(const slk_pipe *p, int32_t *n_pending);
+void slk_pipe_destroy(slk_pipe *p);
+/* slk_pack_bases with the validity as slk_reads takes it: the same codes[ceil(n / 16)]; word w is an exception iff some base p < n of
+ * it is invalid, and its bits are the dense word's.  More exceptions than exc_capacity: SLK_E_CAPACITY with *n_exc = the number
+ * needed (the first exc_capacity are written, the codes in full). */
+int32_t slk_pack_bases_sparse(const uint8_t *bases, uint64_t n, uint32_t *codes, uint32_t *exc_word, uint16_t *exc_bits,
+                              uint64_t exc_capacity, uint64_t *n_exc);
+
 /* ---- FASTA / FASTQ text parsed on the device: replaces FastaTextInput and FastqTextInput (S/kmers/input/FileInputs.scala:155-183,
  * 188-221) -- the records of a text as the layout the classify entry points take (bases without whitespace, offsets[R+1]) plus
  * where every record's title lies in the text.  Per byte:

@@ -39,6 +39,18 @@ object Native {
                                   minHitGroups: Int, thresholds: Array[Double], outTaxon: Array[Int], outClassified: Array[Byte],
                                   outNumDistinct: Array[Int], outTotalKmers: Array[Int], outHitOffsets: Array[Long]): Unit
   @native def packBases(text: ByteBuffer, n: Long, packed: ByteBuffer, validOffset: Long): Unit
+  /** slk_pipe: `depth` batches in flight from one task thread.  pipeSubmit queues a batch and returns its ticket without waiting
+   * for the device; pipeCollect waits for that ticket alone.  `packed` (codes from byte 0, nExc exception word indices at excOffset,
+   * their validity words at bitsOffset) and `lengths` (R uint32, or null with uniformLen > 0) are allocPinned buffers, read by DMA
+   * AFTER pipeSubmit returns: leave them alone until pipeCollect of the ticket has returned. */
+  @native def pipeCreate(h: Long, depth: Int): Long
+  @native def pipeDestroy(p: Long): Unit
+  @native def pipeSubmit(p: Long, packed: ByteBuffer, excOffset: Long, bitsOffset: Long, nExc: Long, lengths: ByteBuffer, uniformLen: Int,
+                         r: Int, minHitGroups: Int, thresholds: Array[Double], spanCounts: Boolean): Long
+  @native def pipeCollect(p: Long, ticket: Long, outTaxon: Array[Int], outClassified: Array[Byte], outNumDistinct: Array[Int],
+                          outTotalKmers: Array[Int], outHitOffsets: Array[Long]): Unit
+  /** slk_pack_bases_sparse: -> the number of exception words (IllegalStateException beyond excCapacity) */
+  @native def packBasesSparse(text: ByteBuffer, n: Long, packed: ByteBuffer, excOffset: Long, bitsOffset: Long, excCapacity: Long): Long
   /** slk_spans_batch (getSpans): outSpans holds {long key; int kmers; byte flag; byte distinct; short pad} per span */
   @native def spansBatch(h: Long, s: Long, bases: ByteBuffer, offsets: Array[Long], mateBases: ByteBuffer, mateOffsets: Array[Long],
                          r: Int, outSpanOffsets: Array[Long], outSpans: ByteBuffer, capacity: Long): Unit
@@ -158,6 +170,50 @@ final class GpuClassifier(index: KeyValueIndex, handle: => Long)(implicit spark:
           new Array[Int](r), new Array[Int](r), ho)
         batch.iterator.zipWithIndex.collect { case (f, i) if ho(i + 1) > ho(i) => (f.header, outCls(i) != 0, outTaxon(i)) }
       } ++ { Native.streamDestroy(st); Iterator.empty }
+    }
+
+  /** classifySimple with TWO batches in flight per task thread (slk_pipe): while batch i is classified, batch i + 1 is packed and
+   * goes up and the rows of batch i - 1 come down.  The reads travel in the compact form -- codes, the validity as exception words,
+   * lengths as uint32 -- out of one pinned buffer set per slot, which is reused only after its ticket has been collected. */
+  def classifyPipelined(subjects: Dataset[InputFragment], cpar: ClassifyParams, threshold: Double): Dataset[(String, Boolean, Int)] =
+    subjects.mapPartitions { frags =>
+      val depth = 2
+      val batchReads = 1 << 20
+      val pipe = Native.pipeCreate(handle, depth)
+      // one set of pinned buffers per slot, sized for the largest batch on first use (reads of up to maxLen bases)
+      final class SlotBuffers { var text: ByteBuffer = _; var packed: ByteBuffer = _; var lengths: ByteBuffer = _; var bytes = 0L }
+      val slots = Array.fill(depth)(new SlotBuffers)
+      val inFlight = scala.collection.mutable.Queue.empty[(Long, Seq[InputFragment])]
+      def collect(): Iterator[(String, Boolean, Int)] = {
+        val (ticket, batch) = inFlight.dequeue()
+        val r = batch.size
+        val outTaxon = new Array[Int](r); val outCls = new Array[Byte](r); val ho = new Array[Long](r + 1)
+        Native.pipeCollect(pipe, ticket, outTaxon, outCls, new Array[Int](r), new Array[Int](r), ho)
+        batch.iterator.zipWithIndex.collect { case (f, i) if ho(i + 1) > ho(i) => (f.header, outCls(i) != 0, outTaxon(i)) }
+      }
+      var n = 0L
+      frags.grouped(batchReads).flatMap { batch =>
+        // (the slot of batch n is free: at most depth - 1 tickets are pending here, and tickets are collected in order)
+        val done = if (inFlight.size == depth) collect() else Iterator.empty
+        val sb = slots((n % depth).toInt); n += 1
+        val total = batch.iterator.map(_.nucleotides.length.toLong).sum
+        val words = (total + 15) / 16
+        val excOffset = (words * 4 + 63) / 64 * 64
+        val bitsOffset = excOffset + (words * 4 + 63) / 64 * 64      // (room for every word to be an exception)
+        if (sb.bytes < total) {
+          sb.text = Native.allocPinned(total + 64)
+          sb.packed = Native.allocPinned(bitsOffset + words * 2 + 64).order(ByteOrder.LITTLE_ENDIAN)
+          sb.lengths = Native.allocPinned(batchReads * 4L).order(ByteOrder.LITTLE_ENDIAN)
+          sb.bytes = total
+        }
+        sb.text.clear(); batch.foreach(f => sb.text.put(f.nucleotides.getBytes("ISO-8859-1")))
+        batch.iterator.zipWithIndex.foreach { case (f, i) => sb.lengths.putInt(i * 4, f.nucleotides.length) }
+        val nExc = Native.packBasesSparse(sb.text, total, sb.packed, excOffset, bitsOffset, words)
+        val ticket = Native.pipeSubmit(pipe, sb.packed, excOffset, bitsOffset, nExc, sb.lengths, 0, batch.size, cpar.minHitGroups,
+          Array(threshold), true)
+        inFlight.enqueue((ticket, batch))
+        done
+      } ++ Iterator.continually(inFlight.nonEmpty).takeWhile(identity).flatMap(_ => collect()) ++ { Native.pipeDestroy(pipe); Iterator.empty }
     }
 
   /** Classifies every fragment on its own (exact for titles that occur once).  Batch buffers should come from Native.allocPinned

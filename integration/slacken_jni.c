@@ -157,6 +157,76 @@ JNIEXPORT void JNICALL Java_com_jnpersson_slacken_gpu_Native_packBases(JNIEnv *e
     throw_state(e);
 }
 
+/* ---- slk_pipe: two (or more) batches in flight per task thread.  A JNI shim has no callbacks, so the pipeline is a submit native and a
+ * collect native; GpuClassifier.classifyPipelined keeps `depth` batches between them.  The reads travel in the compact form: 2-bit
+ * codes, the validity as a list of exception words (packBasesSparse), and one length for all reads or an int[] of lengths -- 37.5
+ * bytes per 150-base read instead of 64.25.
+ * EVERY input buffer is a direct buffer of allocPinned: the library reads it by DMA after pipeSubmit has returned, so the caller
+ * leaves it unchanged until pipeCollect of that ticket returns (one set of buffers per slot in flight).
+ * packed: codes from byte 0, then at excOffset nExc uint32 word indices, then at bitsOffset nExc uint16 validity words; lengths:
+ * direct buffer of R uint32, or null with uniformLen > 0.  Reports-only shape as classifyBatchPacked: no mates, span counts only. */
+#define P(x) ((slk_pipe *)(intptr_t)(x))
+JNIEXPORT jlong JNICALL Java_com_jnpersson_slacken_gpu_Native_pipeCreate(JNIEnv *e, jclass c, jlong h, jint depth) {
+  (void)c;
+  slk_pipe *p = NULL;
+  if (slk_pipe_create(H(h), depth, &p) != SLK_OK) { throw_state(e); return 0; }
+  return (jlong)(intptr_t)p;
+}
+JNIEXPORT void JNICALL Java_com_jnpersson_slacken_gpu_Native_pipeDestroy(JNIEnv *e, jclass c, jlong p) { (void)e; (void)c; slk_pipe_destroy(P(p)); }
+JNIEXPORT jlong JNICALL Java_com_jnpersson_slacken_gpu_Native_pipeSubmit(JNIEnv *e, jclass c, jlong p, jobject packed, jlong excOffset,
+                                                                         jlong bitsOffset, jlong nExc, jobject lengths, jint uniformLen, jint R,
+                                                                         jint minHitGroups, jdoubleArray thresholds, jboolean spanCounts) {
+  (void)c;
+  const uint8_t *buf = (const uint8_t *)(*e)->GetDirectBufferAddress(e, packed);
+  jsize C = (*e)->GetArrayLength(e, thresholds);
+  jdouble thr[16];
+  if (C > 16) C = 16;
+  (*e)->GetDoubleArrayRegion(e, thresholds, 0, C, thr);
+  slk_reads reads = {0};
+  reads.codes = (const uint32_t *)buf;
+  reads.n_exc = (uint64_t)nExc;
+  if (nExc) {
+    reads.exc_word = (const uint32_t *)(buf + excOffset);
+    reads.exc_bits = (const uint16_t *)(buf + bitsOffset);
+  }
+  if (lengths) reads.lengths = (const uint32_t *)(*e)->GetDirectBufferAddress(e, lengths);
+  else reads.uniform_len = (uint32_t)uniformLen;
+  uint64_t ticket = 0;
+  if (slk_pipe_submit(P(p), (uint64_t)R, &reads, NULL, minHitGroups, thr, C, spanCounts ? 1 : 0, &ticket) != SLK_OK) { throw_state(e); return 0; }
+  return (jlong)ticket;
+}
+/* the results of one ticket into caller-owned arrays (copied out of the pipe's memory: the arrays need not be pinned) */
+JNIEXPORT void JNICALL Java_com_jnpersson_slacken_gpu_Native_pipeCollect(JNIEnv *e, jclass c, jlong p, jlong ticket, jintArray outTaxon,
+                                                                         jbyteArray outClassified, jintArray outNumDistinct,
+                                                                         jintArray outTotalKmers, jlongArray outHitOffsets) {
+  (void)c;
+  /* the call below blocks on the GPU: no critical sections are held across it */
+  jint *t = (*e)->GetIntArrayElements(e, outTaxon, NULL);
+  jbyte *cl = (*e)->GetByteArrayElements(e, outClassified, NULL);
+  jint *nd = (*e)->GetIntArrayElements(e, outNumDistinct, NULL);
+  jint *tk = (*e)->GetIntArrayElements(e, outTotalKmers, NULL);
+  jlong *ho = outHitOffsets ? (*e)->GetLongArrayElements(e, outHitOffsets, NULL) : NULL;
+  int32_t rc = slk_pipe_collect(P(p), (uint64_t)ticket, (int32_t *)t, (uint8_t *)cl, (int32_t *)nd, (int32_t *)tk, (uint64_t *)ho, NULL, 0);
+  if (ho) (*e)->ReleaseLongArrayElements(e, outHitOffsets, ho, 0);
+  (*e)->ReleaseIntArrayElements(e, outTotalKmers, tk, 0);
+  (*e)->ReleaseIntArrayElements(e, outNumDistinct, nd, 0);
+  (*e)->ReleaseByteArrayElements(e, outClassified, cl, 0);
+  (*e)->ReleaseIntArrayElements(e, outTaxon, t, 0);
+  if (rc != SLK_OK) throw_state(e);
+}
+/* slk_pack_bases_sparse: text (direct buffer) -> codes at byte 0 of `packed`, the exception words at excOffset and their bits at
+ * bitsOffset (room for excCapacity of each); -> the number of exceptions (more than excCapacity: IllegalStateException, grow and repeat) */
+JNIEXPORT jlong JNICALL Java_com_jnpersson_slacken_gpu_Native_packBasesSparse(JNIEnv *e, jclass c, jobject text, jlong n, jobject packed,
+                                                                              jlong excOffset, jlong bitsOffset, jlong excCapacity) {
+  (void)c;
+  uint8_t *buf = (uint8_t *)(*e)->GetDirectBufferAddress(e, packed);
+  uint64_t n_exc = 0;
+  if (slk_pack_bases_sparse((const uint8_t *)(*e)->GetDirectBufferAddress(e, text), (uint64_t)n, (uint32_t *)buf, (uint32_t *)(buf + excOffset),
+                            (uint16_t *)(buf + bitsOffset), (uint64_t)excCapacity, &n_exc) != SLK_OK)
+    throw_state(e);
+  return (jlong)n_exc;
+}
+
 /* slk_spans_batch: OrdinalSpan per fragment (KeyValueIndex.getSpans :163-173) -- here for the `distinct` flags of fragments whose title
  * repeats (GpuClassifier.regroup).  outSpans: direct buffer of slk_span {long key; int kmers; byte flag; byte distinct; short pad} */
 JNIEXPORT void JNICALL Java_com_jnpersson_slacken_gpu_Native_spansBatch(JNIEnv *e, jclass c, jlong h, jlong s, jobject bases, jlongArray offsets,

@@ -67,6 +67,11 @@ class ShardResults(C.Structure):
 
 
 EXCHANGE_AUTO, EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1, 2
+class _Reads(C.Structure):   # slk_reads: one side of a batch of slk_pipe_submit
+    _fields_ = [("bases", C.c_void_p), ("codes", C.c_void_p), ("valid", C.c_void_p), ("exc_word", C.c_void_p), ("exc_bits", C.c_void_p),
+                ("n_exc", C.c_uint64), ("offsets", C.c_void_p), ("lengths", C.c_void_p), ("uniform_len", C.c_uint32)]
+
+
 SPAN_DTYPE = np.dtype([("key", "<i8"), ("kmers", "<i4"), ("flag", "i1"), ("distinct", "u1"), ("pad", "<u2")])
 HIT_DTYPE = np.dtype([("taxon", "<i4"), ("count", "<i4")])
 
@@ -85,7 +90,9 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_coverage_destroy",
            "slk_support_create", "slk_support_add", "slk_support_result", "slk_support_totals", "slk_support_destroy",
            "slk_parse_tile_bytes", "slk_parse_device", "slk_parse_text", "slk_classify_text",
-           "slk_pair_device", "slk_parse_text_paired", "slk_classify_text_paired"]
+           "slk_pair_device", "slk_parse_text_paired", "slk_classify_text_paired",
+           "slk_pipe_create", "slk_pipe_set_merged_hits", "slk_pipe_submit", "slk_pipe_collect", "slk_pipe_pending", "slk_pipe_destroy",
+           "slk_pack_bases_sparse"]
 
 PAIR_FIELDS = ("P", "mismatch", "consumed1", "consumed2", "R1", "R2", "n_bases", "n_mate_bases")   # slk_pair_record, in order
 
@@ -227,6 +234,15 @@ def lib():
     L.slk_classify_text_paired.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.c_int32, u8p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
                                            C.POINTER(C.c_double), C.c_int32, i32p, u8p, i32p, i32p, u64p, u64p, u64p, vp, u64p, vp,
                                            C.c_uint64, C.c_uint64, u64p]
+    L.slk_pipe_create.argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    L.slk_pipe_set_merged_hits.argtypes = [vp, C.c_int32]
+    L.slk_pipe_submit.argtypes = [vp, C.c_uint64, C.POINTER(_Reads), C.POINTER(_Reads), C.c_int32, C.POINTER(C.c_double), C.c_int32, C.c_int32,
+                                  C.POINTER(C.c_uint64)]
+    L.slk_pipe_collect.argtypes = [vp, C.c_uint64, i32p, u8p, i32p, i32p, u64p, vp, C.c_uint64]
+    L.slk_pipe_pending.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.slk_pipe_destroy.argtypes = [vp]
+    L.slk_pipe_destroy.restype = None
+    L.slk_pack_bases_sparse.argtypes = [u8p, C.c_uint64, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -256,6 +272,23 @@ def pack_bases(bases, pinned=False):
     codes, valid = make(max(words, 1), np.uint32), make(max(words, 1), np.uint16)
     _check(lib().slk_pack_bases(_ptr(bases), bases.size, _ptr(codes), _ptr(valid)))
     return codes, valid
+
+
+def pack_bases_sparse(bases, pinned=False):
+    """ASCII bases -> (codes uint32 [ceil(n / 16)], exc_word uint32 [n_exc], exc_bits uint16 [n_exc]): the codes of pack_bases and
+    the validity as the list of the words that hold an invalid base (slk_pack_bases_sparse; Pipe.submit takes it)"""
+    bases = _np(bases, np.uint8)
+    words = (bases.size + 15) // 16
+    make = (lambda n, dt: pinned_array((n,), dt)) if pinned else (lambda n, dt: np.zeros(n, dt))
+    codes = make(max(words, 1), np.uint32)
+    cap, n = max(16, words // 64), C.c_uint64(0)
+    while True:
+        exc_word, exc_bits = make(cap, np.uint32), make(cap, np.uint16)
+        rc = lib().slk_pack_bases_sparse(_ptr(bases), bases.size, _ptr(codes), _ptr(exc_word), _ptr(exc_bits), cap, C.byref(n))
+        if rc != -5:   # SLK_E_CAPACITY: n says what the list needs
+            _check(rc)
+            return codes, exc_word[:n.value], exc_bits[:n.value]
+        cap = int(n.value)
 
 
 def pinned_array(shape, dtype):
@@ -716,6 +749,126 @@ class ShardSet:
         if getattr(self, "h", None):
             lib().slk_shardset_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Pipe:
+    """slk_pipe: `depth` batches in flight from one thread.  submit() queues a batch and returns its ticket at once; collect()
+    waits for that ticket alone and returns what Stream.classify_batch returns.  A side of a batch is a dict with
+      bases (ASCII)  or  codes with valid (pack_bases)  or  codes with exc_word, exc_bits (pack_bases_sparse; both may be absent)
+      and one of offsets [R + 1], lengths [R], uniform_len
+    Every array a ticket was submitted with is kept alive here until the ticket is collected (pinned arrays are read by DMA
+    after submit returns: do not change them before)."""
+
+    _DTYPES = dict(bases=np.uint8, codes=np.uint32, valid=np.uint16, exc_word=np.uint32, exc_bits=np.uint16, offsets=np.uint64,
+                   lengths=np.uint32)
+
+    def __init__(self, index, depth=2):
+        self.index = index
+        h = C.c_void_p()
+        _check(lib().slk_pipe_create(index.h, depth, C.byref(h)))
+        self.h = h
+        self._tickets = {}    # ticket -> (R, C, hits, default hits capacity, the input arrays)
+
+    def set_merged_hits(self, on=True):
+        _check(lib().slk_pipe_set_merged_hits(self.h, 1 if on else 0))
+
+    def pending(self):
+        n = C.c_int32(0)
+        _check(lib().slk_pipe_pending(self.h, C.byref(n)))
+        return int(n.value)
+
+    @classmethod
+    def _side(cls, d):
+        """-> (slk_reads, the arrays it points to, the R the side implies or None, its bases)"""
+        keep = {k: _np(d[k], dt) for k, dt in cls._DTYPES.items() if d.get(k) is not None}
+        R = keep["offsets"].size - 1 if "offsets" in keep else keep["lengths"].size if "lengths" in keep else None
+        n_exc = keep["exc_word"].size if "exc_word" in keep else 0
+        for k in keep:   # (an empty array may have no address: the call tells present from absent by the pointer)
+            if keep[k].size == 0:
+                keep[k] = np.zeros(1, cls._DTYPES[k])
+        r = _Reads()
+        for k, a in keep.items():
+            setattr(r, k, a.ctypes.data)
+        r.n_exc = int(d["n_exc"]) if "n_exc" in d else n_exc
+        r.uniform_len = int(d.get("uniform_len") or 0)
+        return r, keep, R
+
+    @staticmethod
+    def _total(keep, r, R):
+        if "offsets" in keep:
+            return int(keep["offsets"][R])
+        if "lengths" in keep:
+            return int(keep["lengths"][:R].sum(dtype=np.uint64))
+        return R * int(r.uniform_len)
+
+    def submit(self, reads, mates=None, R=None, min_hit_groups=2, thresholds=(0.0,), hits=2):
+        """hits: 0 = none, 1 = num_hits only, 2 = the hit lists.  R is needed where no array says it (uniform_len).  -> ticket"""
+        r, keep, Rr = self._side(reads)
+        m = mkeep = None
+        if mates is not None:
+            m, mkeep, Rm = self._side(mates)
+            if Rr is not None and Rm is not None and Rr != Rm:
+                raise SlackenError(-1, f"the mates describe {Rm} reads, the reads {Rr}")
+            Rr = Rr if Rr is not None else Rm
+        if R is not None and Rr is not None and int(R) != Rr:
+            raise SlackenError(-1, f"R = {R}, the arrays describe {Rr} reads")
+        R = int(R) if R is not None else Rr
+        if R is None:
+            raise ValueError("uniform_len needs R")
+        Cn = len(thresholds)
+        thr = (C.c_double * Cn)(*thresholds)
+        ticket = C.c_uint64(0)
+        _check(lib().slk_pipe_submit(self.h, R, C.byref(r), C.byref(m) if m is not None else None, min_hit_groups, thr, Cn, hits,
+                                     C.byref(ticket)))
+        cap = self._total(keep, r, R) + (self._total(mkeep, m, R) + R if m is not None else 0) + 1
+        self._tickets[ticket.value] = (R, Cn, hits, cap, (keep, mkeep))
+        return int(ticket.value)
+
+    def collect(self, ticket, hits_capacity=None, out=None):
+        """-> the dict of Stream.classify_batch (hits 2: with hit_offsets, hits, num_hits; hits 1: with num_hits).  out: optional
+        dict of preallocated result arrays, as there.  SLK_E_CAPACITY (hits_capacity too small) leaves the ticket collectable."""
+        R, Cn, hits, cap, _ = self._tickets.get(ticket, (0, 1, 0, 0, None))
+        if out is not None:
+            taxon, cls, nd, tk = out["taxon"], out["classified"], out["num_distinct"], out["total_kmers"]
+            assert taxon.shape == (Cn, R) and taxon.dtype == np.int32 and cls.shape == (Cn, R) and cls.dtype == np.uint8
+            assert all(a.flags.c_contiguous for a in (taxon, cls, nd, tk))
+        else:
+            taxon, cls = np.zeros((Cn, R), np.int32), np.zeros((Cn, R), np.uint8)
+            nd, tk = np.zeros(R, np.int32), np.zeros(R, np.int32)
+        hit_off = hit_arr = None
+        if hits:
+            hit_off = np.zeros(R + 1, np.uint64)
+        if hits == 2:
+            cap = hits_capacity if hits_capacity is not None else cap
+            hit_arr = np.zeros(max(cap, 1), HIT_DTYPE)
+        rc = lib().slk_pipe_collect(self.h, ticket, _ptr(taxon), _ptr(cls), _ptr(nd), _ptr(tk), _ptr(hit_off), _ptr(hit_arr),
+                                    cap if hits == 2 else 0)
+        if rc == -5:   # SLK_E_CAPACITY: the offsets say what the lists need
+            err = SlackenError(rc, lib().slk_last_error().decode())
+            err.hit_offsets = hit_off
+            raise err
+        self._tickets.pop(ticket, None)
+        _check(rc)
+        res = dict(taxon=taxon, classified=cls, num_distinct=nd, total_kmers=tk)
+        if hits:
+            res["num_hits"] = np.diff(hit_off.astype(np.int64)).astype(np.int32)
+        if hits == 2:
+            res["hit_offsets"] = hit_off
+            res["hits"] = hit_arr[:int(hit_off[R])]
+        return res
+
+    def close(self):
+        """slk_pipe_destroy: waits for what is pending and drops it"""
+        if getattr(self, "h", None):
+            lib().slk_pipe_destroy(self.h)
+            self.h = None
+            self._tickets.clear()
 
     def __del__(self):
         try:

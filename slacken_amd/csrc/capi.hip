@@ -90,3 +90,35 @@ int32_t slk_pack_bases(const uint8_t *bases, uint64_t n, uint32_t *codes, uint16
   });
   return SLK_OK;
 }
+
+// The same codes, the validity as the list of the words that hold an invalid base (slk_reads: exc_word / exc_bits).  Large inputs
+// are cut as above; a slice keeps its exceptions to itself until all are through, then they are written in order.
+int32_t slk_pack_bases_sparse(const uint8_t *bases, uint64_t n, uint32_t *codes, uint32_t *exc_word, uint16_t *exc_bits, uint64_t exc_capacity,
+                              uint64_t *n_exc) {
+  if (!n_exc || (n && (!bases || !codes)) || (exc_capacity && (!exc_word || !exc_bits))) return fail(SLK_E_INVALID, "null argument");
+  *n_exc = 0;
+  if ((n + 15) / 16 > (1ULL << 32)) return fail(SLK_E_INVALID, "exception words are 32-bit indices: at most 2^36 bases per call");
+  const uint64_t SLICE = (uint64_t)1 << 22;
+  const uint64_t parts = (n + SLICE - 1) / SLICE;
+  uint64_t need = 0;
+  if (parts <= 1) {
+    need = pack_bases_sparse(bases, n, 0, codes, exc_word, exc_bits, 0, exc_capacity);
+  } else {
+    std::vector<std::vector<uint32_t>> words(parts);
+    std::vector<std::vector<uint16_t>> bits(parts);
+    host_pool().parallel_for(parts, [&](size_t i) {
+      const uint64_t a = i * SLICE, b = std::min(n, a + SLICE);
+      const uint64_t most = (b - a + 15) / 16;   // (room for every word while the slice is packed, cut back to what it listed)
+      words[i].resize(most); bits[i].resize(most);
+      const uint64_t cnt = pack_bases_sparse(bases + a, b - a, a / 16, codes + a / 16, words[i].data(), bits[i].data(), 0, most);
+      words[i].resize(cnt); bits[i].resize(cnt);
+      words[i].shrink_to_fit(); bits[i].shrink_to_fit();
+    });
+    for (uint64_t i = 0; i < parts; i++)
+      for (size_t j = 0; j < words[i].size(); j++, need++)
+        if (need < exc_capacity) { exc_word[need] = words[i][j]; exc_bits[need] = bits[i][j]; }
+  }
+  *n_exc = need;
+  if (need > exc_capacity) return fail(SLK_E_CAPACITY, "%llu exception words, capacity is %llu", (unsigned long long)need, (unsigned long long)exc_capacity);
+  return SLK_OK;
+}

@@ -210,7 +210,7 @@ static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want
   return p;
 }
 
-static int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call) {
+int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call) {
   ClassifyCall c = call;
   if (c.out.stride == 0) c.out.stride = c.in.R;
   const Reads &in = c.in;
@@ -587,7 +587,7 @@ int32_t slk_stream_last_stage_ms(slk_stream *st, float out_ms[3]) {
   return SLK_OK;
 }
 
-static int32_t validate_reads(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R) {
+int32_t slk::validate_reads(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R) {
   // (4 M reads are 4 M compares per array: split over the copy threads)
   const uint64_t PART = 1 << 18;
   const uint64_t parts = (R + PART - 1) / PART;
@@ -720,7 +720,7 @@ struct ReadSource {
 };
 
 // bases [p0, p1) of one mate from the caller's memory to dst (+ the device-side unpack on `run` for packed reads), ordered on `up`
-static int32_t upload_range(slk_stream *st, Staging *g, hipStream_t up, hipStream_t run, hipEvent_t ev, bool packed, const uint8_t *bases,
+int32_t slk::upload_range(slk_stream *st, Staging *g, hipStream_t up, hipStream_t run, hipEvent_t ev, bool packed, const uint8_t *bases,
                             const uint32_t *codes, const uint16_t *valid, DevBuf &d_codes, DevBuf &d_valid, uint8_t *dst, uint64_t p0, uint64_t p1) {
   if (p1 <= p0) return SLK_OK;
   if (!packed) return copy_in(g, up, dst + p0, bases + p0, p1 - p0);
@@ -758,7 +758,7 @@ static ClassifyCall sub_call(const ClassifyCall &whole, uint64_t r0, uint64_t r1
 static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // the stream's buffers at their sizes for a call of R fragments: result rows, reads, and the packed reads as they arrive
-static int32_t size_host_buffers(slk_stream *st, uint64_t R, int32_t C, uint64_t total, uint64_t mate_total, bool paired, bool pk) {
+int32_t slk::size_host_buffers(slk_stream *st, uint64_t R, int32_t C, uint64_t total, uint64_t mate_total, bool paired, bool pk) {
   const int32_t rc = ensure_outputs(st, R, C);
   if (rc) return rc;
   // (packed reads are unpacked in whole words of 16 bases: the ASCII buffers hold the last word in full)
@@ -855,7 +855,7 @@ static int32_t upload_whole(slk_stream *st, const ReadSource &src, const uint64_
 
 // The hit lists of a batch whose kernels are through: their offsets, then (out_hits given) the lists themselves, as the spans lie or
 // merged (slk_stream_set_merged_hits).  th (call timing only): when the offsets, the gather and the download were through.
-static int32_t assemble_hits(slk_stream *st, const Reads &in, bool want_hits, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity,
+int32_t slk::assemble_hits(slk_stream *st, const Reads &in, bool want_hits, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity,
                              bool call_timing, double th[3]) {
   const uint64_t R = in.R;
   const bool merged = st->merged_hits && want_hits;

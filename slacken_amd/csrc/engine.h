@@ -513,5 +513,14 @@ void launch_gather_hits(const uint64_t *offsets, const uint64_t *mate_offsets, u
                         const int32_t *span_taxon, const uint64_t *out_offsets, void *out, hipStream_t s);
 // words [w0, w1) of a packed read stream (host/pack.hpp) -> out[16 w0 .. 16 w1): "ACGT" by code, 'N' where the validity bit is clear
 void launch_unpack_bases(const uint32_t *codes, const uint16_t *valid, uint64_t w0, uint64_t w1, uint8_t *out, hipStream_t s);
+// readform.hip: the compact forms of slk_pipe_submit.  lengths[n] (n >= 1) -> out[n + 1], their exclusive prefix sums, clamped to
+// `expect` (the host's sum); a sum that differs raises READFORM_STATUS_BIT in *status.  tmp holds n / READFORM_TILE + 2 words.
+constexpr int READFORM_TILE = 1024;        // lengths per block of the count and the scatter pass
+constexpr int READFORM_STATUS_BIT = 4;     // (bits 1 and 2 of a stream's status word are the classify kernels': classify.hip, check_status)
+void launch_lengths_to_offsets(const uint32_t *lengths, uint64_t n, uint64_t *out, uint64_t *tmp, uint64_t expect, int32_t *status, hipStream_t s);
+void launch_uniform_offsets(uint32_t len, uint64_t n, uint64_t *out, hipStream_t s);   // out[r] = r * len, r = 0 .. n
+// codes[nwords] -> out[16 nwords) with every base valid, then the words exc_word[n_exc) again with the validity bits exc_bits[n_exc)
+void launch_unpack_sparse(const uint32_t *codes, uint64_t nwords, const uint32_t *exc_word, const uint16_t *exc_bits, uint64_t n_exc, uint8_t *out,
+                          hipStream_t s);
 
 }  // namespace slk

@@ -471,6 +471,14 @@ Thresholds thresholds_of(const double *v, int32_t C);
 int32_t ensure_outputs(slk_stream *st, uint64_t R, int32_t C);   // the stream's result rows (out_taxon .. out_nh) for R fragments
 struct HostRows { int32_t *taxon; uint8_t *classified; int32_t *nd, *tk; };   // a host call's results in the caller's memory (nullable from nd on)
 int32_t download_rows(slk_stream *st, const HostRows &out, uint64_t R, int32_t C);   // complete on return
+// the pieces of the host batch entry that pipe.hip queues per slot (classify.hip)
+int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call);   // the kernels of a batch and the status word's copy, queued on st->s
+int32_t validate_reads(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R);
+int32_t size_host_buffers(slk_stream *st, uint64_t R, int32_t C, uint64_t total, uint64_t mate_total, bool paired, bool pk);
+int32_t upload_range(slk_stream *st, Staging *g, hipStream_t up, hipStream_t run, hipEvent_t ev, bool packed, const uint8_t *bases,
+                     const uint32_t *codes, const uint16_t *valid, DevBuf &d_codes, DevBuf &d_valid, uint8_t *dst, uint64_t p0, uint64_t p1);
+int32_t assemble_hits(slk_stream *st, const Reads &in, bool want_hits, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity,
+                      bool call_timing, double th[3]);
 // textparse.hip: FASTA / FASTQ text parsed on the device (used by classify.hip: slk_classify_text)
 int32_t check_parse_args(uint64_t n, int32_t format);
 int32_t parse_uploaded(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, bool final, uint64_t bases_capacity,

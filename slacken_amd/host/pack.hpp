@@ -74,4 +74,28 @@ inline void pack_bases(const uint8_t *b, uint64_t n, uint32_t *codes, uint16_t *
   pack_bases_scalar(b, n, codes, valid);
 }
 
+// The same codes with the validity as a list of exceptions (slk_pack_bases_sparse): word w (counted from word0, which the slice b
+// starts at) is listed iff one of its bases is invalid, with the dense word's bits; the words come out ascending.  At most `cap`
+// entries are written, from entry `at` on; returns at + the exceptions of this slice, written or not.  The codes are always whole.
+inline uint64_t pack_bases_sparse(const uint8_t *b, uint64_t n, uint64_t word0, uint32_t *codes, uint32_t *exc_word, uint16_t *exc_bits,
+                                  uint64_t at, uint64_t cap) {
+  constexpr uint64_t STEP = 2048;   // words per round: the dense validity of a round stays in a buffer on the stack
+  uint16_t valid[STEP];
+  const uint64_t words = (n + 15) / 16;
+  for (uint64_t w0 = 0; w0 < words; w0 += STEP) {
+    const uint64_t w1 = w0 + STEP < words ? w0 + STEP : words;
+    const uint64_t p0 = w0 * 16, p1 = w1 * 16 < n ? w1 * 16 : n;
+    pack_bases(b + p0, p1 - p0, codes + w0, valid);
+    for (uint64_t w = w0; w < w1; w++) {
+      const uint64_t m = n - w * 16 < 16 ? n - w * 16 : 16;   // bases of this word
+      const uint16_t v = valid[w - w0];
+      if (v != (uint16_t)((1u << m) - 1)) {
+        if (at < cap) { exc_word[at] = (uint32_t)(word0 + w); exc_bits[at] = v; }
+        at++;
+      }
+    }
+  }
+  return at;
+}
+
 }  // namespace slk
