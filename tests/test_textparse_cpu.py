@@ -36,6 +36,24 @@ def test_symbols_declared_exported_and_bound():
     assert hasattr(capi.Stream, "parse_text") and hasattr(capi.Stream, "classify_text")
 
 
+def test_constants_the_scale_tests_are_sized_by():
+    """tests/test_gpu_textparse_scale.py places its texts right below, on and above the parser's scan block, grid and line tile and the
+    command line's default chunk: whoever retunes one of these moves the ladder of that file along with it."""
+    source = open(os.path.join(ROOT, "slacken_amd", "csrc", "textparse.hip")).read()
+    revisit = "revisit SB, G, LB and the sizes of tests/test_gpu_textparse_scale.py"
+    for name, value in (("TP_SCAN_BLOCK", 1024), ("TP_MAX_GRID", 2048), ("TP_BLOCK", 256), ("TP_LANE_BYTES", 16)):
+        m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*(\d+)\s*;" % name, source)
+        assert m, f"{name} is no longer a plain constant of textparse.hip: {revisit}"
+        assert int(m.group(1)) == value, f"{name} is {m.group(1)}, the scale tests assume {value}: {revisit}"
+    assert re.search(r"constexpr\s+uint32_t\s+TP_TILE\s*=\s*TP_BLOCK\s*\*\s*TP_LANE_BYTES\s*;", source), f"TP_TILE: {revisit}"
+    assert capi.parse_tile_bytes() == 256 * 16, revisit
+    seqio = open(os.path.join(ROOT, "slacken_amd", "host", "seqio.hpp")).read()
+    body = re.search(r"inline\s+size_t\s+io_chunk_bytes\s*\(\s*\)\s*\{(.*?)\n\}", seqio, re.S)
+    assert body, f"io_chunk_bytes() is gone from host/seqio.hpp: {revisit}"
+    assert re.search(r":\s*\(size_t\)\s*8\s*<<\s*20\s*;", body.group(1)), f"the default chunk is no longer 8 << 20 bytes: {revisit}"
+    assert 2048 * capi.parse_tile_bytes() == 8 << 20   # the default chunk is exactly one grid of tiles: any carry makes the blocks stride
+
+
 def _library_stub(tmp_path, m=31, k=35):
     loc = str(tmp_path / "lib")
     with open(loc + ".properties", "w") as f:
