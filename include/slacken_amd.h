@@ -780,6 +780,47 @@ int32_t slk_support_result(slk_support *s, uint64_t *n_taxa, int32_t *taxa, uint
 int32_t slk_support_totals(slk_support *s, uint64_t *sequences, uint64_t *supermers, uint64_t *matched, uint64_t *kept);
 void slk_support_destroy(slk_support *s);
 
+/* ---- low-complexity masking of genomes (mask.hip): replaces the `k2mask -r x` that the reference's library preparation runs over
+ * every .fna before a library is built (scripts/k2/mask_low_complexity.sh, called from download_genomic_library.sh).  The function
+ * is the symmetric DUST of Morgulis et al. 2006, pinned to the published definition in integers (equality with
+ * k2mask's own output is unpinned):
+ *   letters     A C G T U in either case are valid, U reads as T; every maximal run of valid letters inside one sequence is masked
+ *               on its own -- a run never crosses an invalid letter or a sequence border.
+ *   intervals   a run of n letters has the triplets t_0 .. t_{n-3} (6-bit values of three letters).  An interval [a, b] of
+ *               l = b - a + 1 triplets, 2 <= l <= window - 2, has S = sum over the triplet values v of c_v (c_v - 1) / 2, c_v the
+ *               occurrences of v in it.  It is good iff 10 * S > threshold * (l - 1), and perfect iff it is good and no sub-interval
+ *               of l' >= 2 triplets scores strictly higher: S' * (l - 1) <= S * (l' - 1) for all of them.  No floating point.
+ *   masked      letters a .. b + 2 of the run, for every perfect interval.  A masked letter becomes `replacement`, or its lower-case
+ *               form when replacement == 0 (k2mask's default); every other byte stays as it was.
+ *   cfg         NULL, or window 0 / threshold 0: window 64, threshold 20 (in tenths, as k2mask -T).  window outside 8..64 or
+ *               threshold outside 1..255 is SLK_E_INVALID and nothing is touched.
+ * The layout is the one slk_index_add_sequences takes: sequence i is bases[offsets[i] .. offsets[i+1]), no whitespace; offsets
+ * non-decreasing from offsets[0] = 0.  The masked count is the number of letters CHANGED (a lower-case letter masked with replacement 0
+ * stays as it is and is not counted).  The stream's index is only the stream's owner here: it need hold no record and no taxonomy.
+ *   slk_mask_device     in place on the stream's device: d_bases, d_offsets (n_sequences + 1 entries) and d_masked (one uint64) are
+ *                       device pointers.  The kernels run asynchronously on st; the call itself first waits for what st holds, because
+ *                       it reads the number of letters from d_offsets[n_sequences] to size its scratch -- two bits per letter, the
+ *                       stream's, no other allocation.
+ *   slk_mask_sequences  from and to host memory, synchronous.  The letters are staged in batches of SLK_MASK_BATCH_BASES (environment;
+ *                       default 2^28) with a halo of window - 1 letters on either side, so a sequence longer than a batch is cut and
+ *                       the result does not depend on the batch size.
+ *   slk_index_add_sequences_masked  slk_index_add_sequences of the letters masked first (`build --mask`): uploaded once to the
+ *                       stream's staging, masked where they lie and scanned where they lie (slk_index_add_sequences_device).  The
+ *                       caller's letters are not touched; st must be a stream of ix.  Synchronous.
+ *   slk_mask_tile_bases the interval starts one workgroup takes at a time (tests place borders on its multiples). */
+typedef struct {
+  uint32_t window;      /* 0: 64 */
+  uint32_t threshold;   /* 0: 20 */
+  uint8_t replacement;  /* 0: lower-case */
+} slk_mask_config;
+uint32_t slk_mask_tile_bases(void);
+int32_t slk_mask_device(slk_stream *st, uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_sequences, const slk_mask_config *cfg,
+                        uint64_t *d_masked);
+int32_t slk_mask_sequences(slk_stream *st, uint8_t *bases, const uint64_t *offsets, uint64_t n_sequences, const slk_mask_config *cfg,
+                           uint64_t *out_masked);
+int32_t slk_index_add_sequences_masked(slk_index *ix, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const int32_t *taxa,
+                                       uint64_t n_sequences, const slk_mask_config *cfg /* nullable */, uint64_t *out_masked);
+
 #ifdef __cplusplus
 }
 #endif

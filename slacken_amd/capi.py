@@ -92,7 +92,8 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_parse_tile_bytes", "slk_parse_device", "slk_parse_text", "slk_classify_text",
            "slk_pair_device", "slk_parse_text_paired", "slk_classify_text_paired",
            "slk_pipe_create", "slk_pipe_set_merged_hits", "slk_pipe_submit", "slk_pipe_collect", "slk_pipe_pending", "slk_pipe_destroy",
-           "slk_pack_bases_sparse"]
+           "slk_pack_bases_sparse",
+           "slk_mask_tile_bases", "slk_mask_device", "slk_mask_sequences", "slk_index_add_sequences_masked"]
 
 PAIR_FIELDS = ("P", "mismatch", "consumed1", "consumed2", "R1", "R2", "n_bases", "n_mate_bases")   # slk_pair_record, in order
 
@@ -106,6 +107,15 @@ def _format(fmt):
         return {"fasta": FORMAT_FASTA, "fa": FORMAT_FASTA, "fastq": FORMAT_FASTQ, "fq": FORMAT_FASTQ}[str(fmt).lower()]
     except KeyError:
         raise ValueError(f"format {fmt!r}: 'fasta' or 'fastq'") from None
+
+
+class MaskConfig(C.Structure):   # slk_mask_config
+    _fields_ = [("window", C.c_uint32), ("threshold", C.c_uint32), ("replacement", C.c_uint8)]
+
+
+def mask_tile_bases():
+    """The interval starts one workgroup of the masker takes at a time (slk_mask_tile_bases)"""
+    return int(lib().slk_mask_tile_bases())
 
 
 def parse_tile_bytes():
@@ -243,6 +253,11 @@ def lib():
     L.slk_pipe_destroy.argtypes = [vp]
     L.slk_pipe_destroy.restype = None
     L.slk_pack_bases_sparse.argtypes = [u8p, C.c_uint64, vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.slk_mask_tile_bases.argtypes = []
+    L.slk_mask_tile_bases.restype = C.c_uint32
+    L.slk_mask_device.argtypes = [vp, u8p, u64p, C.c_uint64, C.POINTER(MaskConfig), u64p]
+    L.slk_mask_sequences.argtypes = [vp, u8p, u64p, C.c_uint64, C.POINTER(MaskConfig), C.POINTER(C.c_uint64)]
+    L.slk_index_add_sequences_masked.argtypes = [vp, vp, u8p, u64p, i32p, C.c_uint64, C.POINTER(MaskConfig), C.POINTER(C.c_uint64)]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -918,6 +933,15 @@ class Stream:
         n = C.c_uint64(0)
         _check(lib().slk_stream_last_deferred(self.h, C.byref(n)))
         return int(n.value)
+
+    def mask_sequences(self, bases, offsets, window=64, threshold=20, replacement=ord("x")):
+        """Low-complexity masking (symmetric DUST; slk_mask_sequences) of sequences in the layout of add_sequences
+        -> (masked copy of bases, letters changed).  replacement 0: lower case."""
+        bases, offsets = _np(bases, np.uint8).copy(), _np(offsets, np.uint64)
+        cfg = MaskConfig(window, threshold, replacement)
+        masked = C.c_uint64(0)
+        _check(lib().slk_mask_sequences(self.h, _ptr(bases), _ptr(offsets), offsets.size - 1, C.byref(cfg), C.byref(masked)))
+        return bases, int(masked.value)
 
     def spans_batch(self, bases, offsets, mate_bases=None, mate_offsets=None, capacity=None):
         """-> (span_offsets u64[R+1], spans structured array SPAN_DTYPE)"""

@@ -296,6 +296,7 @@ struct slk_stream {
   Event ev_unpack;
   DevBuf parse_text, parse_scratch, parse_title_pos, parse_title_len, parse_counts;   // textparse.hip: the raw text, the passes' scratch, what comes back beside bases / offsets
   DevBuf parse_text2, parse_title_pos2, parse_title_len2, parse_pair;   // paired text: the mates' text and titles (their bases / offsets are mate_bases / mate_offsets), the pair record
+  DevBuf mask_scratch, mask_count;         // mask.hip: the two bitmaps (sequence starts, masked letters), the host entries' counter
   Stream s2;                               // the segment pass and the wave pass run here, beside the long-lane pass on s
   Event ev_fork, ev_join;
   DevPtr<int32_t> d_status;        // device error bits of the fused kernels

@@ -10,6 +10,7 @@
 
 #include "classify_stream.hpp"
 #include "coverage.hpp"
+#include "mask.hpp"
 #include "migration.hpp"
 #include "repeated_titles.hpp"
 #include "support.hpp"
@@ -941,7 +942,7 @@ static void export_to_writer(const slk_index *ix, LibraryWriter &w, int buckets,
 // ---- build (Slacken.scala:123-171): a library from the genomes of LIBRARY_DIR and the labels of LIBRARY_DIR/seqid2taxid.map ----
 static const char *BUILD_USAGE =
     "usage: [--partitions N] build -i INDEX -t TAXONOMY_DIR -l LIBRARY_DIR [-k 35] [-m 31] [-s|--spaces 7] [--check] [--format parquet|slkrec] "
-    "[--expected-records N] [--devices D]";
+    "[--expected-records N] [--mask] [--devices D]";
 static int g_partitions = 200;          // --partitions, the reference's global option: `buckets` of a library that `build` writes
 constexpr int BUILD_MAX_WINDOW = 28;    // m-mers per window the library builder takes (slk_index_add_sequences)
 
@@ -1017,7 +1018,7 @@ static int cmd_build(int argc, char **argv) {
   const char *why_one = "the library's table must fit one GPU";
   std::string index, taxonomy, library, ordering = "xor";
   int k = 35, m = 31, spaces = 7;
-  bool check = false;
+  bool check = false, mask = false;
   uint64_t expected = 0;
   std::vector<int> devices{0};
   LibraryWriter::Format format = LibraryWriter::AUTO;
@@ -1030,6 +1031,7 @@ static int cmd_build(int argc, char **argv) {
     else if (a == "-s" || a == "--spaces") spaces = std::stoi(a.next());
     else if (a == "--ordering") ordering = a.next();
     else if (a == "--check") check = true;
+    else if (a == "--mask") mask = true;
     else if (a == "--format") format = LibraryWriter::parse_format(a.next());
     else if (a == "--expected-records") expected = std::stoull(a.next());
     else if (a == "--devices") devices = parse_single_device(a.next(), "build", why_one);
@@ -1084,6 +1086,11 @@ static int cmd_build(int argc, char **argv) {
     void clear() { bases.clear(); offsets.assign(1, 0); taxa.clear(); }
   } batch[2];
   int fill = 0;
+  // --mask: every batch is uploaded once, masked where it lies with the defaults of `mask` (window 64, threshold 20) and scanned where
+  // it lies; the files are not touched
+  slk_stream *mask_st = nullptr;
+  std::atomic<uint64_t> n_masked{0};
+  if (mask) SLK_CALL(slk_stream_create(dev.ix, &mask_st));
   uint64_t n_seq = 0, n_bases = 0, n_batches = 0;
   double t_add = 0, t_wait = 0;
   std::future<std::pair<int32_t, std::string>> adding;
@@ -1099,9 +1106,13 @@ static int cmd_build(int argc, char **argv) {
     if (b.taxa.empty()) return;
     wait_for_add();   // (the other buffer is free from here on)
     n_batches++;
-    adding = std::async(std::launch::async, [&dev, &b, &t_add] {
+    adding = std::async(std::launch::async, [&dev, &b, &t_add, mask_st, &n_masked] {
       const double t0 = wall_seconds();
-      const int32_t rc = slk_index_add_sequences(dev.ix, b.bases.data(), b.offsets.data(), b.taxa.data(), b.taxa.size());
+      uint64_t masked = 0;
+      const slk_mask_config mask_cfg{64, 20, (uint8_t)'x'};
+      const int32_t rc = mask_st ? slk_index_add_sequences_masked(dev.ix, mask_st, b.bases.data(), b.offsets.data(), b.taxa.data(), b.taxa.size(), &mask_cfg, &masked)
+                                 : slk_index_add_sequences(dev.ix, b.bases.data(), b.offsets.data(), b.taxa.data(), b.taxa.size());
+      n_masked += masked;
       t_add += wall_seconds() - t0;   // (one add at a time: nobody else writes this)
       return std::make_pair(rc, std::string(rc == SLK_OK ? "" : slk_last_error()));
     });
@@ -1121,6 +1132,7 @@ static int cmd_build(int argc, char **argv) {
     });
     submit();
     wait_for_add();
+    if (mask_st) slk_stream_destroy(mask_st);
     SLK_CALL(slk_index_finalize(dev.ix));
   }
   const double t_walk = wall_seconds() - t_walk0;
@@ -1140,6 +1152,7 @@ static int cmd_build(int argc, char **argv) {
     wr.finish();
   }
   const double t_write = wall_seconds() - t_write0;
+  if (mask) std::cerr << "build: --mask: " << n_masked.load() << " low-complexity letters masked on the device" << std::endl;
   std::cerr << "build: " << n_seq << " sequences, " << n_bases << " bases in " << n_batches << " batches, " << info.records << " records (table grown "
             << info.grown << " times); read and parse " << t_walk - t_wait << " s beside add_sequences " << t_add << " s (waited for it " << t_wait
             << " s); export " << et.export_s << " s in " << et.pieces << " pieces beside the writer (waited for it " << et.write_wait_s << " s), "
@@ -1148,6 +1161,90 @@ static int cmd_build(int argc, char **argv) {
   std::cout << index_stats_text(tax, device_taxon_counts(dev.ix), m) << input_stats_text(label_file, all_labels, tax);
   std::cout.flush();
   return 0;
+}
+
+// ---- mask: low-complexity masking of genome files before `build` (scripts/k2/mask_low_complexity.sh of the reference, which runs
+// `k2mask -r x` over every .fna) ----
+static const char *MASK_USAGE =
+    "usage: mask [-l LIBRARY_DIR | FILES...] [--window 64] [--threshold 20] [--replace x | --soft] [--host] [--devices D]";
+
+static int cmd_mask(int argc, char **argv) {
+  const char *why_one = "masking runs on one GPU";
+  std::vector<std::string> targets;
+  slk_mask_config cfg{64, 20, (uint8_t)'x'};
+  bool host = false;
+  std::vector<int> devices{0};
+  for (Args a(argc, argv); a.take();) {
+    if (a == "-l" || a == "--library") targets.push_back(a.next());
+    else if (a == "--window") cfg.window = (uint32_t)std::stoul(a.next());
+    else if (a == "--threshold") cfg.threshold = (uint32_t)std::stoul(a.next());
+    else if (a == "--replace") {
+      const std::string v = a.next();
+      if (v.size() != 1 || mask_code((uint8_t)v[0]) <= 3 || v[0] == '\n' || v[0] == '\r' || v[0] == '>')
+        die("--replace takes one character that is no nucleotide letter\n" + std::string(MASK_USAGE));
+      cfg.replacement = (uint8_t)v[0];
+    }
+    else if (a == "--soft") cfg.replacement = 0;
+    else if (a == "--host") host = true;
+    else if (a == "--devices") devices = parse_device_list(a.next());   // (one device: the first of the list)
+    else if (a == "--shard-table") refuse_shard_table("mask", why_one, MASK_USAGE);
+    else if (a.opt.size() > 1 && a.opt[0] == '-') die("unknown option " + a.opt + "\n" + MASK_USAGE);
+    else targets.push_back(a.opt);
+  }
+  if (targets.empty()) die(MASK_USAGE);
+  if (!mask_config_ok(cfg)) die("--window takes 8..64 and --threshold 1..255 (tenths, as k2mask -T)\n" + std::string(MASK_USAGE));
+  // a directory: every *.fna below it; a file: itself
+  std::vector<std::string> files;
+  for (auto &t : targets) {
+    if (fs::is_directory(t)) {
+      std::vector<std::string> fna;
+      for (auto &e : fs::recursive_directory_iterator(t))
+        if (e.is_regular_file() && ends_with(e.path().string(), ".fna")) fna.push_back(e.path().string());
+      std::sort(fna.begin(), fna.end());
+      files.insert(files.end(), fna.begin(), fna.end());
+    } else if (fs::is_regular_file(t)) {
+      files.push_back(t);
+    } else {
+      die("Target " + t + " must be directory or regular file, aborting masking");
+    }
+  }
+  slk_index *ix = nullptr;
+  slk_stream *st = nullptr;
+  if (!host) {
+    const slk_params sp{35, 31, 7, 1, SLK_DEFAULT_TOGGLE_MASK, 1, 0};   // (a stream belongs to an index: an empty one of the default shape)
+    const slk_table_config tc{1024, 0, 0.0f};
+    SLK_CALL(slk_index_create(&sp, &tc, devices[0], &ix));
+    SLK_CALL(slk_stream_create(ix, &st));
+  }
+  // pieces of whole records of about SLK_MASK_BATCH_BASES bytes of text (a longer record is a piece of its own): the next piece is read
+  // while the last one is masked.  Host memory: two pieces.
+  const long env_batch = getenv("SLK_MASK_BATCH_BASES") ? atol(getenv("SLK_MASK_BATCH_BASES")) : 0;
+  const size_t piece_bytes = env_batch > 0 ? (size_t)env_batch : (size_t)1 << 28;
+  const size_t threads = host_threads();
+  MaskTotals totals;
+  uint64_t skipped = 0, done = 0;
+  const double t0 = wall_seconds();
+  int status = 0;
+  for (auto &f : files) {
+    if (fs::exists(f + ".masked")) { skipped++; continue; }
+    std::string error;
+    const bool ok = mask_file(f, piece_bytes, [&](uint8_t *bases, const uint64_t *offsets, uint64_t n) -> uint64_t {
+      if (host) return mask_sequences_host(bases, offsets, n, cfg, threads);
+      uint64_t masked = 0;
+      if (slk_mask_sequences(st, bases, offsets, n, &cfg, &masked) != SLK_OK) {
+        remove((f + ".tmp").c_str());   // (the file itself is as it was)
+        die(std::string("slk_mask_sequences: ") + slk_last_error());
+      }
+      return masked;
+    }, &totals, &error);
+    if (!ok) { std::cerr << "slacken-amd: mask: " << error << std::endl; status = 2; break; }
+    done++;
+  }
+  if (st) slk_stream_destroy(st);
+  if (ix) slk_index_destroy(ix);
+  std::cout << "mask: " << done << " files, " << totals.letters << " letters read, " << totals.masked << " letters masked, " << skipped
+            << " files skipped (already masked), " << wall_seconds() - t0 << " s" << (host ? " on the host" : "") << std::endl;
+  return status;
 }
 
 // ---- coverage: the genome coverage of IndexStatistics (S/slacken/IndexStatistics.scala:38-52, 86-111), behind a command of its own.
@@ -1306,11 +1403,22 @@ static const char *HELP =
     "  _sS -- .properties, _taxonomy and the records as bucketed Parquet (as .slkrec with --format slkrec or without Arrow) -- followed\n"
     "  by `Stats for <location>` and the two lines `stats` prints\n"
     "  slacken-amd [--partitions N] build -i INDEX -t TAXONOMY_DIR -l LIBRARY_DIR [-k 35] [-m 31] [-s|--spaces 7] [--check]\n"
-    "  [--format parquet|slkrec] [--expected-records N] [--devices D] (Slacken.scala:123-171): a library from the genomes of\n"
+    "  [--format parquet|slkrec] [--expected-records N] [--mask] [--devices D] (Slacken.scala:123-171): a library from the genomes of\n"
     "  LIBRARY_DIR/library/**/*.fna labelled in LIBRARY_DIR/seqid2taxid.map -- minimizers found and merged by LCA on the GPU, the table\n"
     "  exported piece by piece, grouped by Spark's bucket, into --partitions (200) Parquet files (or INDEX.slkrec), with\n"
     "  INDEX.properties and a copy of TAXONOMY_DIR as INDEX_taxonomy -- followed by the two lines `stats` prints and the label file's\n"
-    "  statistics.  --check only reports the sequences without a minimizer (host only, nothing is written)\n"
+    "  statistics.  --check only reports the sequences without a minimizer (host only, nothing is written).  --mask: every batch of\n"
+    "  genomes is masked on the GPU as `mask` would with its defaults (window 64, threshold 20, letters replaced by x) before it is\n"
+    "  scanned, so low-complexity sequence yields no minimizers; the files are not touched (--check ignores it)\n"
+    "  slacken-amd mask [-l LIBRARY_DIR | FILES...] [--window 64] [--threshold 20] [--replace x | --soft] [--host] [--devices D]\n"
+    "  (scripts/k2/mask_low_complexity.sh, which runs `k2mask -r x` before a library is built): low-complexity masking of genome files\n"
+    "  on the GPU -- symmetric DUST (Morgulis et al. 2006) with a window of 8..64 letters and a threshold of 1..255 tenths, as k2mask\n"
+    "  -W / -T.  Of a directory every *.fna below it is taken; a file with FILE.masked beside it is skipped; otherwise the masked text\n"
+    "  goes to FILE.tmp, which is renamed over FILE, and FILE.masked is created.  Masked letters become x (--replace C: the character\n"
+    "  C; --soft: their lower-case form).  Unlike k2mask, which re-wraps lines, the output differs from the input ONLY in the masked\n"
+    "  letters: header lines, line breaks and line lengths stay byte for byte (a .fai index made beforehand stays valid); line breaks\n"
+    "  inside a sequence do not end a run; every record is masked.  Equality with k2mask's own output is not pinned.  --host: the same\n"
+    "  function on the CPU (no GPU is opened).  One device: the first of --devices.  Prints letters read, letters masked, files skipped\n"
     "  slacken-amd coverage -i INDEX -l|--library LIBRARY_DIR -o OUTPUT [--devices D] (IndexStatistics.scala:38-52, 86-111; the reference's\n"
     "  `stats --library`, `inspect --library` and `classify2 --index-reports` reach this arithmetic, here those flags stay refused): every\n"
     "  genome of LIBRARY_DIR labelled in LIBRARY_DIR/seqid2taxid.map is scanned on the GPU and every super-mer's minimizer looked up in\n"
@@ -1336,7 +1444,8 @@ static const char *HELP =
     "             SLK_GZ_THREADS (threads inflating one gzip input file, default min(16, cores / files read side by side); 0: zlib),\n"
     "             SLK_CLASSIFY_THREADS (threads classifying batches, each with its own stream, default 2),\n"
     "             SLK_HOST_TIMING (report where the wall clock of the classify loop went),\n"
-    "             SLK_BUILD_BATCH_BASES (bases per batch of `build` and `coverage`, default 2^30), SLK_COVERAGE_MAX_PAIRS ((minimizer, source\n"
+    "             SLK_BUILD_BATCH_BASES (bases per batch of `build` and `coverage`, default 2^30), SLK_MASK_BATCH_BASES (bytes of text per piece\n"
+    "             of `mask` and letters per staged batch of slk_mask_sequences, default 2^28), SLK_COVERAGE_MAX_PAIRS ((minimizer, source\n"
     "             taxon) pairs `coverage` counts at a time, default: what half of the GPU's free memory holds), SLK_EXPORT_PIECE_BUCKETS (table buckets per exported\n"
     "             piece of `build` and `respace`, default 2^23)\n";
 
@@ -1347,7 +1456,7 @@ int main(int argc, char **argv) {
     if (i + 1 < argc) g_partitions = atoi(argv[i + 1]);
     i += 2;
   }
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|bracken-build|compare-index|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|mask|bracken-build|compare-index|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1357,7 +1466,7 @@ int main(int argc, char **argv) {
       {"bracken-build", cmd_bracken_build}, {"kmer-distrib", cmd_kmer_distrib}, {"compare-index", cmd_compare_index},
       {"compareIndex", cmd_compare_index}, {"migration-report", cmd_migration_report}, {"stats", cmd_stats}, {"inspect", cmd_inspect},
       {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build},
-      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}, {"support", cmd_support}};
+      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}, {"support", cmd_support}, {"mask", cmd_mask}};
   // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
   //  they were commands)
   const bool bare = (cmd == "stats" || cmd == "inspect") && i >= argc;
@@ -1367,6 +1476,6 @@ int main(int argc, char **argv) {
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `bracken-build`, `compare-index`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `mask`, `bracken-build`, `compare-index`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }
