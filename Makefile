@@ -29,7 +29,7 @@ $(STREAM_SUM): tools/stream_sum.hip
 
 HIPSRC := $(addprefix $(CSRC)/,kernels.hip fused.hip lane.hip build.hip shard.hip wide.hip capi.hip index.hip classify.hip shardset.hip bracken.hip migration.hip taxstats.hip respace.hip export.hip coverage.hip support.hip textparse.hip readform.hip pipe.hip mask.hip)
 
-$(LIB): $(HIPSRC) $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h $(CSRC)/chunkscan.h $(CSRC)/wavetools.h $(CSRC)/chunkcut.h slacken_amd/host/pack.hpp include/slacken_amd.h
+$(LIB): $(HIPSRC) $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/hostside.h $(CSRC)/pairmap.h $(CSRC)/chunkscan.h $(CSRC)/wavetools.h $(CSRC)/chunkcut.h $(CSRC)/pieces.h slacken_amd/host/pack.hpp include/slacken_amd.h
 	@mkdir -p slacken_amd/lib
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIPSRC) -ldl
 

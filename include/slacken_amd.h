@@ -641,6 +641,39 @@ int32_t slk_stream_last_stage_ms(slk_stream *st, float out_ms[3]);
  * (longer than 1000 bases, or more than 12 distinct taxa); 0 if that call did not take the lane kernel.  Synchronises st. */
 int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count);
 
+/* ---- Contig-length fragments: one fragment split over many waves.  A fragment otherwise runs on ONE wave, at
+ * about 15 Mbp/s, with a taxon map of 128 entries; a batch of a few hundred assembled contigs leaves most of the part idle, and a contig
+ * that names more than 128 taxa sends its whole batch through the staged kernels again.  On the piece route an unpaired fragment of at
+ * least min_len bases is cut into pieces of 65 536 k-mer windows, every piece is scanned and probed by a wave of its own, and the
+ * pieces' counts are merged in HBM, in a taxon map that cannot overflow, before the fragment is resolved -- with the results of the
+ * other routes, bit for bit.  Scope: unpaired fragments, the default window of five m-mers, calls that want no hit lists; everything
+ * else keeps its route.  A fragment of 2^31 bases or more on this route fails the call (SLK_E_INVALID, at the next synchronisation).
+ *   slk_stream_set_split_long  min_len = -1: the engine's own choice -- fragments of at least 300 000 bases (where the route measured
+ *                              faster), in batches whose fragments average over 1000 bases and whose map scratch
+ *                              stays under 2 GiB and under 8 bytes per base of the batch (it grows with the cells' taxon bits:
+ *                              with 18-bit ids 300 kbp contigs stay unsplit, 4 Mbp ones are split); batches of reads see nothing
+ *                              of the route --, 0: off, > 0: fragments of at
+ *                              least that many bases, whatever scratch that takes (with many taxon bits and fragments of a few
+ *                              hundred kbp that measured SLOWER than not splitting: DESIGN.md 21); holds for every later classify call on st, through
+ *                              whichever entry: slk_classify_batch[_packed], slk_classify_batch_device, slk_classify_text and the
+ *                              batches of a slk_pipe all reach the same dispatch.  SLK_E_INVALID below -1.
+ *   slk_stream_last_split      of the last classify call on st: the fragments that took the piece route, the pieces they made, and
+ *                              how often a wave emptied a full 128-entry map into its fragment's map before its piece ended; zeros
+ *                              if the route did not run.  Synchronises st.
+ * Environment, read per call: SLK_PIECE_MIN_LEN overrides the setter; SLK_PIECE_WINDOWS sets the piece size in windows (rounded up to
+ * a multiple of 64, at least 4 096).  The entries that take host arrays (slk_classify_batch[_packed], slk_classify_text) size the
+ * scratch from the fragments' lengths and run nothing of the route for a batch without a fragment of min_len bases.  The device
+ * entries and slk_pipe know total_bases alone: a batch of at least min_len bases in all gets one 64-byte memset, four launches and
+ * map scratch for the worst batch of its size -- 32 bytes per base of the batch or, where that is less, 32 bytes per taxon id the
+ * cells can name (2^taxon_bits) for each fragment of min_len bases the batch could hold; SLK_DEBUG_SPLIT=1 prints
+ * slk_stream_last_split's numbers to stderr after every call that ran the route.
+ * A slk_pipe's streams are the pipe's own: its batches follow the engine's choice, or SLK_PIECE_MIN_LEN. */
+int32_t slk_stream_set_split_long(slk_stream *st, int64_t min_len);
+int32_t slk_stream_last_split(slk_stream *st, uint64_t *fragments, uint64_t *pieces, uint64_t *spills);
+/* What the route holds on st: the waves of the piece kernel's fixed grid (more pieces than that are drawn from a counter), and the
+ * bytes of device scratch the route has allocated on st so far (0 until a call ran it; it grows to the largest call's need). */
+int32_t slk_stream_split_info(slk_stream *st, uint64_t *grid_waves, uint64_t *scratch_bytes);
+
 /* ---- Bracken weights: replaces BrackenWeights.buildWeights (S/slacken/BrackenWeights.scala:294-352) -- every read of length
  * read_len at every position of every record (readClassifications :251-268) classified against the index (classify :276-285:
  * resolveTree with confidence 0 and minHitGroups 2) and counted by (dest, source) (groupBy, :350).

@@ -93,7 +93,8 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_pair_device", "slk_parse_text_paired", "slk_classify_text_paired",
            "slk_pipe_create", "slk_pipe_set_merged_hits", "slk_pipe_submit", "slk_pipe_collect", "slk_pipe_pending", "slk_pipe_destroy",
            "slk_pack_bases_sparse",
-           "slk_mask_tile_bases", "slk_mask_device", "slk_mask_sequences", "slk_index_add_sequences_masked"]
+           "slk_mask_tile_bases", "slk_mask_device", "slk_mask_sequences", "slk_index_add_sequences_masked",
+           "slk_stream_set_split_long", "slk_stream_last_split", "slk_stream_split_info"]
 
 PAIR_FIELDS = ("P", "mismatch", "consumed1", "consumed2", "R1", "R2", "n_bases", "n_mate_bases")   # slk_pair_record, in order
 
@@ -203,6 +204,9 @@ def lib():
     L.slk_shard_chunk.restype = C.c_uint32
     L.slk_shard_step_device.argtypes = [vp, vp, C.POINTER(ShardLists), C.POINTER(ShardLookup), C.POINTER(ShardLists), C.POINTER(ShardResults)]
     L.slk_stream_last_deferred.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.slk_stream_set_split_long.argtypes = [vp, C.c_int64]
+    L.slk_stream_last_split.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.slk_stream_split_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.slk_bracken_create.argtypes = [vp, C.c_int32, C.c_uint64, C.POINTER(vp)]
     L.slk_bracken_add.argtypes = [vp, vp, u8p, u64p, i32p, C.c_uint64]
     L.slk_bracken_result.argtypes = [vp, C.POINTER(C.c_uint64), i32p, i32p, u64p, C.c_uint64]
@@ -933,6 +937,24 @@ class Stream:
         n = C.c_uint64(0)
         _check(lib().slk_stream_last_deferred(self.h, C.byref(n)))
         return int(n.value)
+
+    def set_split_long(self, min_len=-1):
+        """Unpaired fragments of at least min_len bases are split over many waves (slk_stream_set_split_long):
+        -1 the engine's own choice (300 000 bases, in batches of long fragments), 0 off.  Holds for every later classify call on this stream."""
+        _check(lib().slk_stream_set_split_long(self.h, int(min_len)))
+
+    def last_split(self):
+        """(fragments, pieces, spills) of the last classify call: the fragments that were split, the pieces they made, and how often a
+        wave emptied a full 128-entry taxon map before its piece ended (slk_stream_last_split)"""
+        f, p, s = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _check(lib().slk_stream_last_split(self.h, C.byref(f), C.byref(p), C.byref(s)))
+        return int(f.value), int(p.value), int(s.value)
+
+    def split_info(self):
+        """(waves of the piece kernel's fixed grid, bytes of scratch the piece route holds on this stream) (slk_stream_split_info)"""
+        g, b = C.c_uint64(0), C.c_uint64(0)
+        _check(lib().slk_stream_split_info(self.h, C.byref(g), C.byref(b)))
+        return int(g.value), int(b.value)
 
     def mask_sequences(self, bases, offsets, window=64, threshold=20, replacement=ord("x")):
         """Low-complexity masking (symmetric DUST; slk_mask_sequences) of sequences in the layout of add_sequences

@@ -93,6 +93,15 @@ static int32_t run_unbounded(slk_stream *st, const ClassifyCall &c) {
 
 int32_t slk::check_status(slk_stream *st) {
   int32_t v = *st->h_status;
+  // SLK_DEBUG_SPLIT (tuning and test aid, like SLK_DEBUG_CALL_TIMING): what the piece route did in the call that is through, once per
+  // call, for the callers whose streams nobody else can ask (a slk_pipe's slots, the command line's workers)
+  if (st->last_used_pieces && !st->split_reported && getenv("SLK_DEBUG_SPLIT") != nullptr) {
+    uint64_t hdr[PieceHdr::WORDS];
+    if (hipMemcpy(hdr, st->piece_scratch.p, sizeof(hdr), hipMemcpyDeviceToHost) == hipSuccess)
+      fprintf(stderr, "slk split: %llu fragments, %llu pieces, %llu spills\n", (unsigned long long)hdr[PieceHdr::N_FRAG],
+              (unsigned long long)hdr[PieceHdr::N_UNIT], (unsigned long long)hdr[PieceHdr::SPILLS]);
+    st->split_reported = true;
+  }
   std::vector<slk_stream::Queued> queued;
   queued.swap(st->queued);
   if (v != 0) {
@@ -110,6 +119,9 @@ int32_t slk::check_status(slk_stream *st) {
       st->reran = true;
       return SLK_OK;
     }
+    if (v & PIECE_STATUS_TOO_LONG) return fail(SLK_E_INVALID, "a fragment of 2^31 bases or more cannot be split into pieces (slk_stream_set_split_long)");
+    if (v & PIECE_STATUS_SCRATCH) return fail(SLK_E_INVALID, "the piece route's scratch, sized from total_bases, did not hold the batch's fragments: total_bases smaller than the batch?");
+    if (v & PIECE_STATUS_MAP) return fail(SLK_E_HIP, "internal: a split fragment named more taxa than its map was sized for (device status %d)", v);
     if (v & 2) return fail(SLK_E_CAPACITY, "a send region of slk_shard_step_device's EMIT job overflowed its capacity_per_owner");
     if (v & 1) return fail(SLK_E_CAPACITY, "a fragment hit more than %d distinct taxa; the per-read taxon map overflowed", 128);
     return fail(SLK_E_HIP, "device status %d", v);
@@ -170,8 +182,30 @@ struct LanePlan {
   uint32_t seg_min_len = 0, wave_min = 0, wave_ratio_q10 = 0;
   uint64_t long_cap = 0;      // entries of a list of fragments over 1000 bases
   size_t hand_bytes = 0;      // the hand-on buffer: header and lists
+  // the piece route (engine.h: PieceArgs): on when piece_min_len != 0; then seg_min_len is at most piece_min_len, so that the
+  // routing hands every fragment the cut may take to the segment pass's list
+  uint32_t piece_min_len = 0, piece_windows = 0;
+  uint64_t piece_frags = 0, piece_units = 0, piece_map = 0;   // entries the batch can need at most
 };
-static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want_hits, int w) {
+// The engine's own threshold of the piece route (slk_stream_set_split_long(-1)): the smallest length at which the route measured
+// faster than the routes before it by more than the spread of the runs (profiles/r16_contigs.json: 100 against 82 Gbp/s at 300 kbp,
+// 105 / 41 at 1 Mbp, 108 / 10 at 4 Mbp), never under two pieces.  Unasked, the route runs only where the host can tell
+// that it costs nothing: in batches whose fragments average over 1000 bases (the batches of reads -- the headline -- see no launch,
+// memset or allocation of it), and while its map scratch stays under PIECE_DEFAULT_MAP_BYTES (a caller who names a threshold gets
+// the scratch the batch needs, whatever it is).
+// What the batch needs: with the offsets on the host (h_offsets: slk_classify_batch[_packed], slk_classify_text) the fragments at or
+// above the threshold are counted and their pieces and map ranges summed exactly -- a batch without such a fragment runs nothing of
+// the route.  The device entries know total_bases alone: the sums are bounds then (a cut fragment has at least min_len bases, makes at
+// most n / windows + 1 pieces of its n windows, and its map has at most 4 min(n, taxa) + 64 entries), and a batch that holds
+// min_len bases in all gets the header's memset, the four launches and the scratch of those bounds whether it has a long fragment or not.
+constexpr int64_t PIECE_DEFAULT_MIN_LEN = 300000;
+constexpr uint64_t PIECE_DEFAULT_MAP_BYTES = 2ull << 30;
+// ... and under PIECE_DEFAULT_MAP_PER_BASE bytes per base of the batch: the ranges are cleared before the pieces run and read whole by
+// the merge, and where they outweigh the bases the route loses what it gains (18 taxon bits, profiles/r16_contigs_18bit.json: 28 bytes
+// of map per base at 300 kbp, 34 against the parent's 79 Gbp/s; 8.4 at 1 Mbp, 54 against 40; 2.1 at 4 Mbp, 59 against 10)
+constexpr uint64_t PIECE_DEFAULT_MAP_PER_BASE = 8;
+static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want_hits, int w, int64_t split_long, uint32_t taxa_bound,
+                          const uint64_t *h_offsets, int k) {
   LanePlan p;
   static const bool force_wave = env_on("SLK_FORCE_WAVE");   // A/B switch: classify with the wave-per-read kernel only
   p.lane = !force_wave && R < 0xFFFFFFFFull;
@@ -207,6 +241,39 @@ static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want
   p.seg_min_len = p.seg_on ? (uint32_t)std::max(seg_min, (int)std::max<uint32_t>(p.long_max, 1000) + 1) : 0;
   p.wave_min = std::max<uint32_t>(p.long_max, 1000) + 1;   // (the wave kernel's eight length classes: 1.75^7 = 50 times the shortest)
   p.wave_ratio_q10 = 1792;
+  // The piece route takes what the segment kernel would, cut up: same scope (unpaired, w = 5, no hit lists).  SLK_PIECE_MIN_LEN
+  // overrides the stream's setting (0: off), SLK_PIECE_WINDOWS sets the piece size (a multiple of 64, at least 64 x 64).
+  const char *piece_env = getenv("SLK_PIECE_MIN_LEN");
+  int64_t piece_min = piece_env ? atoll(piece_env) : split_long;
+  const bool unasked = piece_min < 0;
+  if (p.seg_on && !want_hits && (unasked ? p.route_first : piece_min > 0)) {
+    const uint64_t win = (uint64_t)std::max(1L, env_long("SLK_PIECE_WINDOWS", (long)PIECE_DEFAULT_WINDOWS));
+    p.piece_windows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((win + 63) / 64 * 64, PIECE_MIN_WINDOWS), 1u << 30);
+    if (unasked) piece_min = std::max<int64_t>(PIECE_DEFAULT_MIN_LEN, 2 * (int64_t)p.piece_windows);
+    const uint64_t min_len = std::min<uint64_t>(std::max<uint64_t>((uint64_t)piece_min, (uint64_t)std::max<uint32_t>(p.long_max, 1000) + 1), 0x7FFFFFFFull);
+    uint64_t units = 0;
+    if (h_offsets) {
+      for (uint64_t r = 0; r < R; r++) {
+        const uint64_t len = h_offsets[r + 1] - h_offsets[r];
+        if (len < min_len || len > 0x7FFFFFFFull) continue;   // (host entries hold no longer fragment: validate_reads)
+        const uint32_t nwin = (uint32_t)len - (uint32_t)k + 1;
+        p.piece_frags++;
+        units += (nwin + p.piece_windows - 1) / p.piece_windows;
+        p.piece_map += piece_map_cap(nwin, taxa_bound);
+      }
+    } else {
+      p.piece_frags = std::min<uint64_t>(R, all_bases / min_len);
+      units = all_bases / p.piece_windows + p.piece_frags;
+      p.piece_map = 4 * std::min<uint64_t>(all_bases, p.piece_frags * (uint64_t)taxa_bound) + 64 * p.piece_frags;
+    }
+    // (no fragment of the batch is that long, or the engine's own choice would take too much scratch: nothing of the route runs)
+    const uint64_t map_bytes = p.piece_map * 2 * sizeof(int32_t);
+    if (p.piece_frags != 0 && !(unasked && (map_bytes > PIECE_DEFAULT_MAP_BYTES || map_bytes > PIECE_DEFAULT_MAP_PER_BASE * all_bases))) {
+      p.piece_min_len = (uint32_t)min_len;
+      p.piece_units = units;
+      p.seg_min_len = std::min(p.seg_min_len, p.piece_min_len);
+    }
+  }
   return p;
 }
 
@@ -239,7 +306,10 @@ int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &cal
     A.span_meta = want_hits ? st->span_meta.as<int32_t>() + span_shift : nullptr;
     A.span_taxon = want_hits ? st->span_taxon.as<int32_t>() + span_shift : nullptr;
     A.span_count = want_hits ? st->span_count.as<int32_t>() : nullptr;
-    const LanePlan plan = lane_path_ok(ix) ? plan_lane(R, in.total + in.mate_total, paired, want_hits, ix->sp.w) : LanePlan{};
+    const uint32_t taxa_bound = 1u << std::min(ix->internal_taxon_bits(), 22);   // (lane_path_ok: at most 22 bits)
+    const LanePlan plan = lane_path_ok(ix) ? plan_lane(R, in.total + in.mate_total, paired, want_hits, ix->sp.w, st->split_long, taxa_bound, c.h_offsets, ix->sp.k) : LanePlan{};
+    st->last_used_pieces = false;
+    st->split_reported = false;
     if (plan.lane) {
       st->last_used_lane = true;
       const size_t hdr_bytes = HandOn::WORDS * sizeof(uint64_t);
@@ -265,6 +335,23 @@ int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &cal
       HIPCHK(hipEventRecord(st->ev_fork, st->s));
       if (A.long_max) launch_lane_long(A, A.long_max, st->s);   // (first: its chain of steps is the longest, whoever comes first gets the CUs)
       HIPCHK(hipStreamWaitEvent(st->s2, st->ev_fork, 0));
+      if (plan.piece_min_len) {
+        // the piece route's scratch: header, fragment slots, unit list, piece records; and the maps
+        const size_t hdr_b = PieceHdr::WORDS * sizeof(uint64_t), frag_b = plan.piece_frags * sizeof(PieceFrag), unit_b = plan.piece_units * sizeof(uint64_t);
+        HIPCHK(st->piece_scratch.ensure(hdr_b + frag_b + unit_b + plan.piece_units * sizeof(PieceRecord)));
+        HIPCHK(st->piece_maps.ensure(plan.piece_map * 2 * sizeof(int32_t)));
+        PieceArgs X{};
+        char *const base = (char *)st->piece_scratch.p;
+        X.hdr = (unsigned long long *)base; X.frags = (PieceFrag *)(base + hdr_b); X.units = (uint64_t *)(base + hdr_b + frag_b);
+        X.records = (PieceRecord *)(base + hdr_b + frag_b + unit_b);
+        X.map_key = st->piece_maps.as<int32_t>(); X.map_cnt = X.map_key + plan.piece_map;
+        X.frag_cap = plan.piece_frags; X.unit_cap = plan.piece_units; X.map_cap = plan.piece_map;
+        X.seg_list = A.hand_lists + HandOn::list_at(HandOn::SEG, R, plan.long_cap); X.seg_count = A.hand_hdr + HandOn::SEG;
+        X.min_len = plan.piece_min_len; X.windows = plan.piece_windows; X.taxa_bound = taxa_bound;
+        HIPCHK(hipMemsetAsync(X.hdr, 0, hdr_b, st->s2));
+        launch_pieces(A, X, st->s2);   // (before the segment pass: the cut takes its fragments out of that pass's list)
+        st->last_used_pieces = true;
+      }
       if (plan.seg_on) {
         FusedArgs B = A;
         if (want_hits) B.span_keys = st->span_keys.as<uint64_t>() + span_shift;   // (scratch of the hit lists: the spans' places before the borders are settled)
@@ -576,6 +663,33 @@ int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count) {
   return SLK_OK;
 }
 
+int32_t slk_stream_set_split_long(slk_stream *st, int64_t min_len) {
+  if (!st) return fail(SLK_E_INVALID, "null handle");
+  if (min_len < -1) return fail(SLK_E_INVALID, "min_len %lld: -1 (the engine's default), 0 (off) or a number of bases", (long long)min_len);
+  st->split_long = min_len;
+  return SLK_OK;
+}
+
+int32_t slk_stream_last_split(slk_stream *st, uint64_t *fragments, uint64_t *pieces, uint64_t *spills) {
+  if (!st || !fragments || !pieces || !spills) return fail(SLK_E_INVALID, "null argument");
+  { int32_t rc_ = set_device(st->ix); if (rc_) return rc_; }
+  *fragments = *pieces = *spills = 0;
+  HIPCHK(hipStreamSynchronize(st->s));
+  if (st->piece_scratch.p && st->last_used_pieces) {
+    uint64_t hdr[PieceHdr::WORDS];
+    HIPCHK(hipMemcpy(hdr, st->piece_scratch.p, sizeof(hdr), hipMemcpyDeviceToHost));
+    *fragments = hdr[PieceHdr::N_FRAG]; *pieces = hdr[PieceHdr::N_UNIT]; *spills = hdr[PieceHdr::SPILLS];
+  }
+  return SLK_OK;
+}
+
+int32_t slk_stream_split_info(slk_stream *st, uint64_t *grid_waves, uint64_t *scratch_bytes) {
+  if (!st || !grid_waves || !scratch_bytes) return fail(SLK_E_INVALID, "null argument");
+  *grid_waves = (uint64_t)PIECE_GRID_BLOCKS * 4;
+  *scratch_bytes = st->piece_scratch.cap + st->piece_maps.cap;
+  return SLK_OK;
+}
+
 int32_t slk_stream_last_stage_ms(slk_stream *st, float out_ms[3]) {
   if (!st || !out_ms) return fail(SLK_E_INVALID, "null argument");
   if (!st->timed) return fail(SLK_E_STATE, "no classify call has been issued on this stream");
@@ -748,6 +862,7 @@ static ClassifyCall sub_call(const ClassifyCall &whole, uint64_t r0, uint64_t r1
   ClassifyCall c = whole;
   const bool paired = whole.in.paired();
   c.in.offsets += r0;
+  c.h_offsets = h_offsets + r0;
   if (paired) c.in.mate_offsets += r0;
   c.in.R = r1 - r0; c.in.total = h_offsets[r1]; c.in.mate_total = paired ? h_mate_offsets[r1] : 0;
   c.out.taxon += r0; c.out.classified += r0; c.out.nd += r0; c.out.tk += r0; c.out.nh += r0;
@@ -922,6 +1037,7 @@ static int32_t classify_batch_host(slk_index *ix, slk_stream *st, const ReadSour
   whole.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
                st->out_nh.as<int32_t>(), nullptr, R};
   whole.thr = thresholds_of(thresholds, C); whole.C = C; whole.min_hit_groups = min_hit_groups; whole.want_hits = want_hits;
+  whole.h_offsets = offsets;
   DrainOnExit drain(st);   // (from the first copy queued below, no return leaves work behind that touches the caller's memory)
   if (use_fused(ix) && R >= 2 * SUB) {
     rc = run_sub_batches(ix, st, src, offsets, mate_offsets, whole, SUB, out, &early_down);
@@ -1028,6 +1144,7 @@ int32_t slk_classify_text(slk_index *ix, slk_stream *st, const uint8_t *text, ui
   whole.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
                st->out_nh.as<int32_t>(), nullptr, R};
   whole.thr = thresholds_of(thresholds, C); whole.C = C; whole.min_hit_groups = min_hit_groups; whole.want_hits = want_hits;
+  whole.h_offsets = out_offsets;
   st->reran = false;
   rc = run_classify(ix, st, whole);
   if (rc) return rc;

@@ -385,6 +385,61 @@ struct FusedArgs {
   unsigned long long *work_draw;
 };
 
+// The piece route (pieces.h): an unpaired fragment of at least `min_len` bases on the segment kernel's hand-on list
+// is cut into pieces of `windows` k-mer windows, each piece is a unit of piece_kernel (one wave, one lane per segment: the body of
+// segment_kernel), and piece_merge_kernel settles the borders between pieces and resolves the fragment, one wave per fragment.
+// What crosses from one kernel to the next lies in HBM: a record per piece and the fragment's taxon -> count map, an open-addressing
+// table in a range of the fragment's own (EMPTY keys, sized so that it cannot fill: piece_map_cap).
+struct PieceRecord {                     // what a piece leaves for the merge (its inner borders are settled)
+  uint64_t first_key, last_key;          // keys of its first and of its last super-mer (PIECEF_HAS)
+  uint32_t flags;                        // SEGF_* of its last lane, PIECEF_* of its first
+  int32_t nd, n_out, total, np;          // provisional: the borders between pieces are not settled
+  uint32_t pad[3];
+};
+enum { PIECEF_HAS = 1, PIECEF_ENDS_OPEN = 2, PIECEF_END_AMB = 4,   // (= SEGF_*, fused.hip)
+       PIECEF_STARTS_SEQ = 8,            // its first window is a k-mer of a sequence run
+       PIECEF_FIRST_AMB = 16,            // its first run is an ambiguous span
+       PIECEF_FIRST_NZ = 32 };           // its first super-mer has a taxon (so it was counted as a distinct hit group)
+struct PieceFrag {
+  uint32_t r, npieces;
+  uint64_t unit0;                        // its records are records[unit0 .. unit0 + npieces)
+  uint64_t map0;                         // its map is map_key / map_cnt[map0 .. map0 + cap)
+  uint32_t cap, shift;                   // a power of two; 32 - log2(cap)
+};
+struct PieceHdr {
+  enum { N_FRAG = 0, N_UNIT = 1, N_MAP = 2, SPILLS = 3, UNIT_DRAW = 4,
+         FAILED = 5,    // the cut ran out of scratch (PIECE_STATUS_SCRATCH): the passes behind it do nothing
+         WORDS = 8 };
+};
+constexpr uint32_t PIECE_TAKEN = 0xFFFFFFFFu;       // entry of the segment list whose fragment went to the piece route (R < 2^32 - 1)
+constexpr uint32_t PIECE_MIN_WINDOWS = 64 * 64;     // 64 lanes x SEG_MIN_WINDOWS
+constexpr uint32_t PIECE_DEFAULT_WINDOWS = 64 * 1024;
+constexpr int PIECE_GRID_BLOCKS = 256 * 8;          // piece_kernel's grid (four waves a block; = SLK_PIECE_GRID_WAVES / 4)
+// status bits (1, 2: classify.hip check_status; 4: readform.hip): a fragment of 2^31 bases or more; the cut ran out of the scratch the
+// host sized; a fragment's map range filled or held more taxa than its sizing allows (cannot happen: an internal error)
+constexpr int PIECE_STATUS_TOO_LONG = 8, PIECE_STATUS_SCRATCH = 16, PIECE_STATUS_MAP = 32;
+struct PieceArgs {
+  unsigned long long *hdr;               // PieceHdr::WORDS words, zero before the cut
+  uint32_t *seg_list;                    // the segment kernel's hand-on list: entries that are cut become PIECE_TAKEN
+  const unsigned long long *seg_count;
+  PieceFrag *frags;
+  uint64_t *units;                       // fragment slot << 32 | piece number
+  PieceRecord *records;
+  int32_t *map_key, *map_cnt;
+  uint64_t frag_cap, unit_cap, map_cap;  // entries the arrays hold (the host's bounds: classify.hip piece_plan)
+  uint32_t min_len, windows;
+  uint32_t taxa_bound;                   // no fragment names more distinct taxa than this (2^bits of the cells' taxon field)
+};
+// entries of a fragment's map: its distinct taxa are at most min(windows, taxa) + 1 (NONE), held at a load of at most 0.5
+__host__ __device__ __forceinline__ uint32_t piece_map_cap(uint32_t nwin, uint32_t taxa_bound) {
+  const uint64_t need = 2 * ((uint64_t)(nwin < taxa_bound ? nwin : taxa_bound) + 1);
+  uint32_t cap = 64;
+  while (cap < need) cap <<= 1;          // (taxa_bound <= 2^22 on the lane path: at most 2^24)
+  return cap;
+}
+// cut, clear, the pieces, the merge -- BEFORE launch_segments on the same stream (the cut takes entries out of that pass's list)
+void launch_pieces(const FusedArgs &A, const PieceArgs &X, hipStream_t s);
+
 // APPLY job of the table-sharded step kernel: the lists and the log an EARLIER batch's EMIT left on this rank, the owners' answers,
 // and where that batch's results go (A: R, outputs, thresholds, taxonomy; offsets only when hit lists are written).  A.R == 0: no job.
 struct ApplyJob {
@@ -498,6 +553,9 @@ struct ClassifyCall {
   int32_t C = 0, min_hit_groups = 0;
   bool want_hits = false;
   uint64_t span_shift = 0;   // slots the span arrays are moved by for this call (classify.hip: sub_call)
+  // in.offsets as the HOST holds them ([R + 1]; the entries that take host arrays, or have just brought them back), or null: with
+  // them the piece route is planned from the fragments' true lengths (classify.hip: plan_lane), else from bounds
+  const uint64_t *h_offsets = nullptr;
 };
 // the staged classify kernel over the spans of c.in (map_scratch: their key slots, dead after the probe)
 void launch_classify(const int32_t *parents, const uint4 *nodes, int32_t T, const ClassifyCall &c, const int32_t *span_meta,

@@ -149,7 +149,7 @@ __device__ __forceinline__ void put_span(WaveLds *L, int slot, uint64_t key, int
 }
 
 // ---- probe + fold ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void map_insert(WaveLds *L, int32_t taxon, int32_t count, int32_t *status) {
+__device__ __forceinline__ bool map_try_insert(WaveLds *L, int32_t taxon, int32_t count) {   // false: the map is full
   uint32_t slot = ((uint32_t)taxon * 0x9E3779B1u) >> 25;
   int probe = 0;
   for (; probe < MAP_CAP; probe++) {
@@ -160,7 +160,10 @@ __device__ __forceinline__ void map_insert(WaveLds *L, int32_t taxon, int32_t co
     }
     slot = (slot + 1) & (MAP_CAP - 1);
   }
-  if (probe == MAP_CAP) atomicOr(status, 1);
+  return probe != MAP_CAP;
+}
+__device__ __forceinline__ void map_insert(WaveLds *L, int32_t taxon, int32_t count, int32_t *status) {
+  if (!map_try_insert(L, taxon, count)) atomicOr(status, 1);
 }
 __device__ __forceinline__ int32_t map_get(const WaveLds *L, int32_t taxon) {
   uint32_t slot = ((uint32_t)taxon * 0x9E3779B1u) >> 25;
@@ -275,29 +278,30 @@ __device__ int32_t lca_uniform(const int32_t *parents, int32_t ntax, int32_t a, 
 // the nearest map taxon above the candidate when nothing else is left outside its clade, and ends when the clade holds the whole
 // map.  No walk of parent pointers except towards a tie's LCA and past side branches.  (The intervals live in the span buffer's
 // key array, empty by now.)
-__device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArgs &A, uint64_t r, int lane, int32_t total, int32_t nd,
-                                                      const int2 *dense, int D) {
-  uint32_t *const tin = (uint32_t *)L->span_key, *const tout = tin + MAP_CAP;
-  static_assert(SPAN_CAP * sizeof(uint64_t) >= 2 * MAP_CAP * sizeof(uint32_t), "the intervals alias the span keys");
-  for (int b0 = 0; b0 < D; b0 += 64) {
-    const int i = b0 + lane;
-    if (i < D) {
-      const uint4 n = tax_node(A.nodes, A.ntax, dense[i].x);
-      tin[i] = n.y; tout[i] = n.z;
-    }
-  }
-  wave_sync();
+// (the storage of the map is the caller's: M.taxon / count / in / out of entry i -- the wave's LDS here, the fragment's HBM range on the
+//  piece route, pieces.h)
+struct LdsMapView {
+  const int2 *dense;
+  const uint32_t *tin, *tout;
+  __device__ __forceinline__ int32_t taxon(int i) const { return dense[i].x; }
+  __device__ __forceinline__ int32_t count(int i) const { return dense[i].y; }
+  __device__ __forceinline__ uint32_t in(int i) const { return tin[i]; }
+  __device__ __forceinline__ uint32_t out(int i) const { return tout[i]; }
+};
+template <class MapView>
+__device__ __forceinline__ void resolve_intervals(WaveLds *L, const FusedArgs &A, uint64_t r, int lane, int32_t total, int32_t nd, const MapView &M,
+                                                  int D) {
   // step 1 (:101-123): the LCA of the taxa with the maximal root-path score
   int32_t maxTaxon = 0, best = 0, sum_all = 0;
   uint32_t m_in = 0, m_out = 0;
   for (int b0 = 0; b0 < D; b0 += 64) {
     const int i = b0 + lane;
-    const int32_t t = i < D ? dense[i].x : 0;
+    const int32_t t = i < D ? M.taxon(i) : 0;
     const bool act = t != 0;   // (the map of this kernel keeps NONE, as TaxonCounts.toMap does: it is on no root path and in no clade)
-    const uint32_t ain = act ? tin[i] : 0u, aout = act ? tout[i] : 0u;
+    const uint32_t ain = act ? M.in(i) : 0u, aout = act ? M.out(i) : 0u;
     int32_t score = 0;
-    for (int j = 0; j < D; j++) score += (act && tin[j] <= ain && ain <= tout[j]) ? dense[j].y : 0;   // (uniform j: LDS broadcasts)
-    sum_all += wave_sum(act ? dense[i].y : 0);
+    for (int j = 0; j < D; j++) score += (act && M.in(j) <= ain && ain <= M.out(j)) ? M.count(j) : 0;   // (uniform j: LDS broadcasts)
+    sum_all += wave_sum(act ? M.count(i) : 0);
     const int32_t mx = wave_max(act ? score : -1);
     if (mx > best) { best = mx; maxTaxon = 0; }
     if (mx == best && best > 0) {
@@ -335,11 +339,11 @@ __device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArg
       uint32_t up_in = 0;
       for (int b0 = 0; b0 < D; b0 += 64) {
         const int i = b0 + lane;
-        if (i < D && dense[i].x != 0) {
-          const uint32_t jin = tin[i], jout = tout[i];
+        if (i < D && M.taxon(i) != 0) {
+          const uint32_t jin = M.in(i), jout = M.out(i);
           const bool inside = cin <= jin && jin <= cout;
           const bool above = !inside && jin <= cin && cin <= jout;
-          sum += inside ? dense[i].y : 0;
+          sum += inside ? M.count(i) : 0;
           side = side || (!inside && !above);
           if (above && jin > up_in) up_in = jin;   // (deeper on the candidate's root path = later in the tour)
         }
@@ -352,7 +356,7 @@ __device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArg
         const uint32_t nearest = (uint32_t)wave_max((int)up_in);
         for (int b0 = 0; b0 < D; b0 += 64) {
           const int i = b0 + lane;
-          if (i < D && dense[i].x != 0 && tin[i] == nearest) { L->result[0] = dense[i].x; L->result[1] = (int32_t)tout[i]; }
+          if (i < D && M.taxon(i) != 0 && M.in(i) == nearest) { L->result[0] = M.taxon(i); L->result[1] = (int32_t)M.out(i); }
         }
         wave_sync();
         mt = L->result[0]; cin = nearest; cout = (uint32_t)L->result[1];
@@ -370,6 +374,20 @@ __device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArg
       A.out_classified[(uint64_t)c * A.out_stride + r] = classified ? 1 : 0;
     }
   }
+}
+__device__ __forceinline__ void resolve_map_intervals(WaveLds *L, const FusedArgs &A, uint64_t r, int lane, int32_t total, int32_t nd,
+                                                      const int2 *dense, int D) {
+  uint32_t *const tin = (uint32_t *)L->span_key, *const tout = tin + MAP_CAP;
+  static_assert(SPAN_CAP * sizeof(uint64_t) >= 2 * MAP_CAP * sizeof(uint32_t), "the intervals alias the span keys");
+  for (int b0 = 0; b0 < D; b0 += 64) {
+    const int i = b0 + lane;
+    if (i < D) {
+      const uint4 n = tax_node(A.nodes, A.ntax, dense[i].x);
+      tin[i] = n.y; tout[i] = n.z;
+    }
+  }
+  wave_sync();
+  resolve_intervals(L, A, r, lane, total, nd, LdsMapView{dense, tin, tout}, D);
 }
 
 // resolveTree over the LDS map (the general case: at least two distinct non-NONE taxa)
@@ -799,33 +817,49 @@ __device__ __forceinline__ void seg_flush_queue(SegHitLds<true> *Q, uint2 *mine,
 template <bool ALL>
 __device__ __forceinline__ void seg_flush_queue(SegHitLds<false> *, uint2 *, int) {}
 
-template <bool HITS>
-__global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
-  __shared__ WaveLds lds[FW];
-  __shared__ SegLds seg[FW];
-  __shared__ SegHitLds<HITS> hitq[FW];
-  // (four blocks per CU at 37 888 bytes; at 39 936 -- four times that is still under 160 KB -- the part held three, and the kernel
-  //  lost 12 %: what only the hit lists need lives in SegHitLds)
-  static_assert(HITS || FW * (sizeof(WaveLds) + sizeof(SegLds)) <= 37888, "the plain variant's LDS block grew: four blocks per CU no longer fit");
+}  // namespace slk
+#include "pieces.h"   // the piece route's own kernels and what segment_body calls of it (on top of the wave helpers above)
+namespace slk {
+
+// PIECE (pieces.h; never with HITS): the units are pieces of fragments -- `windows` k-mer windows of one, the last piece the rest --
+// drawn from X's unit list.  A piece is scanned, probed and folded like a whole fragment; at its end its inner borders are settled as
+// below, and instead of resolving, the wave leaves a record of its two ends and adds its map to the fragment's map in HBM.  A wave
+// whose LDS map fills before its piece ends empties it into that map and goes on: nothing here raises status bit 1.
+template <bool HITS, bool PIECE>
+__device__ __forceinline__ void segment_body(const FusedArgs &A, const PieceArgs &X, WaveLds *L, SegLds *G, SegHitLds<HITS> *Q) {
+  static_assert(!(HITS && PIECE), "the piece route writes no hit lists");
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  WaveLds *L = &lds[wib];
-  SegLds *G = &seg[wib];
-  SegHitLds<HITS> *Q = &hitq[wib];
   const ScanParams P = A.P;
   const int k = P.k, m = P.m;
   const uint64_t nwaves = (uint64_t)gridDim.x * FW;
-  const uint64_t nunits = (uint64_t)*A.work_count;
+  const uint64_t nunits = PIECE ? (X.hdr[PieceHdr::FAILED] ? 0 : (uint64_t)X.hdr[PieceHdr::N_UNIT]) : (uint64_t)*A.work_count;
+  unsigned long long *const draw = PIECE ? X.hdr + PieceHdr::UNIT_DRAW : A.work_draw;
   const uint64_t bases_end = A.offsets[A.R];
   const uint32_t VM = (1u << 1) | (1u << 3) | (1u << 7) | (1u << 20) | (1u << 21);  // A C G T U, either case
   for (uint64_t unit = (uint64_t)blockIdx.x * FW + wib, it = 0;; it++) {
-    if (it) unit = A.work_draw ? nwaves + next_unit(A.work_draw) : unit + nwaves;   // (as in fused_kernel)
+    if (it) unit = draw ? nwaves + next_unit(draw) : unit + nwaves;   // (as in fused_kernel)
     if (unit >= nunits) break;
-    const uint64_t r = A.work_list[unit];
-    const uint64_t o = A.offsets[r];
-    const uint32_t n_all = (uint32_t)(A.offsets[r + 1] - o);
+    uint64_t r, o;
+    uint32_t nwin;                                  // k-mer windows of the unit (seg_min_len > k)
+    PieceFrag frag{};
+    uint32_t piece = 0, spills = 0;
+    if constexpr (PIECE) {
+      const uint64_t u = X.units[unit];
+      frag = X.frags[u >> 32];
+      piece = (uint32_t)u;
+      r = frag.r;
+      const uint64_t fo = A.offsets[r];
+      const uint32_t w_first = piece * X.windows;   // (a fragment holds fewer than 2^31 windows)
+      o = fo + w_first;
+      nwin = min(X.windows, (uint32_t)(A.offsets[r + 1] - fo) - (uint32_t)k + 1 - w_first);
+    } else {
+      r = A.work_list[unit];
+      if (r == PIECE_TAKEN) continue;               // (the piece route took this fragment: launch_pieces)
+      o = A.offsets[r];
+      nwin = (uint32_t)(A.offsets[r + 1] - o) - (uint32_t)k + 1;
+    }
     // ---- this lane's segment ----
-    const uint32_t nwin = n_all - (uint32_t)k + 1;  // (seg_min_len > k)
     const uint32_t S = max(SEG_MIN_WINDOWS, (nwin + 63) / 64);
     const uint32_t w0 = (uint32_t)lane * S;
     const bool exists = w0 < nwin;
@@ -949,7 +983,7 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
             if (emit) put_span(L, slot, ekey, ekmers, 1, distinct);
             else put_span(L, slot, 0, amb_kmers, 2, false);
             if constexpr (HITS) Q->span_dst[slot] = ((uint32_t)lane << 26) | lcount;     // whose span, and its number there (a lane has fewer than 2^25 windows)
-            if (is_first && lane > 0) first_slot = slot;
+            if (is_first && (PIECE || lane > 0)) first_slot = slot;   // (PIECE: lane 0's first super-mer follows another piece's last)
           }
           lcount += push ? 1u : 0u;
           nbuf += __popcll(E);
@@ -999,7 +1033,19 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
           }
         }
         if (map_mode) {
-          if (real) map_insert(L, taxon, count, A.status);
+          if constexpr (PIECE) {
+            // a full LDS map is emptied into the fragment's map; the entries that found no slot follow it there
+            const bool left = real && !map_try_insert(L, taxon, count);
+            if (__ballot(left) != 0) {
+              wave_sync();
+              piece_map_fold(L, X, frag, lane, A.status);
+              wave_sync();
+              if (left) piece_map_add(X, frag, taxon, count, A.status);
+              spills++;
+            }
+          } else if (real) {
+            map_insert(L, taxon, count, A.status);
+          }
         } else if (real) {
           if (taxon != 0) acc_t0 += count;
           else acc_none += count;
@@ -1041,6 +1087,33 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
     nd -= __popcll(__ballot(undo_distinct));
     n_out += (HITS ? 0 : wave_sum(namb)) - wave_sum(merged);   // (HITS: the ambiguous spans went through the buffer and are counted)
     total = wave_sum(total);
+    if constexpr (PIECE) {
+      // what the merge needs of this piece: the keys of its first and of its last super-mer (whichever lanes hold them), how its
+      // last lane ended and how lane 0 began -- and its counts, provisional like a lane's until the borders between pieces are settled
+      const uint64_t has = __ballot(have_last);
+      const int lf = has ? __builtin_ctzll(has) : 0, ll = has ? 63 - __builtin_clzll(has) : 0;
+      const int le = (int)((nwin - 1) / S);                    // the last lane that has windows
+      const uint64_t fk = readlane64(first_key, lf), lk = readlane64(last_key, ll);
+      const uint32_t fl = (has ? PIECEF_HAS : 0u) | (((__ballot(ends_open) >> le) & 1) ? PIECEF_ENDS_OPEN : 0u) |
+                          (((__ballot(end_amb) >> le) & 1) ? PIECEF_END_AMB : 0u) | ((__ballot(starts_seq) & 1) ? PIECEF_STARTS_SEQ : 0u) |
+                          ((__ballot(first_run_amb) & 1) ? PIECEF_FIRST_AMB : 0u) | (((__ballot(first_nz) >> lf) & 1) ? PIECEF_FIRST_NZ : 0u);
+      if (lane == 0) {
+        PieceRecord rec{};
+        rec.first_key = fk; rec.last_key = lk; rec.flags = fl;
+        rec.nd = nd; rec.n_out = n_out; rec.total = total; rec.np = np;
+        X.records[frag.unit0 + piece] = rec;
+        if (spills) atomicAdd(&X.hdr[PieceHdr::SPILLS], (unsigned long long)spills);
+      }
+      if (map_mode) {
+        piece_map_fold(L, X, frag, lane, A.status);
+      } else {   // the single-taxon summary
+        const int32_t c0 = wave_sum(acc_t0), cn = wave_sum(acc_none);
+        if (lane == 0 && t0 != 0 && c0 != 0) piece_map_add(X, frag, t0, c0, A.status);
+        if (lane == 1 && cn != 0) piece_map_add(X, frag, 0, cn, A.status);
+      }
+      wave_sync();
+      continue;
+    }
     if constexpr (HITS) {
       // the hit list in ordinal order: lane j's entries start where the earlier lanes' end
       const uint32_t mine = lcount - (uint32_t)merged;        // (merged implies lcount >= 1: the cut span is this lane's first)
@@ -1105,6 +1178,33 @@ __global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
     }
     wave_sync();
   }
+}
+
+template <bool HITS>
+__global__ void FUSED_BOUNDS segment_kernel(FusedArgs A) {
+  __shared__ WaveLds lds[FW];
+  __shared__ SegLds seg[FW];
+  __shared__ SegHitLds<HITS> hitq[FW];
+  // (four blocks per CU at 37 888 bytes; at 39 936 -- four times that is still under 160 KB -- the part held three, and the kernel
+  //  lost 12 %: what only the hit lists need lives in SegHitLds)
+  static_assert(HITS || FW * (sizeof(WaveLds) + sizeof(SegLds)) <= 37888, "the plain variant's LDS block grew: four blocks per CU no longer fit");
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  segment_body<HITS, false>(A, PieceArgs{}, &lds[wib], &seg[wib], &hitq[wib]);
+}
+// the pieces of the fragments that launch_pieces cut (X.units): the plain variant's LDS block, and its four blocks per CU
+__global__ void FUSED_BOUNDS piece_kernel(FusedArgs A, PieceArgs X) {
+  __shared__ WaveLds lds[FW];
+  __shared__ SegLds seg[FW];
+  __shared__ SegHitLds<false> hitq[FW];
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  segment_body<false, true>(A, X, &lds[wib], &seg[wib], &hitq[wib]);
+}
+
+void launch_pieces(const FusedArgs &A, const PieceArgs &X, hipStream_t s) {
+  hipLaunchKernelGGL(piece_cut_kernel, dim3(256), dim3(256), 0, s, A, X);
+  hipLaunchKernelGGL(piece_clear_kernel, dim3(1024), dim3(256), 0, s, X);
+  hipLaunchKernelGGL(piece_kernel, dim3(PIECE_GRID_BLOCKS), dim3(FW * 64), 0, s, A, X);
+  hipLaunchKernelGGL(piece_merge_kernel, dim3(512), dim3(FW * 64), 0, s, A, X);
 }
 
 // over a hand-on list (A.work_list): unpaired, window width 5; A.span_taxon set: the hit lists too (A.span_keys is their scratch)

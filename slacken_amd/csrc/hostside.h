@@ -314,6 +314,12 @@ struct slk_stream {
   bool reran = false;           // check_status classified queued calls again (a taxon map had overflowed): results on the host are stale
   bool timed = false;
   bool last_used_lane = false;  // the last classify call ran the lane kernel (defer_list[0] is its deferral count)
+  // the piece route (engine.h: PieceArgs): slk_stream_set_split_long, its scratch (header, slots, units, records | the HBM maps), and
+  // whether the last classify call ran it (piece_scratch then starts with its header: slk_stream_last_split)
+  int64_t split_long = -1;
+  DevBuf piece_scratch, piece_maps;
+  bool last_used_pieces = false;
+  bool split_reported = false;   // SLK_DEBUG_SPLIT: the last call's numbers have been printed (check_status)
   // The arguments of every classify call queued since the stream was last synchronised, for the unbounded re-run
   // (check_status): a taxon-map overflow is only seen at the next synchronisation, and by then several calls may have gone by.
   struct Queued {

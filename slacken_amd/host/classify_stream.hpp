@@ -205,6 +205,7 @@ void classify_stream(DeviceIndex &dev, const std::vector<std::string> &files, bo
     lanes[i].st = dev.st;   // the first worker runs on the calling thread with the device's own stream
     if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
     SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merge ? 1 : 0));
+    SLK_CALL(slk_stream_set_split_long(lanes[i].st, dev.split_long));
   }
   std::vector<std::thread> workers;
   for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&pass, &lanes, i] { pass.work(lanes[i]); });
@@ -212,6 +213,7 @@ void classify_stream(DeviceIndex &dev, const std::vector<std::string> &files, bo
   for (auto &t : workers) t.join();
   for (size_t i = 1; i < lanes.size(); i++) if (lanes[i].st) slk_stream_destroy(lanes[i].st);
   if (!dev.sharded) (void)slk_stream_set_merged_hits(dev.st, 0);   // (the device's own stream serves other callers: un-merged lists again)
+  if (!dev.sharded) (void)slk_stream_set_split_long(dev.st, -1);
   pass.order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING"))
     std::cerr << "host timing: " << pass.n_batches << " batches on " << n_workers << " classify thread(s) over " << dev.ixs.size() << " device table(s); summed over them: waiting for input "
@@ -436,6 +438,7 @@ void classify_text_stream(DeviceIndex &dev, const std::vector<std::string> &file
     lanes[i].st = dev.st;
     if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
     SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merged_hits && want_hits ? 1 : 0));
+    SLK_CALL(slk_stream_set_split_long(lanes[i].st, dev.split_long));
   }
   std::vector<std::thread> workers;
   for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&work, &lanes, i] { work(lanes[i]); });
@@ -443,6 +446,7 @@ void classify_text_stream(DeviceIndex &dev, const std::vector<std::string> &file
   for (auto &t : workers) t.join();
   for (size_t i = 1; i < lanes.size(); i++) slk_stream_destroy(lanes[i].st);
   (void)slk_stream_set_merged_hits(dev.st, 0);
+  (void)slk_stream_set_split_long(dev.st, -1);
   order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_batches << " chunks parsed on the device by " << lanes.size() << " classify thread(s)" << std::endl;
   std::cerr << total << " fragments" << std::endl;
@@ -693,6 +697,7 @@ void classify_paired_text_stream(DeviceIndex &dev, const std::vector<std::string
     lanes[i].st = dev.st;
     if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
     SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merged_hits && want_hits ? 1 : 0));
+    SLK_CALL(slk_stream_set_split_long(lanes[i].st, dev.split_long));
   }
   std::vector<std::thread> workers;
   for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&work, i] { work(i); });
@@ -700,6 +705,7 @@ void classify_paired_text_stream(DeviceIndex &dev, const std::vector<std::string
   for (auto &t : workers) t.join();
   for (size_t i = 1; i < lanes.size(); i++) slk_stream_destroy(lanes[i].st);
   (void)slk_stream_set_merged_hits(dev.st, 0);
+  (void)slk_stream_set_split_long(dev.st, -1);
   order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_calls << " paired calls on " << lanes.size() << " classify thread(s)" << std::endl;
   std::cerr << total << " fragments" << std::endl;

@@ -233,6 +233,7 @@ struct ClassifyOpts {
   bool shard_table = false;     // --shard-table: the table is spread over the devices instead (a library beyond one GPU's memory)
   bool device_parse = false;    // --device-parse: the raw text goes to the device, which finds the records (classify_text_stream)
   bool device_pairs = false;    // --device-pairs: both mate files' text goes to the device, which finds and pairs the records (classify_paired_text_stream)
+  long long split_long = -1;    // --split-long LEN: unpaired sequences of at least LEN bases are split over many waves (slk_stream_set_split_long)
   // classify2 (Slacken.scala:199-260)
   std::string library, rank = "species";
   int min_count = -1, min_distinct = -1, reads = -1;
@@ -270,6 +271,11 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
       if (two_step) die("--device-pairs is for classify (classify2 reads its input through the host parser)");
       o.device_pairs = true;
     }
+    else if (a == "--split-long") {
+      if (two_step) die("--split-long is for classify (classify2 classifies reads against a small dynamic library)");
+      o.split_long = std::stoll(a.next());
+      if (o.split_long < 0) die("--split-long takes a number of bases (0: never split)");
+    }
     else if (two_step && (a == "-l" || a == "--library")) o.library = a.next();
     else if (two_step && a == "--rank") o.rank = a.next();
     else if (two_step && (a == "-C" || a == "--min-count")) o.min_count = std::stoi(a.next());
@@ -297,6 +303,8 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
   if (o.device_pairs && o.device_parse) die("--device-pairs and --device-parse exclude each other: --device-pairs is the device route for paired input (-p), --device-parse the one for unpaired input");
   if (o.device_pairs && !o.paired) die("--device-pairs pairs the records of two mate files: give -p and pairs of files (--device-parse is the device route for unpaired input)");
   if (o.device_pairs && o.shard_table) die("--device-pairs needs the whole table on the device that parses (not --shard-table)");
+  if (o.split_long >= 0 && o.paired) die("--split-long splits unpaired sequences (contigs, assemblies): not with -p");
+  if (o.split_long >= 0 && o.shard_table) die("--split-long needs the whole table on the device that classifies (not --shard-table)");
   if (o.device_parse && o.paired) die("--device-parse takes unpaired input (the mates of paired reads are joined by title, on the host)");
   if (o.device_parse && o.shard_table) die("--device-parse needs the whole table on the device that parses (not --shard-table)");
   if (o.thresholds.empty()) o.thresholds.push_back(0.0);
@@ -365,7 +373,12 @@ static int cmd_classify(int argc, char **argv) {
     die("--device-parse supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
   if (o.device_pairs && read_index_params(o.index).m > 32)
     die("--device-pairs supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
+  if (o.split_long >= 0 && read_index_params(o.index).m > 32)
+    die("--split-long supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
+  if (o.split_long > 0 && o.detailed)
+    std::cerr << "note: --split-long has no effect on this run: per-read lines need hit lists, which keep the other routes (give --nodetailed)" << std::endl;
   LoadedIndex lib(o.index, o.devices, o.shard_table);
+  lib.dev.split_long = o.split_long;
   classify_and_write(lib.dev, lib.ip, lib.tax, o);
   return 0;
 }
@@ -1375,6 +1388,9 @@ static const char *HELP =
     "                         minimizers travel to their owners and taxa back): for a library beyond one GPU's memory\n"
     "      --device-parse     classify: send the files' text to the device as it is and find the records there (unpaired input, a\n"
     "                         replicated table, m <= 32; `parse --device FILE` shows what the device finds); the default parses on the host\n"
+    "      --split-long LEN   classify: split unpaired sequences of at least LEN bases (contigs, assemblies) over many waves of the\n"
+    "                         device; the results do not change.  Takes effect where no per-read lines are written (--nodetailed:\n"
+    "                         those need hit lists, which keep the other routes); not with -p or --shard-table.  0: never\n"
     "      --device-pairs     classify -p: send both mate files' text to the device, which finds the records and pairs them in lockstep\n"
     "                         (a replicated table, m <= 32); mates that are out of order end the run -- the default joins them on the host\n"
     "  FILES                  FASTA / FASTQ, plain, .gz or .bz2; @list.txt names a file of file names\n"
