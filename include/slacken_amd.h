@@ -646,8 +646,8 @@ int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count);
  * that names more than 128 taxa sends its whole batch through the staged kernels again.  On the piece route an unpaired fragment of at
  * least min_len bases is cut into pieces of 65 536 k-mer windows, every piece is scanned and probed by a wave of its own, and the
  * pieces' counts are merged in HBM, in a taxon map that cannot overflow, before the fragment is resolved -- with the results of the
- * other routes, bit for bit.  Scope: unpaired fragments, the default window of five m-mers, calls that want no hit lists; everything
- * else keeps its route.  A fragment of 2^31 bases or more on this route fails the call (SLK_E_INVALID, at the next synchronisation).
+ * other routes, bit for bit.  Scope: unpaired fragments, the default window of five m-mers, calls that want no hit lists (or
+ * slk_stream_set_split_hits); everything else keeps its route.  A fragment of 2^31 bases or more on this route fails the call (SLK_E_INVALID, at the next synchronisation).
  *   slk_stream_set_split_long  min_len = -1: the engine's own choice -- fragments of at least 300 000 bases (where the route measured
  *                              faster), in batches whose fragments average over 1000 bases and whose map scratch
  *                              stays under 2 GiB and under 8 bytes per base of the batch (it grows with the cells' taxon bits:
@@ -660,15 +660,24 @@ int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count);
  *   slk_stream_last_split      of the last classify call on st: the fragments that took the piece route, the pieces they made, and
  *                              how often a wave emptied a full 128-entry map into its fragment's map before its piece ended; zeros
  *                              if the route did not run.  Synchronises st.
- * Environment, read per call: SLK_PIECE_MIN_LEN overrides the setter; SLK_PIECE_WINDOWS sets the piece size in windows (rounded up to
+ *   slk_stream_set_split_hits  on != 0: a call that wants hit lists takes the route as well -- under the conditions a call without
+ *                              them takes it after slk_stream_set_split_long(st, min_len) with min_len > 0, and only then: with the
+ *                              engine's own choice (-1) such calls keep the other routes whatever this switch says.  Off by
+ *                              default.  The pieces' waves leave their entries where the segment kernel's lanes do, a plan per
+ *                              piece is made with the borders, and one more kernel moves the entries to their places:
+ *                              hit_offsets and hits are those of the other routes, entry for entry, merged
+ *                              (slk_stream_set_merged_hits) or not.  272 bytes of scratch per piece on top of the route's.
+ * Environment, read per call: SLK_PIECE_MIN_LEN overrides the setter, SLK_PIECE_HITS=0|1 overrides slk_stream_set_split_hits;
+ * SLK_PIECE_WINDOWS sets the piece size in windows (rounded up to
  * a multiple of 64, at least 4 096).  The entries that take host arrays (slk_classify_batch[_packed], slk_classify_text) size the
  * scratch from the fragments' lengths and run nothing of the route for a batch without a fragment of min_len bases.  The device
  * entries and slk_pipe know total_bases alone: a batch of at least min_len bases in all gets one 64-byte memset, four launches and
  * map scratch for the worst batch of its size -- 32 bytes per base of the batch or, where that is less, 32 bytes per taxon id the
  * cells can name (2^taxon_bits) for each fragment of min_len bases the batch could hold; SLK_DEBUG_SPLIT=1 prints
  * slk_stream_last_split's numbers to stderr after every call that ran the route.
- * A slk_pipe's streams are the pipe's own: its batches follow the engine's choice, or SLK_PIECE_MIN_LEN. */
+ * A slk_pipe's streams are the pipe's own: its batches follow the engine's choice, or SLK_PIECE_MIN_LEN and SLK_PIECE_HITS. */
 int32_t slk_stream_set_split_long(slk_stream *st, int64_t min_len);
+int32_t slk_stream_set_split_hits(slk_stream *st, int32_t on);
 int32_t slk_stream_last_split(slk_stream *st, uint64_t *fragments, uint64_t *pieces, uint64_t *spills);
 /* What the route holds on st: the waves of the piece kernel's fixed grid (more pieces than that are drawn from a counter), and the
  * bytes of device scratch the route has allocated on st so far (0 until a call ran it; it grows to the largest call's need). */

@@ -94,7 +94,7 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_pipe_create", "slk_pipe_set_merged_hits", "slk_pipe_submit", "slk_pipe_collect", "slk_pipe_pending", "slk_pipe_destroy",
            "slk_pack_bases_sparse",
            "slk_mask_tile_bases", "slk_mask_device", "slk_mask_sequences", "slk_index_add_sequences_masked",
-           "slk_stream_set_split_long", "slk_stream_last_split", "slk_stream_split_info"]
+           "slk_stream_set_split_long", "slk_stream_set_split_hits", "slk_stream_last_split", "slk_stream_split_info"]
 
 PAIR_FIELDS = ("P", "mismatch", "consumed1", "consumed2", "R1", "R2", "n_bases", "n_mate_bases")   # slk_pair_record, in order
 
@@ -205,6 +205,7 @@ def lib():
     L.slk_shard_step_device.argtypes = [vp, vp, C.POINTER(ShardLists), C.POINTER(ShardLookup), C.POINTER(ShardLists), C.POINTER(ShardResults)]
     L.slk_stream_last_deferred.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.slk_stream_set_split_long.argtypes = [vp, C.c_int64]
+    L.slk_stream_set_split_hits.argtypes = [vp, C.c_int32]
     L.slk_stream_last_split.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.slk_stream_split_info.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.slk_bracken_create.argtypes = [vp, C.c_int32, C.c_uint64, C.POINTER(vp)]
@@ -942,6 +943,11 @@ class Stream:
         """Unpaired fragments of at least min_len bases are split over many waves (slk_stream_set_split_long):
         -1 the engine's own choice (300 000 bases, in batches of long fragments), 0 off.  Holds for every later classify call on this stream."""
         _check(lib().slk_stream_set_split_long(self.h, int(min_len)))
+
+    def set_split_hits(self, on=True):
+        """Calls that want hit lists take the piece route too, where set_split_long(LEN > 0) would send a call without them
+        (slk_stream_set_split_hits; off by default, and never with the engine's own threshold).  The lists are those of the other routes."""
+        _check(lib().slk_stream_set_split_hits(self.h, 1 if on else 0))
 
     def last_split(self):
         """(fragments, pieces, spills) of the last classify call: the fragments that were split, the pieces they made, and how often a

@@ -186,6 +186,7 @@ struct LanePlan {
   // routing hands every fragment the cut may take to the segment pass's list
   uint32_t piece_min_len = 0, piece_windows = 0;
   uint64_t piece_frags = 0, piece_units = 0, piece_map = 0;   // entries the batch can need at most
+  bool piece_hits = false;    // the route writes hit lists (slk_stream_set_split_hits): a side array of PieceHitRecords, the move kernel
 };
 // The engine's own threshold of the piece route (slk_stream_set_split_long(-1)): the smallest length at which the route measured
 // faster than the routes before it by more than the spread of the runs (profiles/r16_contigs.json: 100 against 82 Gbp/s at 300 kbp,
@@ -204,8 +205,8 @@ constexpr uint64_t PIECE_DEFAULT_MAP_BYTES = 2ull << 30;
 // the merge, and where they outweigh the bases the route loses what it gains (18 taxon bits, profiles/r16_contigs_18bit.json: 28 bytes
 // of map per base at 300 kbp, 34 against the parent's 79 Gbp/s; 8.4 at 1 Mbp, 54 against 40; 2.1 at 4 Mbp, 59 against 10)
 constexpr uint64_t PIECE_DEFAULT_MAP_PER_BASE = 8;
-static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want_hits, int w, int64_t split_long, uint32_t taxa_bound,
-                          const uint64_t *h_offsets, int k) {
+static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want_hits, int w, int64_t split_long, bool split_hits,
+                          uint32_t taxa_bound, const uint64_t *h_offsets, int k) {
   LanePlan p;
   static const bool force_wave = env_on("SLK_FORCE_WAVE");   // A/B switch: classify with the wave-per-read kernel only
   p.lane = !force_wave && R < 0xFFFFFFFFull;
@@ -232,7 +233,8 @@ static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want
   // (hit lists: the segment kernel can put them together -- SLK_SEG_HITS=1 --, but the queues that take its spans to memory
   //  in order cost it half its resident waves, and it measured 51-53 Gbp/s against the wave kernel's 68-79 on the same reads:
   //  profiles/r03_long_hits_*.json; so per-read lines of long reads keep the wave kernel unless asked otherwise)
-  p.seg_on = (!want_hits || env_on("SLK_SEG_HITS")) && !paired && w == 5 && seg_min > 0;
+  const bool seg_ok = !paired && w == 5 && seg_min > 0;
+  p.seg_on = (!want_hits || env_on("SLK_SEG_HITS")) && seg_ok;
   p.long_max = long_max > 1000 ? (uint32_t)long_max : 0;
   if (p.long_max) {  // class borders: a geometric ladder from 1000 to the limit (a tile's lanes then differ by at most ~1.5x)
     const double ratio = pow((double)p.long_max / 1000.0, 0.25);
@@ -243,10 +245,15 @@ static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want
   p.wave_ratio_q10 = 1792;
   // The piece route takes what the segment kernel would, cut up: same scope (unpaired, w = 5, no hit lists).  SLK_PIECE_MIN_LEN
   // overrides the stream's setting (0: off), SLK_PIECE_WINDOWS sets the piece size (a multiple of 64, at least 64 x 64).
+  // A call that wants hit lists takes it only where the caller asked for both: a threshold (never the engine's own choice) and
+  // slk_stream_set_split_hits, which SLK_PIECE_HITS=0|1 overrides; the segment pass is then on for the cut's sake, and unless
+  // SLK_SEG_HITS says otherwise its list holds nothing but what the cut takes.
   const char *piece_env = getenv("SLK_PIECE_MIN_LEN");
   int64_t piece_min = piece_env ? atoll(piece_env) : split_long;
   const bool unasked = piece_min < 0;
-  if (p.seg_on && !want_hits && (unasked ? p.route_first : piece_min > 0)) {
+  const char *hits_env = getenv("SLK_PIECE_HITS");
+  const bool hits_on = hits_env ? hits_env[0] == '1' : split_hits;
+  if (want_hits ? (seg_ok && hits_on && piece_min > 0) : (p.seg_on && (unasked ? p.route_first : piece_min > 0))) {
     const uint64_t win = (uint64_t)std::max(1L, env_long("SLK_PIECE_WINDOWS", (long)PIECE_DEFAULT_WINDOWS));
     p.piece_windows = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((win + 63) / 64 * 64, PIECE_MIN_WINDOWS), 1u << 30);
     if (unasked) piece_min = std::max<int64_t>(PIECE_DEFAULT_MIN_LEN, 2 * (int64_t)p.piece_windows);
@@ -271,7 +278,9 @@ static LanePlan plan_lane(uint64_t R, uint64_t all_bases, bool paired, bool want
     if (p.piece_frags != 0 && !(unasked && (map_bytes > PIECE_DEFAULT_MAP_BYTES || map_bytes > PIECE_DEFAULT_MAP_PER_BASE * all_bases))) {
       p.piece_min_len = (uint32_t)min_len;
       p.piece_units = units;
-      p.seg_min_len = std::min(p.seg_min_len, p.piece_min_len);
+      p.piece_hits = want_hits;
+      p.seg_min_len = p.seg_on ? std::min(p.seg_min_len, p.piece_min_len) : p.piece_min_len;
+      p.seg_on = true;
     }
   }
   return p;
@@ -307,7 +316,7 @@ int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &cal
     A.span_taxon = want_hits ? st->span_taxon.as<int32_t>() + span_shift : nullptr;
     A.span_count = want_hits ? st->span_count.as<int32_t>() : nullptr;
     const uint32_t taxa_bound = 1u << std::min(ix->internal_taxon_bits(), 22);   // (lane_path_ok: at most 22 bits)
-    const LanePlan plan = lane_path_ok(ix) ? plan_lane(R, in.total + in.mate_total, paired, want_hits, ix->sp.w, st->split_long, taxa_bound, c.h_offsets, ix->sp.k) : LanePlan{};
+    const LanePlan plan = lane_path_ok(ix) ? plan_lane(R, in.total + in.mate_total, paired, want_hits, ix->sp.w, st->split_long, st->split_hits, taxa_bound, c.h_offsets, ix->sp.k) : LanePlan{};
     st->last_used_pieces = false;
     st->split_reported = false;
     if (plan.lane) {
@@ -340,6 +349,7 @@ int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &cal
         const size_t hdr_b = PieceHdr::WORDS * sizeof(uint64_t), frag_b = plan.piece_frags * sizeof(PieceFrag), unit_b = plan.piece_units * sizeof(uint64_t);
         HIPCHK(st->piece_scratch.ensure(hdr_b + frag_b + unit_b + plan.piece_units * sizeof(PieceRecord)));
         HIPCHK(st->piece_maps.ensure(plan.piece_map * 2 * sizeof(int32_t)));
+        if (plan.piece_hits) HIPCHK(st->piece_hits.ensure(plan.piece_units * sizeof(PieceHitRecord)));
         PieceArgs X{};
         char *const base = (char *)st->piece_scratch.p;
         X.hdr = (unsigned long long *)base; X.frags = (PieceFrag *)(base + hdr_b); X.units = (uint64_t *)(base + hdr_b + frag_b);
@@ -349,7 +359,12 @@ int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &cal
         X.seg_list = A.hand_lists + HandOn::list_at(HandOn::SEG, R, plan.long_cap); X.seg_count = A.hand_hdr + HandOn::SEG;
         X.min_len = plan.piece_min_len; X.windows = plan.piece_windows; X.taxa_bound = taxa_bound;
         HIPCHK(hipMemsetAsync(X.hdr, 0, hdr_b, st->s2));
-        launch_pieces(A, X, st->s2);   // (before the segment pass: the cut takes its fragments out of that pass's list)
+        FusedArgs P = A;
+        if (plan.piece_hits) {
+          X.hits = st->piece_hits.as<PieceHitRecord>();
+          P.span_keys = st->span_keys.as<uint64_t>() + span_shift;   // (the provisional region, as the segment pass below has it)
+        }
+        launch_pieces(P, X, st->s2);   // (before the segment pass: the cut takes its fragments out of that pass's list)
         st->last_used_pieces = true;
       }
       if (plan.seg_on) {
@@ -670,6 +685,12 @@ int32_t slk_stream_set_split_long(slk_stream *st, int64_t min_len) {
   return SLK_OK;
 }
 
+int32_t slk_stream_set_split_hits(slk_stream *st, int32_t on) {
+  if (!st) return fail(SLK_E_INVALID, "null handle");
+  st->split_hits = on != 0;
+  return SLK_OK;
+}
+
 int32_t slk_stream_last_split(slk_stream *st, uint64_t *fragments, uint64_t *pieces, uint64_t *spills) {
   if (!st || !fragments || !pieces || !spills) return fail(SLK_E_INVALID, "null argument");
   { int32_t rc_ = set_device(st->ix); if (rc_) return rc_; }
@@ -686,7 +707,7 @@ int32_t slk_stream_last_split(slk_stream *st, uint64_t *fragments, uint64_t *pie
 int32_t slk_stream_split_info(slk_stream *st, uint64_t *grid_waves, uint64_t *scratch_bytes) {
   if (!st || !grid_waves || !scratch_bytes) return fail(SLK_E_INVALID, "null argument");
   *grid_waves = (uint64_t)PIECE_GRID_BLOCKS * 4;
-  *scratch_bytes = st->piece_scratch.cap + st->piece_maps.cap;
+  *scratch_bytes = st->piece_scratch.cap + st->piece_maps.cap + st->piece_hits.cap;
   return SLK_OK;
 }
 

@@ -400,6 +400,18 @@ enum { PIECEF_HAS = 1, PIECEF_ENDS_OPEN = 2, PIECEF_END_AMB = 4,   // (= SEGF_*,
        PIECEF_STARTS_SEQ = 8,            // its first window is a k-mer of a sequence run
        PIECEF_FIRST_AMB = 16,            // its first run is an ambiguous span
        PIECEF_FIRST_NZ = 32 };           // its first super-mer has a taxon (so it was counted as a distinct hit group)
+// HIT LISTS ON THE PIECE ROUTE (PieceArgs.hits != nullptr; slk_stream_set_split_hits): a piece's wave leaves its entries (taxon, meta)
+// in the provisional region of span_keys -- lane j's i-th at offsets[r] + piece * windows + w0(j) + i, as the segment kernel does --
+// and this record beside its PieceRecord; piece_merge_kernel fills in the plan, and piece_move_kernel, one wave per piece, moves the
+// entries to their final places in span_taxon / span_meta.
+struct PieceHitRecord {
+  uint32_t lane[64];                     // entries of the lane << 1 | its first entry merged into the lane before (lane 0: 0)
+  uint32_t head_kmers;                   // k-mers that go to the entry BEFORE the piece if a border cut its first entry: those of that
+                                         // entry and of every lane's first entry that continues it
+  uint32_t start;                        // the plan: where the piece's entries begin in the fragment's list,
+  uint32_t cut;                          //           whether its first entry continues an earlier piece's last (then it is not stored),
+  uint32_t carry;                        //           and the k-mers that LATER pieces' cut entries add to its last entry
+};
 struct PieceFrag {
   uint32_t r, npieces;
   uint64_t unit0;                        // its records are records[unit0 .. unit0 + npieces)
@@ -425,6 +437,7 @@ struct PieceArgs {
   PieceFrag *frags;
   uint64_t *units;                       // fragment slot << 32 | piece number
   PieceRecord *records;
+  PieceHitRecord *hits;                  // unit_cap of them when the call writes hit lists, else nullptr
   int32_t *map_key, *map_cnt;
   uint64_t frag_cap, unit_cap, map_cap;  // entries the arrays hold (the host's bounds: classify.hip piece_plan)
   uint32_t min_len, windows;
@@ -437,7 +450,7 @@ __host__ __device__ __forceinline__ uint32_t piece_map_cap(uint32_t nwin, uint32
   while (cap < need) cap <<= 1;          // (taxa_bound <= 2^22 on the lane path: at most 2^24)
   return cap;
 }
-// cut, clear, the pieces, the merge -- BEFORE launch_segments on the same stream (the cut takes entries out of that pass's list)
+// cut, clear, the pieces, the merge (X.hits: and the move of the hit lists) -- BEFORE launch_segments on the same stream (the cut takes entries out of that pass's list)
 void launch_pieces(const FusedArgs &A, const PieceArgs &X, hipStream_t s);
 
 // APPLY job of the table-sharded step kernel: the lists and the log an EARLIER batch's EMIT left on this rank, the owners' answers,

@@ -821,13 +821,14 @@ __device__ __forceinline__ void seg_flush_queue(SegHitLds<false> *, uint2 *, int
 #include "pieces.h"   // the piece route's own kernels and what segment_body calls of it (on top of the wave helpers above)
 namespace slk {
 
-// PIECE (pieces.h; never with HITS): the units are pieces of fragments -- `windows` k-mer windows of one, the last piece the rest --
+// PIECE (pieces.h): the units are pieces of fragments -- `windows` k-mer windows of one, the last piece the rest --
 // drawn from X's unit list.  A piece is scanned, probed and folded like a whole fragment; at its end its inner borders are settled as
 // below, and instead of resolving, the wave leaves a record of its two ends and adds its map to the fragment's map in HBM.  A wave
 // whose LDS map fills before its piece ends empties it into that map and goes on: nothing here raises status bit 1.
+// PIECE with HITS: the lanes' entries go to the provisional region as below, but they stay there -- where they end up depends on the
+// pieces before this one -- and the wave leaves a PieceHitRecord for the merge's plan and the move (pieces.h: piece_move_kernel).
 template <bool HITS, bool PIECE>
 __device__ __forceinline__ void segment_body(const FusedArgs &A, const PieceArgs &X, WaveLds *L, SegLds *G, SegHitLds<HITS> *Q) {
-  static_assert(!(HITS && PIECE), "the piece route writes no hit lists");
   const int lane = threadIdx.x & 63;
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const ScanParams P = A.P;
@@ -868,6 +869,7 @@ __device__ __forceinline__ void segment_body(const FusedArgs &A, const PieceArgs
     const uint32_t room = clamp_room(bases_end - o - (exists ? w0 : 0));  // bytes from seq to the end of the caller's buffer
     uint2 *const prov = HITS ? (uint2 *)A.span_keys + o : nullptr;        // (unpaired: the fragment's span region starts at offsets[r])
     uint32_t lcount = 0;                                                   // spans of this lane so far
+    int32_t first_kmers = 0;                                               // (HITS && PIECE) k-mers of this lane's first entry
     if constexpr (HITS) { Q->delivered[lane] = 0; Q->flushed[lane] = 0; }
     // ---- wave state (as fused_kernel) ----
     int nbuf = 0, n_out = 0;
@@ -983,6 +985,7 @@ __device__ __forceinline__ void segment_body(const FusedArgs &A, const PieceArgs
             if (emit) put_span(L, slot, ekey, ekmers, 1, distinct);
             else put_span(L, slot, 0, amb_kmers, 2, false);
             if constexpr (HITS) Q->span_dst[slot] = ((uint32_t)lane << 26) | lcount;     // whose span, and its number there (a lane has fewer than 2^25 windows)
+            if constexpr (HITS && PIECE) first_kmers = lcount == 0 ? (emit ? ekmers : amb_kmers) : first_kmers;
             if (is_first && (PIECE || lane > 0)) first_slot = slot;   // (PIECE: lane 0's first super-mer follows another piece's last)
           }
           lcount += push ? 1u : 0u;
@@ -1087,6 +1090,26 @@ __device__ __forceinline__ void segment_body(const FusedArgs &A, const PieceArgs
     nd -= __popcll(__ballot(undo_distinct));
     n_out += (HITS ? 0 : wave_sum(namb)) - wave_sum(merged);   // (HITS: the ambiguous spans went through the buffer and are counted)
     total = wave_sum(total);
+    if constexpr (HITS && PIECE) {
+      // the hit lists' record: what each lane has in the provisional region, and the k-mers that leave the piece backwards if the
+      // border before it cuts its first entry -- lane 0's first entry then continues an earlier piece's last, and so does the first
+      // entry of every lane after it that merged into an entry that is not stored here (a lane whose first entry merged follows a
+      // lane that has an entry: without that cut every such entry has its place inside the piece)
+      seg_flush_queue<true>(Q, prov + w0, lane);              // what is left in the queues
+      const uint32_t cut = lane == 0 ? (lcount > 0 ? 1u : 0u) : (uint32_t)merged;
+      const uint32_t kept = lcount - cut;
+      uint32_t incl = kept;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+        if (lane >= d) incl += up;
+      }
+      const bool lane0_has = (__ballot(lcount > 0) & 1) != 0;
+      const int32_t head = wave_sum((lane0_has && cut && incl == kept) ? first_kmers : 0);
+      PieceHitRecord *const hr = X.hits + frag.unit0 + piece;
+      hr->lane[lane] = (lcount << 1) | (lane > 0 ? (uint32_t)merged : 0u);
+      if (lane == 0) hr->head_kmers = (uint32_t)head;
+    }
     if constexpr (PIECE) {
       // what the merge needs of this piece: the keys of its first and of its last super-mer (whichever lanes hold them), how its
       // last lane ended and how lane 0 began -- and its counts, provisional like a lane's until the borders between pieces are settled
@@ -1199,12 +1222,22 @@ __global__ void FUSED_BOUNDS piece_kernel(FusedArgs A, PieceArgs X) {
   const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   segment_body<false, true>(A, X, &lds[wib], &seg[wib], &hitq[wib]);
 }
+// ... and with hit lists (X.hits, A.span_keys): segment_kernel<true>'s LDS block, the queues included
+__global__ void FUSED_BOUNDS piece_hits_kernel(FusedArgs A, PieceArgs X) {
+  __shared__ WaveLds lds[FW];
+  __shared__ SegLds seg[FW];
+  __shared__ SegHitLds<true> hitq[FW];
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  segment_body<true, true>(A, X, &lds[wib], &seg[wib], &hitq[wib]);
+}
 
 void launch_pieces(const FusedArgs &A, const PieceArgs &X, hipStream_t s) {
   hipLaunchKernelGGL(piece_cut_kernel, dim3(256), dim3(256), 0, s, A, X);
   hipLaunchKernelGGL(piece_clear_kernel, dim3(1024), dim3(256), 0, s, X);
-  hipLaunchKernelGGL(piece_kernel, dim3(PIECE_GRID_BLOCKS), dim3(FW * 64), 0, s, A, X);
+  if (X.hits) hipLaunchKernelGGL(piece_hits_kernel, dim3(PIECE_GRID_BLOCKS), dim3(FW * 64), 0, s, A, X);
+  else hipLaunchKernelGGL(piece_kernel, dim3(PIECE_GRID_BLOCKS), dim3(FW * 64), 0, s, A, X);
   hipLaunchKernelGGL(piece_merge_kernel, dim3(512), dim3(FW * 64), 0, s, A, X);
+  if (X.hits) hipLaunchKernelGGL(piece_move_kernel, dim3(PIECE_GRID_BLOCKS), dim3(256), 0, s, A, X);
 }
 
 // over a hand-on list (A.work_list): unpaired, window width 5; A.span_taxon set: the hit lists too (A.span_keys is their scratch)

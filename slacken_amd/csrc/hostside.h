@@ -317,7 +317,8 @@ struct slk_stream {
   // the piece route (engine.h: PieceArgs): slk_stream_set_split_long, its scratch (header, slots, units, records | the HBM maps), and
   // whether the last classify call ran it (piece_scratch then starts with its header: slk_stream_last_split)
   int64_t split_long = -1;
-  DevBuf piece_scratch, piece_maps;
+  bool split_hits = false;       // slk_stream_set_split_hits: calls with hit lists take the route too (piece_hits: their side array)
+  DevBuf piece_scratch, piece_maps, piece_hits;
   bool last_used_pieces = false;
   bool split_reported = false;   // SLK_DEBUG_SPLIT: the last call's numbers have been printed (check_status)
   // The arguments of every classify call queued since the stream was last synchronised, for the unbounded re-run

@@ -11,7 +11,13 @@
 //   piece_merge_kernel  one wave per cut fragment: settles the borders BETWEEN pieces from the records with the rules the lanes of a
 //                       piece settle theirs with (fused.hip "the borders"), sums the counts and resolves from the HBM map -- up to 128
 //                       entries through the wave's LDS map and resolve_map as they are, more through the same interval arithmetic
-//                       (resolve_intervals) over the fragment's range
+//                       (resolve_intervals) over the fragment's range.  With hit lists (X.hits) it also writes the plan of the move
+//                       into the pieces' PieceHitRecords: where each piece's entries begin in the fragment's list, whether a border
+//                       cut its first entry, and the k-mers that later pieces' cut entries add to its last one
+//   piece_move_kernel   hit lists only, one wave per piece: the piece's entries from the provisional region (span_keys) to their final
+//                       places in span_taxon / span_meta, 64 consecutive places at a time.  It reads one buffer and writes another (a
+//                       piece's final places may lie in an earlier piece's provisional stretch), and no wave adds to an entry that
+//                       another wave stores: what crosses a border between pieces is in the plan's carry
 // The pieces' records and map entries reach the merge across the kernel boundary: no fence wider than a workgroup in any kernel.
 #pragma once
 #include "engine.h"
@@ -149,6 +155,12 @@ __global__ void __launch_bounds__(FW * 64) piece_merge_kernel(FusedArgs A, Piece
     uint32_t c_pflags = 0;                            // flags and last key of the piece right before this round's first
     uint64_t c_plast = 0;
     int32_t nd = 0, n_out = 0, total = 0, np = 0;
+    // (hit lists) the entries of the pieces so far; the last piece so far that stores an entry, and the k-mers its last entry gets from
+    // the pieces behind it -- written once the next such piece is known: an entry can be cut by many borders in a row, and a piece
+    // that holds nothing but the continuation of an earlier entry stores none and passes its k-mers on
+    uint32_t h_start = 0, h_carry = 0;
+    int64_t h_open = -1;
+    int32_t *const cr = L->result;
     for (uint32_t p0 = 0; p0 < frag.npieces; p0 += 64) {
       const uint32_t p = p0 + (uint32_t)lane;
       const bool in = p < frag.npieces;
@@ -172,6 +184,33 @@ __global__ void __launch_bounds__(FW * 64) piece_merge_kernel(FusedArgs A, Piece
           if ((fp & PIECEF_END_AMB) && (rec.flags & PIECEF_FIRST_AMB)) merged = 1;                             // one ambiguous span, cut
         }
       }
+      if (X.hits) {
+        PieceHitRecord *const hr = X.hits + frag.unit0 + p;           // (in: else unused)
+        const uint32_t own = in ? (uint32_t)(rec.n_out - merged) : 0u;
+        const uint32_t head = (in && merged) ? hr->head_kmers : 0u;
+        uint32_t incl = own;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+          const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+          if (lane >= d) incl += up;
+        }
+        cr[lane] = 0;
+        wave_sync();
+        const uint64_t NZ = __ballot(own > 0);
+        const uint64_t before = NZ & ((1ull << lane) - 1);
+        if (head != 0 && before != 0) atomicAdd(&cr[63 - __builtin_clzll(before)], (int32_t)head);
+        h_carry += (uint32_t)wave_sum((head != 0 && before == 0) ? (int32_t)head : 0);
+        wave_sync();
+        const int last_nz = NZ ? 63 - __builtin_clzll(NZ) : -1;
+        if (NZ != 0 && h_open >= 0 && lane == 0) X.hits[frag.unit0 + (uint64_t)h_open].carry = h_carry;
+        if (in) {
+          hr->start = h_start + incl - own;
+          hr->cut = (uint32_t)merged;
+          if (lane != last_nz) hr->carry = (uint32_t)cr[lane];
+        }
+        if (NZ != 0) { h_open = (int64_t)p0 + last_nz; h_carry = (uint32_t)cr[last_nz]; }
+        h_start += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      }
       nd += rec.nd - (undo_distinct ? 1 : 0);
       n_out += rec.n_out - merged;
       total += rec.total;
@@ -184,6 +223,10 @@ __global__ void __launch_bounds__(FW * 64) piece_merge_kernel(FusedArgs A, Piece
       wave_sync();
     }
     nd = wave_sum(nd); n_out = wave_sum(n_out); total = wave_sum(total); np = wave_sum(np);
+    if (X.hits && lane == 0) {
+      if (h_open >= 0) X.hits[frag.unit0 + (uint64_t)h_open].carry = h_carry;
+      A.span_count[r] = n_out;
+    }
 
     // ---- the map: dense in the front of its range (in place: an entry moves down, to slots that have been read) ----
     int32_t *const mk = X.map_key + frag.map0, *const mc = X.map_cnt + frag.map0;
@@ -222,6 +265,61 @@ __global__ void __launch_bounds__(FW * 64) piece_merge_kernel(FusedArgs A, Piece
       if (A.out_nh) A.out_nh[r] = n_out;
       if (A.out_np) A.out_np[r] = np;
     }
+    wave_sync();
+  }
+}
+
+// the lanes' ends in the piece's part of the list, and whether a lane's first entry is left out (it went into the entry before it)
+struct __attribute__((aligned(16))) MoveLds {
+  uint32_t end[64], skip[64];
+};
+__global__ void __launch_bounds__(256) piece_move_kernel(FusedArgs A, PieceArgs X) {
+  __shared__ MoveLds lds[4];
+  const int lane = threadIdx.x & 63;
+  const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  MoveLds *M = &lds[wib];
+  const uint64_t nunits = X.hdr[PieceHdr::FAILED] ? 0 : (uint64_t)X.hdr[PieceHdr::N_UNIT];
+  for (uint64_t unit = (uint64_t)blockIdx.x * 4 + wib; unit < nunits; unit += (uint64_t)gridDim.x * 4) {
+    const uint64_t u = X.units[unit];
+    const PieceFrag frag = X.frags[u >> 32];
+    const uint32_t piece = (uint32_t)u;
+    const uint64_t fo = A.offsets[frag.r];
+    const uint32_t w_first = piece * X.windows;
+    const uint32_t nwin = min(X.windows, (uint32_t)(A.offsets[frag.r + 1] - fo) - (uint32_t)A.P.k + 1 - w_first);
+    const uint32_t S = max(SEG_MIN_WINDOWS, (nwin + 63) / 64);          // (segment_body: lane j's stretch starts at j * S)
+    const PieceHitRecord *const hr = X.hits + frag.unit0 + piece;
+    const uint2 *const prov = (const uint2 *)A.span_keys + fo + w_first;
+    const uint64_t dst = fo + hr->start;
+    const uint32_t carry = hr->carry;
+    const uint32_t v = hr->lane[lane];
+    const uint32_t lcount = v >> 1;
+    const uint32_t skip = min(lcount, lane == 0 ? hr->cut : (v & 1u));
+    const uint32_t kept = lcount - skip;
+    uint32_t incl = kept;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint32_t up = (uint32_t)__shfl_up((int)incl, d);
+      if (lane >= d) incl += up;
+    }
+    const uint32_t off = incl - kept;
+    M->end[lane] = incl;
+    M->skip[lane] = skip;
+    wave_sync();
+    const uint32_t n_list = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    for (uint32_t t = lane; t < n_list; t += 64) {
+      int j = 0;
+#pragma unroll
+      for (int b = 32; b > 0; b >>= 1) j += (M->end[j + b - 1] <= t) ? b : 0;   // the first lane whose end lies beyond t
+      const uint32_t begin = j > 0 ? M->end[j - 1] : 0u;
+      uint2 e = prov[(uint64_t)j * S + M->skip[j] + (t - begin)];
+      if (t == n_list - 1) e.y += carry << 4;                                  // (engine.h pack_meta: k-mers << 4)
+      A.span_taxon[dst + t] = (int32_t)e.x;
+      A.span_meta[dst + t] = (int32_t)e.y;
+    }
+    // the entries cut by a border between two lanes of the piece: into the entry before them, which this wave has just stored (those
+    // whose entry before lies in an earlier piece -- off == 0 -- are in that piece's carry)
+    piece_range_sync();
+    if (skip && off > 0) atomicAdd(&A.span_meta[dst + off - 1], meta_kmers((int32_t)prov[(uint64_t)lane * S].y) << 4);
     wave_sync();
   }
 }

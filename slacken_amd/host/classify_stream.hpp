@@ -206,6 +206,7 @@ void classify_stream(DeviceIndex &dev, const std::vector<std::string> &files, bo
     if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
     SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merge ? 1 : 0));
     SLK_CALL(slk_stream_set_split_long(lanes[i].st, dev.split_long));
+    SLK_CALL(slk_stream_set_split_hits(lanes[i].st, dev.split_hits ? 1 : 0));
   }
   std::vector<std::thread> workers;
   for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&pass, &lanes, i] { pass.work(lanes[i]); });
@@ -214,6 +215,7 @@ void classify_stream(DeviceIndex &dev, const std::vector<std::string> &files, bo
   for (size_t i = 1; i < lanes.size(); i++) if (lanes[i].st) slk_stream_destroy(lanes[i].st);
   if (!dev.sharded) (void)slk_stream_set_merged_hits(dev.st, 0);   // (the device's own stream serves other callers: un-merged lists again)
   if (!dev.sharded) (void)slk_stream_set_split_long(dev.st, -1);
+  if (!dev.sharded) (void)slk_stream_set_split_hits(dev.st, 0);
   pass.order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING"))
     std::cerr << "host timing: " << pass.n_batches << " batches on " << n_workers << " classify thread(s) over " << dev.ixs.size() << " device table(s); summed over them: waiting for input "
@@ -439,6 +441,7 @@ void classify_text_stream(DeviceIndex &dev, const std::vector<std::string> &file
     if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
     SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merged_hits && want_hits ? 1 : 0));
     SLK_CALL(slk_stream_set_split_long(lanes[i].st, dev.split_long));
+    SLK_CALL(slk_stream_set_split_hits(lanes[i].st, dev.split_hits ? 1 : 0));
   }
   std::vector<std::thread> workers;
   for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&work, &lanes, i] { work(lanes[i]); });
@@ -447,6 +450,7 @@ void classify_text_stream(DeviceIndex &dev, const std::vector<std::string> &file
   for (size_t i = 1; i < lanes.size(); i++) slk_stream_destroy(lanes[i].st);
   (void)slk_stream_set_merged_hits(dev.st, 0);
   (void)slk_stream_set_split_long(dev.st, -1);
+  (void)slk_stream_set_split_hits(dev.st, 0);
   order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_batches << " chunks parsed on the device by " << lanes.size() << " classify thread(s)" << std::endl;
   std::cerr << total << " fragments" << std::endl;
@@ -698,6 +702,7 @@ void classify_paired_text_stream(DeviceIndex &dev, const std::vector<std::string
     if (i > 0) SLK_CALL(slk_stream_create(lanes[i].ix, &lanes[i].st));
     SLK_CALL(slk_stream_set_merged_hits(lanes[i].st, merged_hits && want_hits ? 1 : 0));
     SLK_CALL(slk_stream_set_split_long(lanes[i].st, dev.split_long));
+    SLK_CALL(slk_stream_set_split_hits(lanes[i].st, dev.split_hits ? 1 : 0));
   }
   std::vector<std::thread> workers;
   for (size_t i = 1; i < lanes.size(); i++) workers.emplace_back([&work, i] { work(i); });
@@ -706,6 +711,7 @@ void classify_paired_text_stream(DeviceIndex &dev, const std::vector<std::string
   for (size_t i = 1; i < lanes.size(); i++) slk_stream_destroy(lanes[i].st);
   (void)slk_stream_set_merged_hits(dev.st, 0);
   (void)slk_stream_set_split_long(dev.st, -1);
+  (void)slk_stream_set_split_hits(dev.st, 0);
   order.rethrow_failure();
   if (getenv("SLK_HOST_TIMING")) std::cerr << "host timing: " << n_calls << " paired calls on " << lanes.size() << " classify thread(s)" << std::endl;
   std::cerr << total << " fragments" << std::endl;

@@ -40,6 +40,7 @@ struct DeviceIndex {
   std::vector<slk_shardset *> sets;   // sharded: the rounds of several host threads overlap, each on a set (streams, buffers) of its own
   std::string last_error;             // of add_sequences
   int64_t split_long = -1;            // classify --split-long: what every classify worker's stream is told (slk_stream_set_split_long)
+  bool split_hits = false;            // classify --split-hits: likewise (slk_stream_set_split_hits)
   ~DeviceIndex() { reset(); }
   void reset() {
     for (slk_shardset *s : sets) slk_shardset_destroy(s);

@@ -234,6 +234,7 @@ struct ClassifyOpts {
   bool device_parse = false;    // --device-parse: the raw text goes to the device, which finds the records (classify_text_stream)
   bool device_pairs = false;    // --device-pairs: both mate files' text goes to the device, which finds and pairs the records (classify_paired_text_stream)
   long long split_long = -1;    // --split-long LEN: unpaired sequences of at least LEN bases are split over many waves (slk_stream_set_split_long)
+  bool split_hits = false;      // --split-hits: ... and so are they when per-read lines (hit lists) are written (slk_stream_set_split_hits)
   // classify2 (Slacken.scala:199-260)
   std::string library, rank = "species";
   int min_count = -1, min_distinct = -1, reads = -1;
@@ -276,6 +277,10 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
       o.split_long = std::stoll(a.next());
       if (o.split_long < 0) die("--split-long takes a number of bases (0: never split)");
     }
+    else if (a == "--split-hits") {
+      if (two_step) die("--split-hits is for classify (classify2 classifies reads against a small dynamic library: nothing there to split)");
+      o.split_hits = true;
+    }
     else if (two_step && (a == "-l" || a == "--library")) o.library = a.next();
     else if (two_step && a == "--rank") o.rank = a.next();
     else if (two_step && (a == "-C" || a == "--min-count")) o.min_count = std::stoi(a.next());
@@ -305,6 +310,7 @@ static ClassifyOpts parse_classify_opts(int argc, char **argv, bool two_step) {
   if (o.device_pairs && o.shard_table) die("--device-pairs needs the whole table on the device that parses (not --shard-table)");
   if (o.split_long >= 0 && o.paired) die("--split-long splits unpaired sequences (contigs, assemblies): not with -p");
   if (o.split_long >= 0 && o.shard_table) die("--split-long needs the whole table on the device that classifies (not --shard-table)");
+  if (o.split_hits && o.split_long <= 0) die("--split-hits extends --split-long LEN to runs that write per-read lines: give --split-long with LEN > 0");
   if (o.device_parse && o.paired) die("--device-parse takes unpaired input (the mates of paired reads are joined by title, on the host)");
   if (o.device_parse && o.shard_table) die("--device-parse needs the whole table on the device that parses (not --shard-table)");
   if (o.thresholds.empty()) o.thresholds.push_back(0.0);
@@ -375,10 +381,11 @@ static int cmd_classify(int argc, char **argv) {
     die("--device-pairs supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
   if (o.split_long >= 0 && read_index_params(o.index).m > 32)
     die("--split-long supports minimizers of up to 32 nt (this library has m=" + std::to_string(read_index_params(o.index).m) + ")");
-  if (o.split_long > 0 && o.detailed)
+  if (o.split_long > 0 && o.detailed && !o.split_hits)
     std::cerr << "note: --split-long has no effect on this run: per-read lines need hit lists, which keep the other routes (give --nodetailed)" << std::endl;
   LoadedIndex lib(o.index, o.devices, o.shard_table);
   lib.dev.split_long = o.split_long;
+  lib.dev.split_hits = o.split_hits;
   classify_and_write(lib.dev, lib.ip, lib.tax, o);
   return 0;
 }
@@ -1390,7 +1397,10 @@ static const char *HELP =
     "                         replicated table, m <= 32; `parse --device FILE` shows what the device finds); the default parses on the host\n"
     "      --split-long LEN   classify: split unpaired sequences of at least LEN bases (contigs, assemblies) over many waves of the\n"
     "                         device; the results do not change.  Takes effect where no per-read lines are written (--nodetailed:\n"
-    "                         those need hit lists, which keep the other routes); not with -p or --shard-table.  0: never\n"
+    "                         those need hit lists, which keep the other routes unless --split-hits is given); not with -p or\n"
+    "                         --shard-table.  0: never\n"
+    "      --split-hits       classify, with --split-long LEN (LEN > 0): split those sequences also where per-read lines are written --\n"
+    "                         their hit lists are put together from the pieces; the files do not change\n"
     "      --device-pairs     classify -p: send both mate files' text to the device, which finds the records and pairs them in lockstep\n"
     "                         (a replicated table, m <= 32); mates that are out of order end the run -- the default joins them on the host\n"
     "  FILES                  FASTA / FASTQ, plain, .gz or .bz2; @list.txt names a file of file names\n"

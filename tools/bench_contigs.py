@@ -22,6 +22,13 @@ labelled with a random taxon, and --many contigs of 300 kbp -- about 150 chunks 
 128-entry maps and is classified again by the staged kernels at the synchronisation, which the stream events do not see: the host
 clock is what counts there.
 
+--hits: the same batches WITH hit lists, through slk_classify_batch (host arrays in, lists out: the entry both libraries have), merged
+(slk_stream_set_merged_hits, what the command line uses) and un-merged, timed by the host clock around the call -- uploads, the list
+stages and the download of the lists are in it, on both sides alike.  This tree's library runs every batch with the threshold forced as
+above and slk_stream_set_split_hits off (the parent's routes) and on; the parent's library as it is.
+
+  python tools/bench_contigs.py --hits --parent-lib PATH/libslacken_amd.so --parent-label "parent commit SHA" > profiles/r17_contigs_hits.json
+
 Not part of bench.py; no test gates on these numbers."""
 import argparse
 import ctypes
@@ -162,6 +169,96 @@ def child(a):
     print(json.dumps(out), flush=True)
 
 
+def child_hits(a):
+    """--hits: one library, every batch with hit lists (module docstring)"""
+    has_route = a.lib is None
+    if not has_route:
+        os.environ["SLACKEN_AMD_LIB"] = a.lib
+        tolerate_older_library()
+    import torch
+    import slacken_amd
+    import taxgen
+    rng = np.random.default_rng(16)
+    G, L = a.genomes, int(a.length)
+    parents = taxgen.taxonomy(a.taxa, rng)
+    ls = (len(parents) - 2) // taxgen.N_RANKS
+    leaves = np.arange(7 * ls + 2, 8 * ls + 2, dtype=np.int32)
+    genomes = ACGT[rng.integers(0, 4, G * L, dtype=np.uint8)]
+    ix = slacken_amd.Index(expected_records=int(G * L * 0.45), max_taxon=len(parents) - 1, device=0)
+    ix.set_taxonomy(parents)
+    ix.add_sequences(genomes, np.arange(G + 1, dtype=np.uint64) * np.uint64(L), leaves[np.arange(G) % len(leaves)])
+    ix.finalize()
+    st = ix.stream()
+    if has_route:
+        st.set_split_long(FORCED)
+    out = {"library": a.label, "device": torch.cuda.get_device_name(0), "batches": {}}
+    switches = [("off", False), ("on", True)] if has_route else [("parent", None)]
+    for length in LENGTHS:
+        n = max(1, int(a.batch_bases) // length)
+        bases, offsets = cut_batch(genomes, G, L, n, length, rng)
+        total = int(offsets[-1])
+        res = {}
+        for lists in ("merged", "unmerged"):
+            st.set_merged_hits(lists == "merged")
+            for vname, on in switches:
+                if has_route:
+                    st.set_split_hits(on)
+                times, got = [], None
+                for i in range(a.reps + 1):          # a warm-up, then the runs
+                    t0 = time.perf_counter()
+                    got = st.classify_batch(bases, offsets, thresholds=(0.0, 0.1), min_hit_groups=2, with_hits=True)
+                    if i:
+                        times.append((time.perf_counter() - t0) * 1e3)
+                h = hashlib.sha1()
+                for key in ("taxon", "classified", "num_distinct", "total_kmers", "hit_offsets", "hits"):
+                    h.update(np.ascontiguousarray(got[key]).tobytes())
+                r = dict(fragments=n, bases=total, wall_ms=[round(t, 3) for t in times], gbp_per_s_wall=round(total / min(times) / 1e6, 2),
+                         digest=h.hexdigest(), entries=int(len(got["hits"])))
+                if has_route:
+                    r["last_split"] = list(st.last_split())
+                res[f"{vname}_{lists}"] = r
+                log(f"  {length} bases x {n}, {lists} lists, {vname}: {r['gbp_per_s_wall']} Gbp/s by the host clock {r['wall_ms']}, {r['entries']} entries")
+                del got
+        out["batches"][str(length)] = res
+    st.close()
+    print(json.dumps(out), flush=True)
+
+
+def main_hits(a, common):
+    runs = []
+    for rnd in range(a.rounds):
+        for lib in (os.path.abspath(a.parent_lib), None):
+            log(f"round {rnd}: {'parent' if lib else 'this tree'}")
+            p = subprocess.run(common + ["--hits"] + (["--lib", lib, "--label", a.parent_label] if lib else []), stdout=subprocess.PIPE,
+                               timeout=a.child_timeout, check=True)
+            runs.append(json.loads(p.stdout.decode().strip().splitlines()[-1]))
+    summary = {}
+    for name in runs[0]["batches"]:
+        row = {}
+        for lists in ("merged", "unmerged"):
+            per = {}
+            for r in runs:
+                for v, x in r["batches"][name].items():
+                    if v.endswith("_" + lists):
+                        per.setdefault(v[:-len(lists) - 1], []).append(x)
+            cell = dict(same_results=len({x["digest"] for xs in per.values() for x in xs}) == 1, entries=per["parent"][0]["entries"])
+            for v, xs in per.items():
+                allms = [t for x in xs for t in x["wall_ms"]]
+                cell[v] = dict(gbp_per_s=max(x["gbp_per_s_wall"] for x in xs), gbp_per_s_per_process=[x["gbp_per_s_wall"] for x in xs], ms_all_runs=allms,
+                               spread=round((max(allms) - min(allms)) / min(allms), 4))
+            cell["last_split"] = per["on"][0]["last_split"]
+            cell["on_over_parent"] = round(cell["on"]["gbp_per_s"] / cell["parent"]["gbp_per_s"], 3)
+            cell["off_over_parent"] = round(cell["off"]["gbp_per_s"] / cell["parent"]["gbp_per_s"], 3)
+            cell["beats_parent_beyond_spread"] = bool(min(cell["parent"]["ms_all_runs"]) > max(cell["on"]["ms_all_runs"]))
+            cell["slower_than_parent_beyond_spread"] = bool(max(cell["parent"]["ms_all_runs"]) < min(cell["on"]["ms_all_runs"]))
+            row[lists] = cell
+        row["fragments"], row["bases"] = runs[0]["batches"][name]["parent_merged"]["fragments"], runs[0]["batches"][name]["parent_merged"]["bases"]
+        summary[name] = row
+    print(json.dumps(dict(tool="tools/bench_contigs.py --hits", entry="slk_classify_batch, hit lists, host clock around the call", device=runs[0]["device"],
+                          genomes=a.genomes, genome_bases=int(a.length), taxonomy_size=a.taxa, batch_bases=int(a.batch_bases), piece_windows=PIECE_WINDOWS,
+                          forced_min_len=FORCED, reps=a.reps, rounds=a.rounds, batches=summary, processes=runs), indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", help="libslacken_amd.so of the parent commit")
@@ -172,6 +269,7 @@ def main():
     ap.add_argument("--many", type=int, default=64)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--hits", action="store_true", help="the batches with hit lists, merged and un-merged, slk_stream_set_split_hits off and on")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--lib")
     ap.add_argument("--label", default="this tree")
@@ -179,11 +277,13 @@ def main():
     ap.add_argument("--child-timeout", type=int, default=420)
     a = ap.parse_args()
     if a.child:
-        return child(a)
+        return child_hits(a) if a.hits else child(a)
     if not a.parent_lib or not os.path.exists(a.parent_lib):
         sys.exit("--parent-lib: the parent commit's libslacken_amd.so (build the parent and copy its library aside)")
     common = [sys.executable, os.path.abspath(__file__), "--child", "--genomes", str(a.genomes), "--length", str(a.length), "--batch-bases",
               str(a.batch_bases), "--many", str(a.many), "--reps", str(a.reps), "--taxa", str(a.taxa)]
+    if a.hits:
+        return main_hits(a, common)
     runs = []
     for rnd in range(a.rounds):
         for lib in (os.path.abspath(a.parent_lib), None):
