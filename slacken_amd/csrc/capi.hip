@@ -1,5 +1,5 @@
-// capi.hip -- what the C ABI declared in include/slacken_amd.h has beside its two halves (index.hip: the library side; classify.hip:
-// the classify side): error text, version, pinned host memory, the device count, and host arithmetic exported for tests.
+// capi.hip -- what the C ABI declared in include/slacken_amd.h has beside its two halves (index.hip: the library side; stream.hip,
+// classify.hip, shardstep.hip, hostcalls.hip: the classify side): error text, version, pinned host memory, the device count, and host arithmetic exported for tests.
 // There is NO CPU fallback: without a gfx950 device every compute entry point fails with SLK_E_NO_GPU / SLK_E_HIP.
 #include "hostside.h"
 #include "../host/pack.hpp"

@@ -1,5 +1,5 @@
-// hostside.h -- what the host-side translation units of the library share (index.hip / classify.hip / capi.hip: the C ABI of one
-// index / one stream; shardset.hip: the table-sharded set of indices): the handles' structures, error reporting, the staged copies
+// hostside.h -- what the host-side translation units of the library share (index.hip / stream.hip / classify.hip / hostcalls.hip /
+// capi.hip: the C ABI of one index / one stream; shardset.hip: the table-sharded set of indices): the handles' structures, error reporting, the staged copies
 // between caller memory and HBM.  Internal: not part of the C ABI.
 #pragma once
 #include "../../include/slacken_amd.h"
@@ -465,29 +465,38 @@ struct DrainOnExit {
   }
 };
 
-// defined in classify.hip, used by shardset.hip and bracken.hip too; not exported (the library exports its extern "C" names only)
+// What the host-side translation units share, by the file that defines it; not exported (the library exports its extern "C" names only)
 namespace slk {
+// stream.hip
+int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax);
 int32_t check_status(slk_stream *st);   // call after the stream has been synchronised
+int32_t fork_ready(slk_stream *st);     // st->s2 and the events that fork it from st->s and join it again
+// classify.hip: the dispatch
+bool use_fused(const slk_index *ix);
+bool lane_path_ok(const slk_index *ix);
 uint64_t span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired);
 int32_t ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R);
-int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax);
-bool lane_path_ok(const slk_index *ix);
+Thresholds thresholds_of(const double *v, int32_t C);
+FusedArgs fused_args(const slk_index *ix, const slk_stream *st, const Reads &in);
+void launch_spans(const slk_index *ix, slk_stream *st, const Reads &in, uint64_t *keys, int32_t *meta, int32_t *count);
+int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call);   // the kernels of a batch and the status word's copy, queued on st->s
+int32_t run_unbounded(slk_stream *st, const ClassifyCall &c);   // the batch again by the staged kernels (check_status); synchronises st->s
+// hostcalls.hip: the pieces of the host entries, which pipe.hip queues per slot and shardset.hip and bracken.hip use too
+int32_t validate_reads(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R);
 int32_t upload_reads(slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
                      const uint64_t *mate_offsets, uint64_t R, uint64_t *total, uint64_t *mate_total);
-int32_t counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets, uint64_t capacity);
-Thresholds thresholds_of(const double *v, int32_t C);
-int32_t ensure_outputs(slk_stream *st, uint64_t R, int32_t C);   // the stream's result rows (out_taxon .. out_nh) for R fragments
-struct HostRows { int32_t *taxon; uint8_t *classified; int32_t *nd, *tk; };   // a host call's results in the caller's memory (nullable from nd on)
-int32_t download_rows(slk_stream *st, const HostRows &out, uint64_t R, int32_t C);   // complete on return
-// the pieces of the host batch entry that pipe.hip queues per slot (classify.hip)
-int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call);   // the kernels of a batch and the status word's copy, queued on st->s
-int32_t validate_reads(const uint64_t *offsets, const uint64_t *mate_offsets, uint64_t R);
 int32_t size_host_buffers(slk_stream *st, uint64_t R, int32_t C, uint64_t total, uint64_t mate_total, bool paired, bool pk);
 int32_t upload_range(slk_stream *st, Staging *g, hipStream_t up, hipStream_t run, hipEvent_t ev, bool packed, const uint8_t *bases,
                      const uint32_t *codes, const uint16_t *valid, DevBuf &d_codes, DevBuf &d_valid, uint8_t *dst, uint64_t p0, uint64_t p1);
+ClassifyCall host_call(slk_stream *st, uint64_t R, uint64_t total, uint64_t mate_total, bool paired, const double *thresholds, int32_t C,
+                       int32_t min_hit_groups, bool want_hits, const uint64_t *h_offsets);
+int32_t ensure_outputs(slk_stream *st, uint64_t R, int32_t C);   // the stream's result rows (out_taxon .. out_nh) for R fragments
+struct HostRows { int32_t *taxon; uint8_t *classified; int32_t *nd, *tk; };   // a host call's results in the caller's memory (nullable from nd on)
+int32_t download_rows(slk_stream *st, const HostRows &out, uint64_t R, int32_t C);   // complete on return
+int32_t counts_to_offsets(slk_stream *st, const int32_t *d_counts, uint64_t R, uint64_t *out_offsets, uint64_t capacity);
 int32_t assemble_hits(slk_stream *st, const Reads &in, bool want_hits, uint64_t *out_hit_offsets, slk_hit *out_hits, uint64_t hits_capacity,
                       bool call_timing, double th[3]);
-// textparse.hip: FASTA / FASTQ text parsed on the device (used by classify.hip: slk_classify_text)
+// textparse.hip: FASTA / FASTQ text parsed on the device (used by hostcalls.hip: slk_classify_text)
 int32_t check_parse_args(uint64_t n, int32_t format);
 int32_t parse_uploaded(slk_stream *st, const uint8_t *text, uint64_t n, int32_t format, bool final, uint64_t bases_capacity,
                        uint64_t records_capacity, uint64_t counts[4]);

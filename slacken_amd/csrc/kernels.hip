@@ -532,7 +532,7 @@ __global__ void __launch_bounds__(256) merged_hits_kernel(const uint64_t *__rest
   }
 }
 
-// ---- launchers (called from index.hip and classify.hip) ----
+// ---- launchers (called from index.hip, classify.hip and hostcalls.hip) ----
 // slk_index_finalize, dense taxon ids: the taxon field of every cell becomes to_dense[taxon] (cells whose taxon has no dense
 // id -- not a node of the taxonomy -- are counted; the caller first counts, and rewrites only if there are none)
 __global__ void __launch_bounds__(256) remap_cells_kernel(uint64_t *__restrict__ cells, uint64_t ncells, int32_t taxon_bits,

@@ -89,7 +89,7 @@ __global__ void __launch_bounds__(256) piece_cut_kernel(FusedArgs A, PieceArgs X
     }
     bf = readlane64(bf, 0); bu = readlane64(bu, 0); bm = readlane64(bm, 0);
     if (bf + tot_f > X.frag_cap || bu + tot_u > X.unit_cap || bm + tot_m > X.map_cap) {
-      // (the host's bounds hold for every batch whose total_bases is true -- classify.hip plan_lane; where they do not, nothing is
+      // (the host's bounds hold for every batch whose total_bases is true -- laneplan.h plan_lane; where they do not, nothing is
       //  written past them, the passes behind the cut do nothing, and the call fails)
       if (lane == 0) {
         atomicExch(&X.hdr[PieceHdr::FAILED], 1ull);

@@ -1,9 +1,11 @@
 // pipe.hip -- slk_pipe (include/slacken_amd.h): batches in flight on the C ABI.  A pipe is `depth` slots; a slot is a whole
 // slk_stream -- streams, read and result buffers, span scratch, status word, the record of the queued call for the unbounded
 // re-run -- plus the scratch of the compact read forms (readform.hip) and pinned memory for the result rows.  slk_pipe_submit
-// queues one batch on a free slot's stream with the pieces the synchronous entry is made of (classify.hip: upload_range,
-// run_classify) and returns; slk_pipe_collect synchronises that slot alone and finishes the batch as classify_batch_host does
-// (check_status, assemble_hits).  No sub-batches inside a submit: the overlap comes from the slots.  Host-side only.
+// queues one batch on a free slot's stream with the pieces the synchronous entry is made of (hostcalls.hip: upload_range,
+// host_call; classify.hip: run_classify) and returns; slk_pipe_collect synchronises that slot alone and finishes the batch as
+// hostcalls.hip's finish_host_call does (check_status, assemble_hits), in a shape of its own: its rows lie in the slot's pinned
+// memory already, a failure gives the slot up, and SLK_E_CAPACITY from the hit lists leaves the ticket for a second collect.
+// No sub-batches inside a submit: the overlap comes from the slots.  Host-side only.
 #include "hostside.h"
 
 namespace {
@@ -214,7 +216,6 @@ int32_t slk_pipe_submit(slk_pipe *p, uint64_t R, const slk_reads *reads, const s
   const bool paired = mates != nullptr;
   sl.R = R; sl.C = C; sl.hits = hits; sl.in = Reads{};
   st->merged_hits = p->merged;
-  st->reran = false;
   const double t1 = call_timing ? wall_ms() : 0;
   if (R) {
     rc = size_host_buffers(st, R, C, f[0].total, f[1].total, paired, f[0].packed || f[1].packed);   // (each side in its own form)
@@ -222,12 +223,8 @@ int32_t slk_pipe_submit(slk_pipe *p, uint64_t R, const slk_reads *reads, const s
     if (!rc && paired) rc = size_side(sl, 1, *mates, f[1], R);
     if (rc) return rc;
     HIPCHK(sl.rows.ensure((size_t)C * R * 5 + R * 8));
-    ClassifyCall call;
-    call.in = {st->bases.as<uint8_t>(), st->offsets.as<uint64_t>(), paired ? st->mate_bases.as<uint8_t>() : nullptr,
-               paired ? st->mate_offsets.as<uint64_t>() : nullptr, R, f[0].total, f[1].total};
-    call.out = {st->out_taxon.as<int32_t>(), st->out_cls.as<uint8_t>(), st->out_nd.as<int32_t>(), st->out_tk.as<int32_t>(),
-                st->out_nh.as<int32_t>(), nullptr, R};
-    call.thr = thresholds_of(thresholds, C); call.C = C; call.min_hit_groups = min_hit_groups; call.want_hits = hits == 2;
+    // (no host offsets: a side may come as lengths or as one uniform length, and the piece route then plans from the totals)
+    const ClassifyCall call = host_call(st, R, f[0].total, f[1].total, paired, thresholds, C, min_hit_groups, hits == 2, nullptr);
     sl.in = call.in;
     // (from the first copy queued, a failure leaves nothing behind that reads the caller's memory)
     rc = queue_side(sl, 0, *reads, f[0], R, st->bases.as<uint8_t>(), st->pk_codes, st->pk_valid, st->offsets.as<uint64_t>());

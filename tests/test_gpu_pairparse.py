@@ -1,5 +1,5 @@
 """Two mate texts parsed and paired on the device (slacken_amd/csrc/textparse.hip: slk_parse_text_paired, slk_pair_device;
-classify.hip: slk_classify_text_paired) against the lockstep model (tests/pairparse_model.py) and the single-text device parser, which
+hostcalls.hip: slk_classify_text_paired) against the lockstep model (tests/pairparse_model.py) and the single-text device parser, which
 tests/test_gpu_textparse.py pins: R_i and consumed_i of every call are checked against st.parse_text_raw of each text alone and the
 opener positions its raw_title_pos gives."""
 import json
@@ -390,3 +390,23 @@ def test_classify_text_paired_equals_classify_batch(merged):
     assert got["titles"][j] == halves[j][0] and text1[got["consumed1"]:].startswith("@" + r1[j][0])
     s.close()
     ix.close()
+
+
+@pytest.mark.parametrize("with_hits", [False, True], ids=["rows", "hits"])
+def test_classify_text_paired_reruns_a_batch_whose_taxon_map_overflows(orc, with_hits):
+    """slk_classify_text_paired on texts with one pair of more than 128 distinct taxa: the batch is classified again by the unbounded
+    kernels (status bit 1) before its rows come down -- every pair against the oracle."""
+    import manytaxa
+    import synth
+    w = manytaxa.world(orc, 4300)
+    both = w["reads"]
+    reads, mates = [r[:len(r) // 2] for r in both], [r[len(r) // 2:] for r in both]     # each read's second half is its mate
+    bases, offsets = synth.pack(reads)
+    mb, mo = synth.pack(mates)
+    want = orc.classify_batch(w["p"], w["oix"], w["parents"], bases, offsets, mb, mo, thresholds=manytaxa.THR)
+    text1 = render("fastq", [(f"r{i}/1", r.tobytes().decode()) for i, r in enumerate(reads)])
+    text2 = render("fastq", [(f"r{i}/2", r.tobytes().decode()) for i, r in enumerate(mates)])
+    got = w["st"].classify_text_paired(text1.encode(), "fastq", True, text2.encode(), "fastq", True, thresholds=manytaxa.THR, with_hits=with_hits)
+    assert (got["P"], got["mismatch"]) == (len(reads), False)
+    assert np.array_equal(got["offsets"], offsets) and np.array_equal(got["mate_offsets"], mo)
+    manytaxa.check(orc, w, got, want, with_hits, reads, mates)

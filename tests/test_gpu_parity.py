@@ -730,3 +730,31 @@ def _grow_with_sequences(orc, rng):
     gk, gtx = ix.export()
     assert np.array_equal(gk, want_k) and np.array_equal(gtx, want_t)
     ix.close()
+
+
+@pytest.mark.parametrize("with_hits", [False, True], ids=["rows", "hits"])
+def test_unbounded_rerun_discards_rows_that_came_down_early(orc, with_hits):
+    """A host call cut into sub-batches whose result buffers are pinned brings each sub-batch's rows down beside the next one's
+    kernels.  One fragment with more than 128 distinct taxa has the whole call classified again when it is through (status bit 1):
+    the rows that came down early are stale then, and what the caller reads must be the re-run's -- every read against the oracle."""
+    import manytaxa
+    from slacken_amd import capi
+    w = manytaxa.world(orc, 4100)
+    reads, R = w["reads"], len(w["reads"])
+    bases, offsets = synth.pack(reads)
+    want = orc.classify_batch(w["p"], w["oix"], w["parents"], bases, offsets, thresholds=manytaxa.THR)
+    out = dict(taxon=capi.pinned_array((2, R), np.int32), classified=capi.pinned_array((2, R), np.uint8),
+               num_distinct=capi.pinned_array((R,), np.int32), total_kmers=capi.pinned_array((R,), np.int32))
+    old = os.environ.get("SLK_HOST_SUBBATCH")
+    os.environ["SLK_HOST_SUBBATCH"] = "64"     # five sub-batches, the long read in the second
+    try:
+        for a in out.values():
+            a[...] = -1 if a.dtype == np.int32 else 255
+        got = w["st"].classify_batch(bases, offsets, thresholds=manytaxa.THR, with_hits=with_hits, out=out)
+    finally:
+        if old is None:
+            os.environ.pop("SLK_HOST_SUBBATCH", None)
+        else:
+            os.environ["SLK_HOST_SUBBATCH"] = old
+    manytaxa.check(orc, w, dict(got, **out), want, with_hits, reads)
+    check_classify(orc, w, reads[:manytaxa.BIG], thresholds=(0.0,))     # the stream keeps working on ordinary batches

@@ -325,7 +325,7 @@ def test_hit_lists_of_long_reads_with_ambiguous_runs(orc, world, paired):
 def test_batches_of_mostly_long_fragments_have_no_first_pass(orc, world, monkeypatch, paired, with_hits):
     """A batch whose fragments average over 1000 bases is sorted by a routing kernel instead of a first pass of the lane kernel, and
     its fragments of up to 1000 bases -- empty ones, ones shorter than k, ones of exactly 1000 -- are a fifth class of the lane
-    kernel's long variant (classify.hip: route_first; engine.h: HandOn): the engine's default routes on such a batch, pairs too (a pair
+    kernel's long variant (laneplan.h: route_first; layouts.h: HandOn): the engine's default routes on such a batch, pairs too (a pair
     counts with both mates' bases), against the oracle, and the same with a first pass."""
     for v in ("SLK_SEG_MIN_LEN", "SLK_LANE_LONG_MAX", "SLK_SEG_HITS"):
         monkeypatch.delenv(v)

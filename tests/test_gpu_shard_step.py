@@ -384,7 +384,7 @@ def test_lookup_dealing(worlds):
     T = 6
     reads = synth.make_reads(W.lib, 64 * T - 3, rng, n_single=0.1)
     b = Batch(W, reads, None, 3)
-    # the limit of classify.hip: per_tile <= 3 * own + 8 with own = 2 / (w + 1) * bases / 64 / tiles
+    # the limit of laneplan.h (shard_side_per_tile): per_tile <= 3 * own + 8 with own = 2 / (w + 1) * bases / 64 / tiles
     own = 2.0 / (W.w + 1) * b.total / 64.0 / T
     most = int(3.0 * own + 8.0)
     rides = 5

@@ -292,3 +292,19 @@ def test_classify_text_equals_classify_batch(merged):
     assert got["R"] + rest["R"] == whole["R"] and np.array_equal(rest["taxon"], whole["taxon"][:, got["R"]:])
     s.close()
     ix.close()
+
+
+@pytest.mark.parametrize("with_hits", [False, True], ids=["rows", "hits"])
+def test_classify_text_reruns_a_batch_whose_taxon_map_overflows(orc, with_hits):
+    """slk_classify_text on a text with one record of more than 128 distinct taxa: the batch is classified again by the unbounded
+    kernels (status bit 1) before its rows come down -- every record against the oracle."""
+    import manytaxa
+    import synth
+    w = manytaxa.world(orc, 4200)
+    reads = w["reads"]
+    bases, offsets = synth.pack(reads)
+    want = orc.classify_batch(w["p"], w["oix"], w["parents"], bases, offsets, thresholds=manytaxa.THR)
+    text = "".join(f"@r{i}\n{r.tobytes().decode()}\n+\n{'I' * len(r)}\n" for i, r in enumerate(reads))
+    got = w["st"].classify_text(text.encode(), "fastq", thresholds=manytaxa.THR, with_hits=with_hits)
+    assert got["R"] == len(reads) and got["consumed"] == len(text) and np.array_equal(got["offsets"], offsets)
+    manytaxa.check(orc, w, got, want, with_hits, reads)
