@@ -632,6 +632,9 @@ int32_t slk_shardset_classify(slk_shardset *set, slk_shard_batch *batches /* [n_
 int32_t slk_shardset_classify_rounds(slk_shardset *set, slk_shard_batch *batches /* [n_rounds][n_members] */, int32_t n_rounds,
                                      int32_t device_resident, int32_t min_hit_groups, const double *thresholds, int32_t C);
 int32_t slk_shardset_exchange_mode(const slk_shardset *set); /* SLK_EXCHANGE_RCCL or SLK_EXCHANGE_COPY: what AUTO chose */
+/* The ordered pairs (a, b), a != b, of members whose copies are staged through pinned host memory: b's device cannot reach the memory
+ * of a's (hipDeviceCanAccessPeer), or SLK_SHARDSET_NO_PEER=1 was set when the set was created.  0 with SLK_EXCHANGE_RCCL. */
+int32_t slk_shardset_staged_pairs(const slk_shardset *set);
 void slk_shardset_destroy(slk_shardset *set);
 
 /* Per-stage device timing of the last slk_classify_batch_device call on st, in milliseconds (HIP events on the

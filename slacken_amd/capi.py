@@ -84,7 +84,7 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
            "slk_shard_of", "slk_stream_set_merged_hits", "slk_classify_hits_device", "slk_shard_batch_rows", "slk_shard_chunk", "slk_shard_step_device",
            "slk_stream_last_deferred", "slk_table_slot", "slk_table_hash_of",
-           "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy",
+           "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_staged_pairs", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy",
            "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy",
            "slk_coverage_create", "slk_coverage_add", "slk_coverage_fold", "slk_coverage_result", "slk_coverage_totals", "slk_coverage_budget",
            "slk_coverage_destroy",
@@ -159,6 +159,7 @@ def lib():
     L.slk_shardset_classify.argtypes = [vp, C.POINTER(_ShardBatch), C.c_int32, C.POINTER(C.c_double), C.c_int32]
     L.slk_shardset_classify_rounds.argtypes = [vp, C.POINTER(_ShardBatch), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32]
     L.slk_shardset_exchange_mode.argtypes = [vp]
+    L.slk_shardset_staged_pairs.argtypes = [vp]
     L.slk_shardset_destroy.argtypes = [vp]
     L.slk_shardset_destroy.restype = None
     L.slk_index_set_shard.argtypes = [vp, C.c_uint32, C.c_uint32]
@@ -662,6 +663,11 @@ class ShardSet:
     def exchange_mode(self):
         return int(lib().slk_shardset_exchange_mode(self.h))
 
+    @property
+    def staged_pairs(self):
+        """ordered pairs of members whose copies go through pinned host memory (slk_shardset_staged_pairs)"""
+        return int(lib().slk_shardset_staged_pairs(self.h))
+
     def classify(self, batches, min_hit_groups=2, thresholds=(0.0,), with_hits=True):
         """One round: batches[g] = (bases, offsets) or (bases, offsets, mate_bases, mate_offsets) or None for member g.
         -> list of result dicts as Stream.classify_batch returns them (None for members without a batch)."""
@@ -717,21 +723,27 @@ class ShardSet:
                 if b is None:
                     continue
                 arr[r * n + g] = _ShardBatch(b["bases"], b["offsets"], b.get("mate_bases"), b.get("mate_offsets"), b["R"], b["out_taxon"],
-                                             b["out_classified"], b.get("out_num_distinct"), b.get("out_total_kmers"), None, None, 0)
+                                             b["out_classified"], b.get("out_num_distinct"), b.get("out_total_kmers"),
+                                             b.get("out_hit_offsets"), b.get("out_hits"), 0)   # (hit lists: refused, SLK_E_UNSUPPORTED)
         _check(lib().slk_shardset_classify_rounds(self.h, arr, len(rounds), 1, min_hit_groups, thr, Cn))
 
-    def classify_rounds(self, rounds, min_hit_groups=2, thresholds=(0.0,), with_hits=True):
+    def classify_rounds(self, rounds, min_hit_groups=2, thresholds=(0.0,), with_hits=True, hits_capacity=None):
         """Several rounds of classify() in ONE pipelined call (slk_shardset_classify_rounds, host pointers): rounds[r][g] as
-        classify()'s batches[g].  -> list (per round) of lists (per member) of result dicts."""
+        classify()'s batches[g].  with_hits: one bool for the call, or a [rounds][members] matrix of bools (a batch asks for its
+        hit lists or not).  hits_capacity: None, or a [rounds][members] matrix of entry counts (None: what the batch can need at
+        most).  -> list (per round) of lists (per member) of result dicts."""
         n = len(self.members)
         Cn = len(thresholds)
         thr = (C.c_double * Cn)(*thresholds)
         arr = (_ShardBatch * (n * len(rounds)))()
         keep, outs = [], []
+        want = with_hits if isinstance(with_hits, (list, tuple)) else [[bool(with_hits)] * n for _ in rounds]
+        assert len(want) == len(rounds) and all(len(w) == n for w in want)
         for r, rnd in enumerate(rounds):
             assert len(rnd) == n
             row = []
             for g, b in enumerate(rnd):
+                with_hits = bool(want[r][g])
                 if b is None:
                     row.append(None)
                     continue
@@ -746,7 +758,9 @@ class ShardSet:
                 cap = 0
                 if with_hits:
                     cap = int(bases.size + (mb.size + R if mb is not None else 0)) + 1
-                    hit_off, hits = np.zeros(R + 1, np.uint64), np.zeros(cap, HIT_DTYPE)
+                    if hits_capacity is not None and hits_capacity[r][g] is not None:
+                        cap = int(hits_capacity[r][g])
+                    hit_off, hits = np.zeros(R + 1, np.uint64), np.zeros(max(cap, 1), HIT_DTYPE)
                 keep.append((bases, offsets, mb, mo, hit_off, hits))
                 arr[r * n + g] = _ShardBatch(_ptr(bases), _ptr(offsets), _ptr(mb), _ptr(mo), R, _ptr(o["taxon"]), _ptr(o["classified"]),
                                              _ptr(o["num_distinct"]), _ptr(o["total_kmers"]), _ptr(hit_off), _ptr(hits), cap)

@@ -136,6 +136,10 @@ struct Member {
   Event ev_sent, ev_found, ev_bounce;
   PinnedPtr<void> h_bounce;         // pinned: copies to devices that cannot reach this one's memory
   size_t bounce_cap = 0;
+  bool bounce_written = false;      // ev_bounce has been recorded: behind it the last copy INTO h_bounce
+  // ev_read[a] (made at the first such copy): THIS member's last copy OUT of member a's bounce buffer has finished.  Recorded on
+  // whichever stream of this member the exchange ran on; a waits for it before it writes into its buffer again or frees it.
+  std::vector<Event> ev_read;
 };
 
 }  // namespace
@@ -188,6 +192,32 @@ int32_t exchange(slk_shardset *set, const std::vector<const void *> &src, const 
     if (e || e2) return fail(SLK_E_HIP, "RCCL exchange failed: %s", rccl().GetErrorString(e ? e : e2));
     return SLK_OK;
   }
+  // The senders whose copies are staged through their pinned bounce buffer (no peer access to a destination).  The buffer is a's, with
+  // a region per destination laid out by THIS exchange's sizes -- so a region written now may overlap one that ANOTHER destination
+  // read in an earlier exchange, which may have run on other streams (staged_lookup: the compute streams; the pipeline: xs), and a
+  // member that sent or received nothing in between has ordered nothing.  Hence, explicitly: before a writes into its buffer, its
+  // stream waits for every destination's last copy out of it (Member::ev_read); before the buffer is replaced by a larger one, the
+  // host waits for them, and for a's own last copy into it.
+  for (int a = 0; a < W; a++) {
+    Member &ma = set->m[a];
+    uint64_t row = 0;
+    bool staged = false;
+    for (int d = 0; d < W; d++) { row += n[a][d]; staged = staged || (n[a][d] && !set->peer[d][a]); }
+    if (!staged) continue;
+    int32_t rc = use(ma);
+    if (rc) return rc;
+    if (row * esz > ma.bounce_cap) {
+      HIPCHK(hipStreamSynchronize(str[a]));
+      if (ma.bounce_written) HIPCHK(hipEventSynchronize(ma.ev_bounce));
+      for (int d = 0; d < W; d++)
+        if (set->m[d].ev_read[a]) HIPCHK(hipEventSynchronize(set->m[d].ev_read[a]));
+      ma.bounce_cap = 0;
+      HIPCHK(hipHostMalloc(ma.h_bounce.put(), row * esz + row * esz / 4 + 4096, hipHostMallocPortable));
+      ma.bounce_cap = row * esz + row * esz / 4 + 4096;
+    }
+    for (int d = 0; d < W; d++)
+      if (set->m[d].ev_read[a]) HIPCHK(hipStreamWaitEvent(str[a], set->m[d].ev_read[a], 0));
+  }
   for (int b = 0; b < W; b++) {
     for (int a = 0; a < W; a++) {
       if (!n[a][b]) continue;
@@ -200,26 +230,22 @@ int32_t exchange(slk_shardset *set, const std::vector<const void *> &src, const 
         HIPCHK(hipStreamWaitEvent(str[b], ev[a], 0));
         HIPCHK(hipMemcpyAsync(to, from, bytes, hipMemcpyDefault, str[b]));
       } else {
-        // no peer access between the two devices: down to a's pinned bounce buffer on a's stream, up from there on b's.  (The
-        // buffer is a's; a region per destination, so that the pairs of one exchange do not wait for each other.)
-        Member &ma = set->m[a];
+        // down to a's bounce buffer on a's stream, up from there on b's (a region per destination, so that the pairs of one
+        // exchange do not wait for each other)
+        Member &ma = set->m[a], &mb = set->m[b];
         int32_t rc = use(ma);
         if (rc) return rc;
-        uint64_t row = 0, off = 0;
-        for (int d = 0; d < W; d++) { if (d == b) off = row; row += n[a][d]; }
-        if (row * esz > ma.bounce_cap) {
-          HIPCHK(hipStreamSynchronize(str[a]));   // (the copies still using the old buffer)
-          ma.bounce_cap = 0;
-          HIPCHK(hipHostMalloc(ma.h_bounce.put(), row * esz + row * esz / 4 + 4096, hipHostMallocPortable));
-          ma.bounce_cap = row * esz + row * esz / 4 + 4096;
-        }
-        HIPCHK(hipStreamWaitEvent(str[a], ev[a], 0));
+        uint64_t off = 0;
+        for (int d = 0; d < b; d++) off += n[a][d];
         HIPCHK(hipMemcpyAsync((char *)ma.h_bounce.get() + off * esz, from, bytes, hipMemcpyDeviceToHost, str[a]));
         HIPCHK(hipEventRecord(ma.ev_bounce, str[a]));
-        rc = use(set->m[b]);
+        ma.bounce_written = true;
+        rc = use(mb);
         if (rc) return rc;
         HIPCHK(hipStreamWaitEvent(str[b], ma.ev_bounce, 0));
         HIPCHK(hipMemcpyAsync(to, (const char *)ma.h_bounce.get() + off * esz, bytes, hipMemcpyHostToDevice, str[b]));
+        if (!mb.ev_read[a]) HIPCHK(hipEventCreateWithFlags(mb.ev_read[a].put(), hipEventDisableTiming));
+        HIPCHK(hipEventRecord(mb.ev_read[a], str[b]));
       }
     }
   }
@@ -436,7 +462,12 @@ uint64_t region_capacity(const slk_index *ix, uint64_t bases, uint64_t R, int W)
   uint64_t cap = (uint64_t)(expect / W * 1.2) + 4096 + (uint64_t)chunk * std::min<uint64_t>(tiles, 8192);
   cap = (cap + chunk - 1) / chunk * chunk;
   const uint64_t limit = ((1ull << 32) - 1) / chunk * chunk - chunk;
-  return std::min(cap, limit);
+  cap = std::min(cap, limit);
+  // SLK_SHARDSET_REGION_CAP: at most this many entries (whole chunks, at least one), read at every call -- so that a test can get to
+  // the route of a region that overflows in mid-pipeline; no result depends on it
+  const long forced = env_long("SLK_SHARDSET_REGION_CAP", 0);
+  if (forced > 0) cap = std::min(cap, std::max<uint64_t>((uint64_t)forced / chunk, 1) * chunk);
+  return cap;
 }
 
 struct Pipe {
@@ -631,10 +662,10 @@ int32_t exchange_after_step(Pipe &P, int t, std::vector<std::vector<uint64_t>> &
       bool over = false;
       for (int d = 0; d < W; d++) over = over || sl.h_cursors[d] > sl.lists.capacity_per_owner;
       if (over) {   // a region was too small: nothing of this batch travels; all of it takes the staged route
+        // (The status word keeps the EMIT's capacity bit until the call's end, where it is masked and the word cleared behind the
+        //  last step: the next step's kernel is queued on the compute stream already, and a clear from here would race with its
+        //  bits and with its copy of the word.)
         sl.failed = true;
-        mb.st->queued.clear();
-        *mb.st->h_status = 0;
-        HIPCHK(hipMemsetAsync(mb.st->d_status, 0, sizeof(int32_t), mb.xs));
         continue;
       }
       for (int d = 0; d < W; d++) sent[r][g][d] = sl.h_cursors[d];
@@ -878,8 +909,25 @@ int32_t finish_deferred(Pipe &P, int r) {
   return SLK_OK;
 }
 
+// What DrainOnExit is to a host entry of one stream: no return of a call -- a failing one in mid-pipeline least of all, with steps,
+// exchanges and uploads queued on slots the next call takes again -- leaves work behind on any member's streams.
+struct DrainSetOnExit {
+  slk_shardset *set;
+  explicit DrainSetOnExit(slk_shardset *set_) : set(set_) {}
+  DrainSetOnExit(const DrainSetOnExit &) = delete;
+  ~DrainSetOnExit() {
+    for (Member &mb : set->m) {
+      if (hipSetDevice(mb.device) != hipSuccess) { (void)hipGetLastError(); continue; }
+      for (hipStream_t s : {mb.us.get(), mb.st->s.get(), mb.xs.get(), mb.ds.get()})
+        if (s && hipStreamSynchronize(s) != hipSuccess) (void)hipGetLastError();
+      mb.st->queued.clear();
+    }
+  }
+};
+
 int32_t run_rounds(slk_shardset *set, slk_shard_batch *batches, int rounds, bool on_device, int32_t min_hit_groups, const double *thresholds, int32_t C) {
   const int W = set->n;
+  DrainSetOnExit drain(set);
   Pipe P{set, batches, rounds, on_device, min_hit_groups, C, thresholds, W, {}};
   P.deferred.assign((size_t)rounds * W, {});
   bool fast = true;
@@ -991,6 +1039,7 @@ int32_t slk_shardset_create(slk_index *const *members, int32_t n_members, int32_
     Member &mb = set->m[g];
     mb.ix = members[g];
     mb.device = members[g]->device;
+    mb.ev_read.resize(n_members);
     int32_t rc = slk_stream_create(mb.ix, &mb.st);
     if (rc) { cleanup(); return rc; }
     bool ok = hipHostMalloc((void **)mb.h_counts.put(), ((size_t)n_members + 3) * 8, hipHostMallocDefault) == hipSuccess &&
@@ -1016,9 +1065,16 @@ int32_t slk_shardset_create(slk_index *const *members, int32_t n_members, int32_
   }
   // Which members' devices reach each other's memory.  Copies between two that do not are staged through pinned host memory (said
   // once, here, with the reason) instead of failing in the first round.
+  // SLK_SHARDSET_NO_PEER=1 (read at every create; copy mode): no member reaches another's memory, members on one device included --
+  // every copy between two members takes the host-staged leg, so that a test can get there on any machine.  No result depends on it.
+  const bool no_peer = mode == SLK_EXCHANGE_COPY && n_members > 1 && env_long("SLK_SHARDSET_NO_PEER", 0) == 1;
+  if (no_peer)
+    fprintf(stderr, "[slacken_amd] shard set: SLK_SHARDSET_NO_PEER=1: peer access is taken as absent (forced, not probed): every copy "
+                    "between two of the %d members is staged through pinned host memory\n", n_members);
   for (int a = 0; a < n_members; a++)
     for (int b = 0; b < n_members; b++) {
       const int da = set->m[a].device, db = set->m[b].device;
+      if (no_peer) { set->peer[a][b] = (char)(a == b); continue; }
       if (da == db) continue;
       int can = 0;
       if (hipDeviceCanAccessPeer(&can, da, db) != hipSuccess) { (void)hipGetLastError(); can = 0; }
@@ -1048,6 +1104,15 @@ int32_t slk_shardset_create(slk_index *const *members, int32_t n_members, int32_
 
 int32_t slk_shardset_exchange_mode(const slk_shardset *set) { return set ? set->mode : SLK_E_INVALID; }
 
+int32_t slk_shardset_staged_pairs(const slk_shardset *set) {
+  if (!set) return SLK_E_INVALID;
+  if (set->mode != SLK_EXCHANGE_COPY) return 0;
+  int32_t pairs = 0;
+  for (int a = 0; a < set->n; a++)
+    for (int b = 0; b < set->n; b++) pairs += a != b && !set->peer[b][a];   // (as exchange() asks: the receiver b reaches a's memory)
+  return pairs;
+}
+
 int32_t slk_shardset_classify(slk_shardset *set, slk_shard_batch *batches, int32_t min_hit_groups, const double *thresholds, int32_t C) {
   int32_t rc = check_batches(set, batches, 1, false, thresholds, C);
   if (rc) return rc;
@@ -1063,6 +1128,11 @@ int32_t slk_shardset_classify_rounds(slk_shardset *set, slk_shard_batch *batches
 
 void slk_shardset_destroy(slk_shardset *set) {
   if (!set) return;
+  for (Member &mb : set->m) {   // (a member's bounce buffer is read on the OTHERS' streams: nothing goes before all of them are idle)
+    (void)hipSetDevice(mb.device);
+    for (hipStream_t s : {mb.st ? mb.st->s.get() : nullptr, mb.xs.get()})
+      if (s) (void)hipStreamSynchronize(s);
+  }
   for (Member &mb : set->m) {
     (void)hipSetDevice(mb.device);   // (the member's own copy: its index may be gone already)
     if (mb.st) (void)hipStreamSynchronize(mb.st->s);

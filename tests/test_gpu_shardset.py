@@ -12,11 +12,31 @@ import taxgen
 pytestmark = pytest.mark.gpu
 
 
-def make_members(lib, parents, n, **kw):
+NO_PEER = pytest.mark.parametrize("no_peer", [False, True], ids=["peer", "no_peer"])
+
+
+def set_no_peer(monkeypatch, no_peer):
+    """SLK_SHARDSET_NO_PEER (read by slk_shardset_create): every copy between two members through the pinned bounce buffer"""
+    if no_peer:
+        monkeypatch.setenv("SLK_SHARDSET_NO_PEER", "1")
+    else:
+        monkeypatch.delenv("SLK_SHARDSET_NO_PEER", raising=False)
+
+
+def staged_as_asked(sset, no_peer):
+    """members on ONE device: every ordered pair is staged through the host with the switch, none without; copies either way"""
+    from slacken_amd import capi
+    n = len(sset.members)
+    assert sset.exchange_mode == capi.EXCHANGE_COPY
+    assert sset.staged_pairs == (n * (n - 1) if no_peer else 0)
+
+
+def make_members(lib, parents, n, devices=None, **kw):
     import slacken_amd
     members = []
     for g in range(n):
-        ix = slacken_amd.Index(expected_records=max(len(lib.keys) // n * 2, 64), max_taxon=len(parents) - 1, **kw)
+        ix = slacken_amd.Index(expected_records=max(len(lib.keys) // n * 2, 64), max_taxon=len(parents) - 1,
+                               device=devices[g] if devices else 0, **kw)
         ix.set_shard(g, n)
         ix.set_taxonomy(parents)
         for a in range(0, len(lib.keys), 7001):       # the whole record stream, in chunks, to every member
@@ -52,8 +72,10 @@ def world(orc):
     return dict(p=p, parents=parents, lib=lib, oix=orc.Index(1, lib.keys, lib.taxa), rng=rng)
 
 
+@NO_PEER
 @pytest.mark.parametrize("n", [2, 3])
-def test_rounds_equal_the_oracle_and_the_replicated_mode(orc, world, n):
+def test_rounds_equal_the_oracle_and_the_replicated_mode(orc, world, n, no_peer, monkeypatch):
+    set_no_peer(monkeypatch, no_peer)
     import slacken_amd
     from slacken_amd import capi
     lib, parents, p, rng = world["lib"], world["parents"], world["p"], world["rng"]
@@ -67,6 +89,7 @@ def test_rounds_equal_the_oracle_and_the_replicated_mode(orc, world, n):
         assert np.isin(lib.keys[:2000][mine], k).all() and not np.isin(lib.keys[:2000][~mine], k).any()
     sset = capi.ShardSet(members)
     assert sset.exchange_mode == capi.EXCHANGE_COPY          # (all members on device 0)
+    staged_as_asked(sset, no_peer)
     whole = slacken_amd.Index(expected_records=len(lib.keys), max_taxon=len(parents) - 1)
     whole.append(lib.keys, lib.taxa)
     whole.set_taxonomy(parents)
@@ -107,13 +130,16 @@ def test_rounds_equal_the_oracle_and_the_replicated_mode(orc, world, n):
     sset.close()
 
 
-def test_paired_rounds_and_many_taxa(orc, world):
+@NO_PEER
+def test_paired_rounds_and_many_taxa(orc, world, no_peer, monkeypatch):
     """pairs (the mate border's pseudo-span in the hit lists) and fragments with more than 12 distinct taxa (handed back by the
     lane kernel: staged round) through a set of two"""
     from slacken_amd import capi
+    set_no_peer(monkeypatch, no_peer)
     lib, parents, p, rng = world["lib"], world["parents"], world["p"], world["rng"]
     members = make_members(lib, parents, 2)
     sset = capi.ShardSet(members, exchange=capi.EXCHANGE_COPY)
+    staged_as_asked(sset, no_peer)
     thr = (0.0, 0.15)
     batches, wants, pairs = [], [], []
     for g in range(2):
@@ -141,6 +167,7 @@ def test_paired_rounds_and_many_taxa(orc, world):
     l2.keys, l2.taxa = keys, tx
     members = make_members(l2, parents, 2)
     sset = capi.ShardSet(members)
+    staged_as_asked(sset, no_peer)
     bases, offsets = synth.pack(reads)
     half = len(reads) // 2
     b0, o0 = synth.pack(reads[:half])
@@ -221,11 +248,14 @@ def test_rccl_leg_runs_with_one_member(tmp_path):
     assert p.returncode == 0 and "RCCL-OK" in p.stdout, p.stderr[-3000:]
 
 
-def test_splitter_outside_the_lane_kernels_range_takes_the_staged_round(orc):
+@NO_PEER
+def test_splitter_outside_the_lane_kernels_range_takes_the_staged_round(orc, no_peer, monkeypatch):
     """A window of 40 m-mers (k = 70, m = 31): neither the lane kernel nor the wave kernel take it -- every fragment of every member
-    goes through the staged round (scan kernel, keys collected by owner, exchange, unbounded classify kernel)."""
+    goes through the staged round (scan kernel, keys collected by owner, exchange, unbounded classify kernel).  With the switch the
+    exchange of that round -- on the COMPUTE streams -- takes the host-staged leg."""
     import slacken_amd
     from slacken_amd import capi
+    set_no_peer(monkeypatch, no_peer)
     rng = np.random.default_rng(21)
     parents = taxgen.taxonomy(8 * 16, rng)
     p = orc.params(k=70, m=31, spaces=5)
@@ -239,6 +269,7 @@ def test_splitter_outside_the_lane_kernels_range_takes_the_staged_round(orc):
         ix.finalize()
         members.append(ix)
     sset = capi.ShardSet(members)
+    staged_as_asked(sset, no_peer)
     oix = orc.Index(1, lib.keys, lib.taxa)
     batches, wants, all_reads = [], [], []
     for g in range(2):
