@@ -866,6 +866,58 @@ int32_t slk_mask_sequences(slk_stream *st, uint8_t *bases, const uint64_t *offse
 int32_t slk_index_add_sequences_masked(slk_index *ix, slk_stream *st, const uint8_t *bases, const uint64_t *offsets, const int32_t *taxa,
                                        uint64_t n_sequences, const slk_mask_config *cfg /* nullable */, uint64_t *out_masked);
 
+/* ---- classifications joined with a truth mapping (compare.hip): the join of `compare` (S/slacken/Slacken.scala:343-366,
+ * S/slacken/analysis/MappingComparison.scala), on the bytes of the read ids.  The rows of a reference mapping stay resident on the
+ * device; the per-read output of `classify` streams through and every row whose id equals a kept reference id is counted under
+ * (reference taxon, test taxon).  The taxonomy stays with the caller: taxa go in and come out RAW, as the texts have them, and the
+ * caller applies primary(), isDefined and the rank arithmetic to the distinct pairs.
+ * Text: lines end with \n, \r\n or a lone \r; empty lines are skipped; fields are split at TAB only, quotes mean nothing.  A line
+ * with fewer columns than asked for, an empty id or taxon field, or a taxon that Java's Integer.parseInt refuses ("+7" is 7) or that
+ * is negative is a bad line.  Chunks follow the parser's contract: n < 2^32; with final = 0 a line counts only when its terminator
+ * lies inside the chunk (a \r on the last byte is undecided); *consumed is the start of the first undecided line, where the next
+ * chunk starts; *consumed == 0 with final = 0 and n > 0 means the chunk must grow.  Results do not depend on how a text was cut.
+ *   slk_compare_create         an empty handle on the device of st; the stream's index is only its owner, as for slk_mask_*.
+ *                              SLK_COMPARE_HASH_BITS=N (environment, read here) truncates the ids' hash to N bits (tests).
+ *   slk_compare_add_reference  replaces readCustomFormat (:265-274) and the build side of the join: id_col and taxon_col count from 1;
+ *                              a row whose id holds "/2" is dropped, every "/1" is removed from the others' ids, and the row is
+ *                              kept.  Host text, synchronous; _device takes device text, aligned to 16 bytes (synchronous too: the
+ *                              table, the arena of id bytes and the count maps are sized from the chunk's lines and grow by themselves).
+ *   slk_compare_begin_test     a new test location: clears the pairs, the "matched" flags and the test totals; the reference stays.
+ *   slk_compare_add_test       replaces readKrakenFormat (:259-263) and the join (:157-159, :216-217): columns 2 and 3, the id as it is.
+ *   slk_compare_pairs          the distinct (reference taxon, test taxon) of the joined rows of the current test with their rows,
+ *                              ascending (what hitCategory :313-331 and the per-taxon sets :170-209 are computed from).  *n = their
+ *                              number; cap 0 queries only that, 0 < cap < *n gives SLK_E_CAPACITY (the first cap rows are written),
+ *                              as slk_support_result.
+ *   slk_compare_reference_taxa the kept reference rows per raw taxon, ascending (the isDefined filter :130-131 and refTaxa :177-183).
+ *   slk_compare_totals         reference rows read, dropped as "/2", kept; test rows read and joined (the current test).  Any
+ *                              pointer may be null.
+ *   slk_compare_error          where the text was wrong: the byte offset of the line in its whole text (all chunks counted) and
+ *                              SLK_COMPARE_BAD_LINE, SLK_COMPARE_DUPLICATE_REFERENCE (an id twice among the kept reference rows; the
+ *                              reference's join would multiply such rows) or SLK_COMPARE_DUPLICATE_TEST (an id twice among the
+ *                              JOINED test rows; an unjoined id may repeat).  Of several the lowest offset; a duplicate reports one
+ *                              of its occurrences.  The add that met it returned SLK_E_INVALID.
+ * After SLK_E_HIP, and after an add that returned SLK_E_INVALID for a bad line or a duplicate, the handle holds an unknown part and is
+ * spent: every call but slk_compare_error, slk_compare_totals and slk_compare_destroy returns SLK_E_STATE. */
+#define SLK_COMPARE_NO_ERROR 0
+#define SLK_COMPARE_BAD_LINE 1
+#define SLK_COMPARE_DUPLICATE_REFERENCE 2
+#define SLK_COMPARE_DUPLICATE_TEST 3
+typedef struct slk_compare slk_compare;
+int32_t slk_compare_create(slk_stream *st, slk_compare **out);
+int32_t slk_compare_add_reference(slk_compare *h, slk_stream *st, const uint8_t *text, uint64_t n, int32_t id_col, int32_t taxon_col,
+                                  int32_t final, uint64_t *consumed);
+int32_t slk_compare_add_reference_device(slk_compare *h, slk_stream *st, const uint8_t *d_text, uint64_t n, int32_t id_col,
+                                         int32_t taxon_col, int32_t final, uint64_t *consumed);
+int32_t slk_compare_begin_test(slk_compare *h);
+int32_t slk_compare_add_test(slk_compare *h, slk_stream *st, const uint8_t *text, uint64_t n, int32_t final, uint64_t *consumed);
+int32_t slk_compare_add_test_device(slk_compare *h, slk_stream *st, const uint8_t *d_text, uint64_t n, int32_t final, uint64_t *consumed);
+int32_t slk_compare_pairs(slk_compare *h, uint64_t *n, int32_t *ref_taxon, int32_t *test_taxon, uint64_t *count, uint64_t cap);
+int32_t slk_compare_reference_taxa(slk_compare *h, uint64_t *n, int32_t *taxa, uint64_t *count, uint64_t cap);
+int32_t slk_compare_totals(slk_compare *h, uint64_t *reference_rows, uint64_t *dropped_second, uint64_t *kept_ids, uint64_t *test_rows,
+                           uint64_t *joined_rows);
+int32_t slk_compare_error(slk_compare *h, uint64_t *byte_offset, int32_t *kind);
+void slk_compare_destroy(slk_compare *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ The product is libslacken_amd.so (hand-written HIP for gfx950 behind the C ABI i
 This package is the thin Python plumbing used by tests and bench.py: a ctypes binding of that ABI.
 There is no CPU fallback: importing works anywhere, computing needs the built library and a gfx950 device.
 """
-from .capi import (Index, Stream, Pipe, SlackenError, BrackenWeights, Coverage, Support, E_INVALID, E_UNSUPPORTED, lib, lib_path, ClassifyParams, DEFAULT_TOGGLE_MASK,  # noqa: F401
+from .capi import (Index, Stream, Pipe, SlackenError, BrackenWeights, Coverage, Support, Compare, E_INVALID, E_UNSUPPORTED, lib, lib_path, ClassifyParams, DEFAULT_TOGGLE_MASK,  # noqa: F401
                    TAXON_NONE, TAXON_ROOT, TAXON_AMBIGUOUS, TAXON_MATE_PAIR_BORDER,
                    FLAG_SEQUENCE, FLAG_AMBIGUOUS, FLAG_MATE_PAIR_BORDER)
 

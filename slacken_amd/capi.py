@@ -94,7 +94,12 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_pipe_create", "slk_pipe_set_merged_hits", "slk_pipe_submit", "slk_pipe_collect", "slk_pipe_pending", "slk_pipe_destroy",
            "slk_pack_bases_sparse",
            "slk_mask_tile_bases", "slk_mask_device", "slk_mask_sequences", "slk_index_add_sequences_masked",
-           "slk_stream_set_split_long", "slk_stream_set_split_hits", "slk_stream_last_split", "slk_stream_split_info"]
+           "slk_stream_set_split_long", "slk_stream_set_split_hits", "slk_stream_last_split", "slk_stream_split_info",
+           "slk_compare_create", "slk_compare_add_reference", "slk_compare_add_reference_device", "slk_compare_begin_test",
+           "slk_compare_add_test", "slk_compare_add_test_device", "slk_compare_pairs", "slk_compare_reference_taxa", "slk_compare_totals",
+           "slk_compare_error", "slk_compare_destroy"]
+
+COMPARE_BAD_LINE, COMPARE_DUPLICATE_REFERENCE, COMPARE_DUPLICATE_TEST = 1, 2, 3   # SLK_COMPARE_* of the header
 
 PAIR_FIELDS = ("P", "mismatch", "consumed1", "consumed2", "R1", "R2", "n_bases", "n_mate_bases")   # slk_pair_record, in order
 
@@ -264,6 +269,18 @@ def lib():
     L.slk_mask_device.argtypes = [vp, u8p, u64p, C.c_uint64, C.POINTER(MaskConfig), u64p]
     L.slk_mask_sequences.argtypes = [vp, u8p, u64p, C.c_uint64, C.POINTER(MaskConfig), C.POINTER(C.c_uint64)]
     L.slk_index_add_sequences_masked.argtypes = [vp, vp, u8p, u64p, i32p, C.c_uint64, C.POINTER(MaskConfig), C.POINTER(C.c_uint64)]
+    L.slk_compare_create.argtypes = [vp, C.POINTER(vp)]
+    L.slk_compare_add_reference.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
+    L.slk_compare_add_reference_device.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64)]
+    L.slk_compare_begin_test.argtypes = [vp]
+    L.slk_compare_add_test.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]
+    L.slk_compare_add_test_device.argtypes = [vp, vp, u8p, C.c_uint64, C.c_int32, C.POINTER(C.c_uint64)]
+    L.slk_compare_pairs.argtypes = [vp, C.POINTER(C.c_uint64), i32p, i32p, u64p, C.c_uint64]
+    L.slk_compare_reference_taxa.argtypes = [vp, C.POINTER(C.c_uint64), i32p, u64p, C.c_uint64]
+    L.slk_compare_totals.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 5
+    L.slk_compare_error.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+    L.slk_compare_destroy.argtypes = [vp]
+    L.slk_compare_destroy.restype = None
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:  # default: int32 status
@@ -641,6 +658,107 @@ class Support:
         if getattr(self, "h", None):
             lib().slk_support_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Compare:
+    """Classifications joined with a truth mapping on the read id (slk_compare_*: the join of MappingComparison,
+    S/slacken/analysis/MappingComparison.scala:157-159, 216-217).  The reference mapping's rows stay on the device; each test text
+    is a begin_test(), its add_test() calls, then pairs().  Taxa are RAW, as the texts have them: primary(), isDefined and the rank
+    arithmetic are the caller's, over the distinct pairs.
+
+    No Index or Stream is needed: Compare(device=0) makes the small empty index and the stream that own the handle.
+
+        c = Compare()
+        c.add_reference(open("reads_mapping.tsv", "rb").read())          # columns 2 and 3, or id_col= / taxon_col=
+        c.begin_test()
+        c.add_test(open("part-00000.txt", "rb").read())                  # the per-read lines `classify` writes
+        ref_taxon, test_taxon, rows = c.pairs()
+
+    add_reference / add_test take a whole text, or, with final=False, a chunk: they return the bytes consumed, where the next chunk
+    starts (0: the chunk holds no whole line and must grow).  A bad line or a duplicated id raises SlackenError (code -1); error()
+    then gives (byte offset of the line in its whole text, kind)."""
+
+    def __init__(self, stream=None, device=0):
+        self._index = None
+        if stream is None:
+            self._index = Index(expected_records=1024, device=device)
+            stream = self._index.stream()
+        self.stream = stream
+        h = C.c_void_p()
+        _check(lib().slk_compare_create(stream.h, C.byref(h)))
+        self.h = h
+
+    def _add(self, fn, text, args, final):
+        text = np.frombuffer(bytes(text), np.uint8) if not isinstance(text, np.ndarray) else _np(text, np.uint8)
+        consumed = C.c_uint64(0)
+        _check(fn(self.h, self.stream.h, _ptr(text) if text.size else None, text.size, *args, 1 if final else 0, C.byref(consumed)))
+        return int(consumed.value)
+
+    def add_reference(self, text, id_col=2, taxon_col=3, final=True):
+        return self._add(lib().slk_compare_add_reference, text, (int(id_col), int(taxon_col)), final)
+
+    def begin_test(self):
+        _check(lib().slk_compare_begin_test(self.h))
+
+    def add_test(self, text, final=True):
+        return self._add(lib().slk_compare_add_test, text, (), final)
+
+    def add_reference_device(self, d_text_ptr, n, id_col=2, taxon_col=3, final=True):
+        """add_reference with the text resident on the handle's GPU (raw device address, aligned to 16 bytes)"""
+        consumed = C.c_uint64(0)
+        _check(lib().slk_compare_add_reference_device(self.h, self.stream.h, d_text_ptr, n, int(id_col), int(taxon_col), 1 if final else 0,
+                                                      C.byref(consumed)))
+        return int(consumed.value)
+
+    def add_test_device(self, d_text_ptr, n, final=True):
+        consumed = C.c_uint64(0)
+        _check(lib().slk_compare_add_test_device(self.h, self.stream.h, d_text_ptr, n, 1 if final else 0, C.byref(consumed)))
+        return int(consumed.value)
+
+    def pairs(self):
+        """(reference taxon, test taxon, joined rows) of the current test, ascending, as numpy arrays"""
+        n = C.c_uint64(0)
+        _check(lib().slk_compare_pairs(self.h, C.byref(n), None, None, None, 0))
+        ref, test, count = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_compare_pairs(self.h, C.byref(n), _ptr(ref), _ptr(test), _ptr(count), n.value))
+        return ref, test, count
+
+    def reference_taxa(self):
+        """(raw taxon, kept reference rows), ascending"""
+        n = C.c_uint64(0)
+        _check(lib().slk_compare_reference_taxa(self.h, C.byref(n), None, None, 0))
+        taxa, count = np.zeros(n.value, np.int32), np.zeros(n.value, np.uint64)
+        if n.value:
+            _check(lib().slk_compare_reference_taxa(self.h, C.byref(n), _ptr(taxa), _ptr(count), n.value))
+        return taxa, count
+
+    def totals(self):
+        """(reference rows, dropped as "/2", kept ids, test rows, joined rows)"""
+        v = [C.c_uint64(0) for _ in range(5)]
+        _check(lib().slk_compare_totals(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def error(self):
+        """(byte offset, kind) of the bad line or duplicate that ended an add; kind 0: none"""
+        off, kind = C.c_uint64(0), C.c_int32(0)
+        _check(lib().slk_compare_error(self.h, C.byref(off), C.byref(kind)))
+        return int(off.value), int(kind.value)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().slk_compare_destroy(self.h)
+            self.h = None
+            if self._index is not None:   # (the index and the stream made for this handle alone)
+                self.stream.close()
+                self._index.close()
+                self._index = None
 
     def __del__(self):
         try:

@@ -9,6 +9,7 @@
 #include <sstream>
 
 #include "classify_stream.hpp"
+#include "compare.hpp"
 #include "coverage.hpp"
 #include "mask.hpp"
 #include "migration.hpp"
@@ -1267,6 +1268,176 @@ static int cmd_mask(int argc, char **argv) {
   return status;
 }
 
+// ---- compare (Slacken.scala:343-366): MappingComparison.processFiles / processDirectories.  compare.hpp has the contract; here are
+// the options, the readers and the joiner on the device ----
+static const char *COMPARE_USAGE =
+    "usage: compare -t TAXONOMY_DIR -r REFERENCE -o OUTPUT [--id-col 2] [-T|--taxon-col 3] [--header] (--test-files F... | --multi-dirs D...) "
+    "[--devices D] [--host]";
+
+// the join of slk_compare_*: one small empty index and a stream own the handle
+class DeviceJoin : public CompareJoiner {
+  slk_index *ix_ = nullptr;
+  slk_stream *st_ = nullptr;
+  slk_compare *h_ = nullptr;
+
+  size_t done(int32_t rc, const char *call, uint64_t consumed) {
+    if (rc == SLK_OK) return (size_t)consumed;
+    uint64_t at = 0;
+    int32_t kind = SLK_COMPARE_NO_ERROR;
+    if (rc == SLK_E_INVALID && slk_compare_error(h_, &at, &kind) == SLK_OK && kind != SLK_COMPARE_NO_ERROR) throw CompareTextError{at, kind};
+    die(std::string(call) + ": " + slk_last_error());
+  }
+
+ public:
+  explicit DeviceJoin(int device) {
+    const slk_params sp{35, 31, 7, 1, SLK_DEFAULT_TOGGLE_MASK, 1, 0};   // (a stream belongs to an index: an empty one of the default shape)
+    const slk_table_config tc{1024, 0, 0.0f};
+    SLK_CALL(slk_index_create(&sp, &tc, device, &ix_));
+    SLK_CALL(slk_stream_create(ix_, &st_));
+    SLK_CALL(slk_compare_create(st_, &h_));
+  }
+  ~DeviceJoin() override {
+    slk_compare_destroy(h_);
+    slk_stream_destroy(st_);
+    slk_index_destroy(ix_);
+  }
+  size_t add_reference(const char *p, size_t n, int id_col, int taxon_col, bool final) override {
+    uint64_t consumed = 0;
+    const int32_t rc = slk_compare_add_reference(h_, st_, (const uint8_t *)p, n, id_col, taxon_col, final ? 1 : 0, &consumed);
+    return done(rc, "slk_compare_add_reference", consumed);   // (the call first: it writes `consumed`)
+  }
+  void begin_test() override { SLK_CALL(slk_compare_begin_test(h_)); }
+  size_t add_test(const char *p, size_t n, bool final) override {
+    uint64_t consumed = 0;
+    const int32_t rc = slk_compare_add_test(h_, st_, (const uint8_t *)p, n, final ? 1 : 0, &consumed);
+    return done(rc, "slk_compare_add_test", consumed);
+  }
+  CompareCounts counts() override {
+    CompareCounts c;
+    uint64_t n = 0;
+    SLK_CALL(slk_compare_pairs(h_, &n, nullptr, nullptr, nullptr, 0));
+    std::vector<int32_t> a(n), b(n);
+    std::vector<uint64_t> rows(n);
+    if (n) SLK_CALL(slk_compare_pairs(h_, &n, a.data(), b.data(), rows.data(), n));
+    for (uint64_t i = 0; i < n; i++) c.pairs.push_back({a[i], b[i], rows[i]});
+    SLK_CALL(slk_compare_reference_taxa(h_, &n, nullptr, nullptr, 0));
+    a.resize(n); rows.resize(n);
+    if (n) SLK_CALL(slk_compare_reference_taxa(h_, &n, a.data(), rows.data(), n));
+    for (uint64_t i = 0; i < n; i++) c.ref_taxa.emplace_back(a[i], rows[i]);
+    SLK_CALL(slk_compare_totals(h_, &c.reference_rows, &c.dropped_second, &c.kept_ids, &c.test_rows, &c.joined_rows));
+    return c;
+  }
+};
+
+static int cmd_compare(int argc, char **argv) {
+  const char *why_one = "the reference mapping is joined on one GPU";
+  std::string taxonomy_dir, reference, output;
+  std::vector<std::string> test_files, multi_dirs;
+  int id_col = 2, taxon_col = 3;
+  bool header = false, host = false, have_files = false, have_dirs = false;
+  std::vector<int> devices{0};
+  for (Args a(argc, argv); a.take();) {
+    auto list = [&](std::vector<std::string> &into) {
+      while (a.peek() && a.peek()[0] != '-') into.push_back(a.next());
+    };
+    if (a == "-t" || a == "--taxonomy") taxonomy_dir = a.next();
+    else if (a == "-r" || a == "--reference") reference = a.next();
+    else if (a == "-o" || a == "--output") output = a.next();
+    else if (a == "--id-col") id_col = std::stoi(a.next());
+    else if (a == "-T" || a == "--taxon-col") taxon_col = std::stoi(a.next());
+    else if (a == "--header") header = true;
+    else if (a == "--noheader") header = false;
+    else if (a == "--test-files") { have_files = true; list(test_files); }
+    else if (a == "--multi-dirs") { have_dirs = true; list(multi_dirs); }
+    else if (a == "--host") host = true;
+    else if (a == "--devices") devices = parse_single_device(a.next(), "compare", why_one);
+    else if (a == "--shard-table") refuse_shard_table("compare", why_one, COMPARE_USAGE);
+    else die("unknown option " + a.opt + "\n" + COMPARE_USAGE);
+  }
+  if (taxonomy_dir.empty() || reference.empty() || output.empty()) die(COMPARE_USAGE);
+  if (have_files == have_dirs) die("compare takes exactly one of --test-files and --multi-dirs\n" + std::string(COMPARE_USAGE));
+  if ((have_files ? test_files : multi_dirs).empty()) die(std::string(have_files ? "--test-files" : "--multi-dirs") + " names nothing\n" + COMPARE_USAGE);
+  if (id_col < 1 || taxon_col < 1 || id_col == taxon_col) die("--id-col and --taxon-col are two columns, counted from 1\n" + std::string(COMPARE_USAGE));
+  const Taxonomy tax = Taxonomy::load(taxonomy_dir);
+  std::vector<std::pair<std::string, std::string>> locations;   // (test location, its reference mapping)
+  if (have_files) for (auto &f : test_files) locations.emplace_back(f, reference);
+  else {
+    for (auto &d : multi_dirs) if (!fs::is_directory(d)) die(d + " is no directory");
+    locations = compare_multi_locations(multi_dirs, reference);
+  }
+  const long env_chunk = getenv("SLK_COMPARE_CHUNK") ? atol(getenv("SLK_COMPARE_CHUNK")) : 0;
+  const size_t chunk = env_chunk > 0 ? (size_t)env_chunk : (size_t)64 << 20;
+  const char *kinds[] = {"", "too few columns, an empty id or taxon field, or a taxon that is no non-negative int", "this id occurs twice among the kept reference rows",
+                         "this id occurs twice among the test rows that have a reference row"};
+  // where in which file a joiner's offset lies, and the run ends
+  auto text_error = [&](const CompareTextError &e, const std::vector<std::pair<std::string, uint64_t>> &files, int idc, int txc) {
+    size_t fi = 0;
+    while (fi + 1 < files.size() && files[fi + 1].second <= e.offset) fi++;
+    ByteSource src(files[fi].first);
+    std::string text;
+    const uint64_t line = locate_line([&](char *dst, size_t cap) { return src.read(dst, cap); }, e.offset - files[fi].second, text);
+    std::string_view id;
+    int32_t taxon = 0;
+    std::string what = kinds[e.kind];
+    if (e.kind != COMPARE_BAD_LINE && compare_fields(text.data(), text.size(), idc - 1, txc - 1, id, taxon)) what += " (" + std::string(id) + ")";
+    die("compare: " + files[fi].first + " line " + std::to_string(line) + ": " + what);
+  };
+  std::map<std::string, std::unique_ptr<CompareJoiner>> resident;   // by reference mapping: uploaded once
+  std::vector<std::string> rows{compare_metrics_header()}, late;
+  const double t0 = wall_seconds();
+  double t_reference = 0, t_tests = 0;
+  for (auto &loc : locations) {
+    std::unique_ptr<CompareJoiner> &join = resident[loc.second];
+    if (!join) {
+      const double t1 = wall_seconds();
+      if (host) join = std::make_unique<HostJoin>();
+      else join = std::make_unique<DeviceJoin>(devices[0]);
+      uint64_t skipped = 0;   // (the header's bytes are not given to the joiner: its offsets lie that much lower)
+      try {
+        ByteSource src(loc.second);
+        feed_text([&](char *dst, size_t cap) { return src.read(dst, cap); }, chunk, header,
+                  [&](const char *p, size_t n, bool final) { return join->add_reference(p, n, id_col, taxon_col, final); }, &skipped);
+      } catch (CompareTextError &e) {
+        e.offset += skipped;
+        text_error(e, {{loc.second, 0}}, id_col, taxon_col);
+      }
+      t_reference += wall_seconds() - t1;
+    }
+    const double t1 = wall_seconds();
+    join->begin_test();
+    std::vector<std::pair<std::string, uint64_t>> files;
+    uint64_t base = 0;
+    try {
+      for (auto &f : compare_location_files(loc.first)) {
+        files.emplace_back(f, base);
+        ByteSource src(f);
+        feed_text([&](char *dst, size_t cap) { return src.read(dst, cap); }, chunk, false, [&](const char *p, size_t n, bool final) {
+          const size_t used = join->add_test(p, n, final);
+          base += used;
+          return used;
+        });
+      }
+    } catch (const CompareTextError &e) {
+      text_error(e, files, 2, 3);
+    }
+    LocationMetrics m;
+    std::cout << location_report(tax, join->counts(), loc.first, have_dirs, m) << std::flush;
+    for (int ri = 0; ri < 2; ri++) {
+      std::string row;
+      (metrics_row(m, ri, row) ? rows : late).push_back(row);
+    }
+    t_tests += wall_seconds() - t1;
+  }
+  for (auto &l : late) std::cout << l << "\n";
+  std::ofstream out = open_output(output + "_metrics.tsv");
+  for (auto &r : rows) out << r << "\n";
+  out.close();
+  if (!out) die("cannot write " + output + "_metrics.tsv");
+  std::cerr << "compare: " << locations.size() << " locations, " << resident.size() << " reference mappings (" << t_reference << " s), tests "
+            << t_tests << " s, " << wall_seconds() - t0 << " s in all" << (host ? " on the host" : "") << std::endl;
+  return 0;
+}
+
 // ---- coverage: the genome coverage of IndexStatistics (S/slacken/IndexStatistics.scala:38-52, 86-111), behind a command of its own.
 // The reference reaches it through `stats --library`, `inspect --library` and `classify2 --index-reports`; those stay refused here.
 static const char *COVERAGE_USAGE = "usage: coverage -i INDEX -l LIBRARY_DIR -o OUTPUT [--devices D]";
@@ -1417,6 +1588,22 @@ static const char *HELP =
     "  the records of library SUBJECT joined on the minimizer with those of library REFERENCE (normally a superset; its table goes to\n"
     "  one GPU).  stdout: how many records moved up by how many standard ranks; OUTPUT_taxaToRoot_report.txt: a Kraken report of the\n"
     "  taxa whose minimizers went to the root or to cellular organisms.  Both libraries must share k, m, spaces, mask and canonical\n"
+    "  slacken-amd compare -t TAXONOMY_DIR -r REFERENCE -o OUTPUT [--id-col 2] [-T|--taxon-col 3] [--header] (--test-files F... |\n"
+    "  --multi-dirs D...) [--devices D] [--host] (Slacken.scala:343-366, MappingComparison.scala): the per-read lines `classify` wrote are\n"
+    "  joined on the read id with a truth mapping (TSV; rows whose id holds /2 are dropped, every /1 is removed from the others' ids) -- on\n"
+    "  the GPU, byte for byte, the mapping resident and uploaded once per file.  Per test location and for the ranks Genus and Species:\n"
+    "  true, vague and false positives and false negatives per read, precision and recall per taxon (a taxon counts with 10 reads); stdout\n"
+    "  has the reference's lines, OUTPUT_metrics.tsv one row per location and rank whose title has the shape\n"
+    "  FAMILY/GROUP/LIBRARY_K_M_sS_cC_classified/sample=ID (any other title is reported and left out, as by the reference -- so always\n"
+    "  with --test-files, whose title is the file name).  --test-files: files, or directories of part files (names beginning with _ or .\n"
+    "  are skipped; plain, .gz, .bz2), all against REFERENCE.  --multi-dirs: every subdirectory sample=ID of every D against\n"
+    "  REFERENCE/sampleID/reads_mapping.tsv, e.g. what `classify -o OUT --sample-regex ... -c 0.15` left, renamed to the shape above:\n"
+    "    slacken-amd compare -t TAX -r TRUTH -o eval --multi-dirs fam/grp/std_35_31_s7_c0.15_classified\n"
+    "  --header drops the first non-empty line of REFERENCE.  --host: the same command with the join in a host hash map (no GPU is\n"
+    "  opened).  Unlike the reference, which throws or silently multiplies rows: a line with too few columns, an empty id or taxon, or\n"
+    "  a taxon that is no non-negative int ends the run naming file and line; so does a taxon outside the taxonomy, an id that occurs\n"
+    "  twice among the kept reference rows, and an id that occurs twice among the test rows that have a reference row.  Ids containing\n"
+    "  a double quote are not pinned against Spark's CSV reader.  One device\n"
     "  slacken-amd stats -i INDEX [--histogram] [--devices D] (Slacken.scala:281-315): the splitter's masks, then how many taxa the\n"
     "  library stores, how many of them are leaves and how many records lie on leaves; with --histogram the records and the stored\n"
     "  taxa by rank depth instead.  Counted on the GPU from the resident table (--library, the genome coverage check, is not supported)\n"
@@ -1473,7 +1660,7 @@ static const char *HELP =
     "             SLK_BUILD_BATCH_BASES (bases per batch of `build` and `coverage`, default 2^30), SLK_MASK_BATCH_BASES (bytes of text per piece\n"
     "             of `mask` and letters per staged batch of slk_mask_sequences, default 2^28), SLK_COVERAGE_MAX_PAIRS ((minimizer, source\n"
     "             taxon) pairs `coverage` counts at a time, default: what half of the GPU's free memory holds), SLK_EXPORT_PIECE_BUCKETS (table buckets per exported\n"
-    "             piece of `build` and `respace`, default 2^23)\n";
+    "             piece of `build` and `respace`, default 2^23), SLK_COMPARE_CHUNK (bytes of text `compare` joins at a time, default 2^26)\n";
 
 int main(int argc, char **argv) {
   int i = 1;
@@ -1482,7 +1669,7 @@ int main(int argc, char **argv) {
     if (i + 1 < argc) g_partitions = atoi(argv[i + 1]);
     i += 2;
   }
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|mask|bracken-build|compare-index|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|mask|bracken-build|compare-index|compare|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1492,7 +1679,8 @@ int main(int argc, char **argv) {
       {"bracken-build", cmd_bracken_build}, {"kmer-distrib", cmd_kmer_distrib}, {"compare-index", cmd_compare_index},
       {"compareIndex", cmd_compare_index}, {"migration-report", cmd_migration_report}, {"stats", cmd_stats}, {"inspect", cmd_inspect},
       {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build},
-      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}, {"support", cmd_support}, {"mask", cmd_mask}};
+      {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}, {"support", cmd_support}, {"mask", cmd_mask},
+      {"compare", cmd_compare}};
   // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
   //  they were commands)
   const bool bare = (cmd == "stats" || cmd == "inspect") && i >= argc;
@@ -1502,6 +1690,6 @@ int main(int argc, char **argv) {
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `mask`, `bracken-build`, `compare-index`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `mask`, `bracken-build`, `compare-index`, `compare`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }

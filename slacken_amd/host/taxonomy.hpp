@@ -128,6 +128,32 @@ struct Taxonomy {
     return -1;
   }
 
+  // Taxonomy.stepsToAncestor :241-244 over pathToRoot :204-215: the index of `ancestor` on t's path to the root, -1 if it is not there
+  // (an id the taxonomy does not define has a path of just itself; NONE has none)
+  int stepsToAncestor(Taxon t, Taxon ancestor) const {
+    int steps = 0;
+    for (Taxon p = t; p > 0 && p < size(); p = parents[p], steps++)
+      if (p == ancestor) return steps;
+    return -1;
+  }
+  bool hasAncestor(Taxon t, Taxon ancestor) const { return stepsToAncestor(t, ancestor) != -1; }  // :236-237
+  // Taxonomy.standardStepsToAncestor :248-254
+  int standardStepsToAncestor(Taxon t, Taxon ancestor) const { return hasAncestor(t, ancestor) ? depth(t) - depth(ancestor) : -1; }
+  // Taxonomy.standardAncestorAtLevel :276-279: the LAST taxon of the path's leading stretch at rank_depth or deeper (S rather than
+  // S1 or S2); NONE where the reference has None
+  Taxon standardAncestorAtLevel(Taxon t, int rank_depth) const {
+    Taxon last = NONE;
+    for (Taxon p = t; p > 0 && p < size() && depth(p) >= rank_depth; p = parents[p]) last = p;
+    return last;
+  }
+  // Taxonomy.taxaWithAncestors :307-310 as a membership vector
+  std::vector<uint8_t> taxaWithAncestors(const std::vector<Taxon> &taxa) const {
+    std::vector<uint8_t> in(parents.size(), 0);
+    for (Taxon a : taxa)
+      for (Taxon p = a; p > 0 && p < size() && !in[p]; p = parents[p]) in[p] = 1;
+    return in;
+  }
+
   // Taxonomy.missingStepsToRoot :298-304: which of the eight standard levels (superkingdom = depth 1 .. species = depth 8) no taxon
   // on t's path to the root has as its depth
   std::vector<int> missingStepsToRoot(Taxon t) const {
