@@ -132,7 +132,10 @@ int32_t slk_host_alloc(size_t bytes, void **out);
 int32_t slk_host_register(void *ptr, size_t bytes);
 int32_t slk_host_free(void *ptr);
 
-/* ---- index: replaces KeyValueIndex.load / loadRecords (S/slacken/KeyValueIndex.scala:150-159,413-426) ---- */
+/* ---- index: replaces KeyValueIndex.load / loadRecords (S/slacken/KeyValueIndex.scala:150-159,413-426) ----
+ * Windows: k - m + 1 m-mers, at most 512 -- and with one id column at most what a workgroup's LDS holds of the staged scan's ring, 512
+ * bytes per m-mer of the window: 320 m-mers on MI355X (160 KiB).  A wider window is refused here (SLK_E_UNSUPPORTED, the numbers in
+ * the message), not at the first classify call. */
 int32_t slk_index_create(const slk_params *params, const slk_table_config *cfg, int32_t device, slk_index **out);
 /* Append records (id1: int64 left-aligned minimizer, taxon: int32) -- the rows of the Parquet table, in any order
  * and any chunking (one call per bucket file is the intended use).  Keys are unique (guaranteed by makeRecords'
@@ -643,6 +646,25 @@ int32_t slk_stream_last_stage_ms(slk_stream *st, float out_ms[3]);
 /* How many fragments of the last classify call on st the lane-per-fragment kernel handed to the wave-per-fragment kernel
  * (longer than 1000 bases, or more than 12 distinct taxa); 0 if that call did not take the lane kernel.  Synchronises st. */
 int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count);
+/* Which kernels the last classify call on st launched, one SLK_ROUTE_* bit each, as the host issued them (a pass that found its list
+ * empty counts: the bit says the launch, not the work).  The lane path is LANE or ROUTING first, then LONG, SEGMENT, PIECES as the
+ * batch's plan has them, then WAVE for what they hand on; WAVE alone is the wave-per-fragment kernel as the batch's only pass (taxon
+ * ids over 22 bits without the dense renumbering, a taxonomy set after finalize, SLK_FORCE_WAVE=1); STAGED alone the three staged
+ * kernels (windows over 32 m-mers, several id columns, SLK_FORCE_V1=1).  RERUN is added when a taxon map was found overflowed and the
+ * batch was classified again by the staged kernels: that happens in slk_stream_synchronize or at the end of a host entry, so after
+ * slk_classify_batch_device the bit can appear only once the caller has synchronised.  Both switches are read once per classify call.
+ * Of a host call cut into sub-batches: the last sub-batch's.  0 before the first call.  Host bookkeeping: nothing is synchronised. */
+enum {
+  SLK_ROUTE_LANE = 1,      /* lane per fragment, the first pass over the whole batch */
+  SLK_ROUTE_ROUTING = 2,   /* the routing kernel that stands for it in batches of long fragments */
+  SLK_ROUTE_LONG = 4,      /* the lane kernel's long variant (1001 .. 4999 bases) */
+  SLK_ROUTE_SEGMENT = 8,   /* lane per segment */
+  SLK_ROUTE_PIECES = 16,   /* the piece route */
+  SLK_ROUTE_WAVE = 32,     /* wave per fragment */
+  SLK_ROUTE_STAGED = 64,   /* scan, probe, classify as three kernels */
+  SLK_ROUTE_RERUN = 128    /* the staged kernels again, unbounded taxon maps, after an overflow */
+};
+int32_t slk_stream_last_route(slk_stream *st, uint32_t *mask);
 
 /* ---- Contig-length fragments: one fragment split over many waves.  A fragment otherwise runs on ONE wave, at
  * about 15 Mbp/s, with a taxon map of 128 entries; a batch of a few hundred assembled contigs leaves most of the part idle, and a contig

@@ -83,7 +83,7 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_classify_batch_packed", "slk_pack_bases",
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
            "slk_shard_of", "slk_stream_set_merged_hits", "slk_classify_hits_device", "slk_shard_batch_rows", "slk_shard_chunk", "slk_shard_step_device",
-           "slk_stream_last_deferred", "slk_table_slot", "slk_table_hash_of",
+           "slk_stream_last_deferred", "slk_stream_last_route", "slk_table_slot", "slk_table_hash_of",
            "slk_shardset_create", "slk_shardset_classify", "slk_shardset_classify_rounds", "slk_shardset_exchange_mode", "slk_shardset_staged_pairs", "slk_shardset_destroy", "slk_bracken_create", "slk_bracken_add", "slk_bracken_result", "slk_bracken_destroy",
            "slk_migration_create", "slk_migration_add", "slk_migration_add_device", "slk_migration_result", "slk_migration_destroy",
            "slk_coverage_create", "slk_coverage_add", "slk_coverage_fold", "slk_coverage_result", "slk_coverage_totals", "slk_coverage_budget",
@@ -98,6 +98,11 @@ EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc"
            "slk_compare_create", "slk_compare_add_reference", "slk_compare_add_reference_device", "slk_compare_begin_test",
            "slk_compare_add_test", "slk_compare_add_test_device", "slk_compare_pairs", "slk_compare_reference_taxa", "slk_compare_totals",
            "slk_compare_error", "slk_compare_destroy"]
+
+# SLK_ROUTE_* of the header: the kernels a classify call launched (Stream.last_route)
+ROUTE_LANE, ROUTE_ROUTING, ROUTE_LONG, ROUTE_SEGMENT, ROUTE_PIECES, ROUTE_WAVE, ROUTE_STAGED, ROUTE_RERUN = (1 << i for i in range(8))
+ROUTE_NAMES = {ROUTE_LANE: "lane", ROUTE_ROUTING: "routing", ROUTE_LONG: "long", ROUTE_SEGMENT: "segment", ROUTE_PIECES: "pieces",
+               ROUTE_WAVE: "wave", ROUTE_STAGED: "staged", ROUTE_RERUN: "rerun"}
 
 COMPARE_BAD_LINE, COMPARE_DUPLICATE_REFERENCE, COMPARE_DUPLICATE_TEST = 1, 2, 3   # SLK_COMPARE_* of the header
 
@@ -210,6 +215,7 @@ def lib():
     L.slk_shard_chunk.restype = C.c_uint32
     L.slk_shard_step_device.argtypes = [vp, vp, C.POINTER(ShardLists), C.POINTER(ShardLookup), C.POINTER(ShardLists), C.POINTER(ShardResults)]
     L.slk_stream_last_deferred.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.slk_stream_last_route.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.slk_stream_set_split_long.argtypes = [vp, C.c_int64]
     L.slk_stream_set_split_hits.argtypes = [vp, C.c_int32]
     L.slk_stream_last_split.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1070,6 +1076,13 @@ class Stream:
         n = C.c_uint64(0)
         _check(lib().slk_stream_last_deferred(self.h, C.byref(n)))
         return int(n.value)
+
+    def last_route(self):
+        """the ROUTE_* bits of the kernels the last classify call on this stream launched, ROUTE_RERUN among them once a synchronisation
+        classified it again after a taxon-map overflow (slk_stream_last_route)"""
+        m = C.c_uint32(0)
+        _check(lib().slk_stream_last_route(self.h, C.byref(m)))
+        return int(m.value)
 
     def set_split_long(self, min_len=-1):
         """Unpaired fragments of at least min_len bases are split over many waves (slk_stream_set_split_long):

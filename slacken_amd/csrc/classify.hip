@@ -18,21 +18,24 @@ int32_t slk::ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R) {
 
 // The fused wave-per-read kernels (fused.hip) cover windows of up to 32 m-mers; wider windows (and SLK_FORCE_V1=1, an
 // A/B switch for tests) run the three separate lane-per-read kernels of kernels.hip.  Both are HIP: no CPU path.
-bool slk::use_fused(const slk_index *ix) {
-  static const bool force_v1 = env_on("SLK_FORCE_V1");
-  return !force_v1 && ix->W == 1 && ix->sp.w <= 32;
-}
+// With the switch as a value: what a classify call decided once (run_classify).  Without: the environment as it is now, for the
+// callers that decide per index or per entry, outside a classify call.
+bool slk::use_fused(const slk_index *ix, bool force_v1) { return !force_v1 && ix->W == 1 && ix->sp.w <= 32; }
+bool slk::use_fused(const slk_index *ix) { return use_fused(ix, env_on("SLK_FORCE_V1")); }
 
-bool slk::lane_path_ok(const slk_index *ix) {
-  return use_fused(ix) && ix->sp.w <= 32 && ix->internal_taxon_bits() <= 22 && ix->d_nodes != nullptr;
+bool slk::lane_path_ok(const slk_index *ix, bool force_v1) {
+  return use_fused(ix, force_v1) && ix->sp.w <= 32 && ix->internal_taxon_bits() <= 22 && ix->d_nodes != nullptr;
 }
+bool slk::lane_path_ok(const slk_index *ix) { return lane_path_ok(ix, env_on("SLK_FORCE_V1")); }
 
 // The fused kernels keep a fragment's taxon -> count map in LDS (12 slots per lane, 128 per wave).  A fragment that hits more
 // distinct taxa than that (long reads across conserved regions can) raises status bit 1; the batch is then classified again
 // by the staged kernels, whose per-fragment map lives in HBM scratch and is unbounded -- the same three kernels that serve
 // windows wider than 32 m-mers.  Slower (HBM intermediates), rare, and bit-identical for every other fragment.
+// (Only a call that ran fused is ever run again -- Queued.valid, as run_classify read the switches --, and this way never asks them.)
 int32_t slk::run_unbounded(slk_stream *st, const ClassifyCall &c) {
   slk_index *ix = st->ix;
+  st->last_route |= SLK_ROUTE_RERUN;
   const Reads &in = c.in;
   int32_t rc = ensure_scratch(st, span_slots(in.total, in.mate_total, in.R, in.paired()) + c.span_shift, in.R);
   if (rc) return rc;
@@ -60,7 +63,7 @@ Thresholds slk::thresholds_of(const double *v, int32_t C) {
   return thr;
 }
 
-// the spans of a batch, by the kernel that scans for this index
+// the spans of a batch, by the kernel that scans for this index (slk_scan_device: SLK_FORCE_V1 as the environment has it at the call)
 void slk::launch_spans(const slk_index *ix, slk_stream *st, const Reads &in, uint64_t *keys, int32_t *meta, int32_t *count) {
   if (ix->W > 1) {
     launch_wide_scan(ix->wp, in.bases, in.offsets, in.mate_bases, in.mate_offsets, in.R, keys, meta, count, st->s);
@@ -100,6 +103,7 @@ static int32_t first_pass(slk_stream *st, const LanePlan &plan, FusedArgs &A) {
   A.hand_stride = A.R; A.hand_long_cap = plan.long_cap; A.route_first = plan.route_first ? 1 : 0;
   A.long_max = plan.long_max; memcpy(A.long_bound, plan.long_bound, sizeof(A.long_bound));
   A.seg_min_len = plan.seg_min_len; A.wave_min = plan.wave_min; A.wave_ratio_q10 = plan.wave_ratio_q10;
+  st->last_route |= plan.route_first ? SLK_ROUTE_ROUTING : SLK_ROUTE_LANE;
   if (plan.route_first) launch_route(A, st->s);
   else launch_lane(A, nullptr, 1000, st->s);  // (the one-word map entries carry 10-bit k-mer counts)
   return SLK_OK;
@@ -128,6 +132,7 @@ static int32_t piece_pass(slk_stream *st, const ClassifyCall &c, const LanePlan 
   }
   launch_pieces(P, X, st->s2);
   st->last_used_pieces = true;
+  st->last_route |= SLK_ROUTE_PIECES;
   return SLK_OK;
 }
 
@@ -136,6 +141,7 @@ static void segment_pass(slk_stream *st, const ClassifyCall &c, const LanePlan &
   if (c.want_hits) B.span_keys = provisional_spans(st, c);
   B.work_list = A.hand_lists + HandOn::list_at(HandOn::SEG, A.R, plan.long_cap); B.work_count = A.hand_hdr + HandOn::SEG; B.work_draw = A.hand_hdr + HandOn::SEG_DRAW;
   launch_segments(B, st->s2);
+  st->last_route |= SLK_ROUTE_SEGMENT;
 }
 
 // the wave kernel over its lists strung together longest first (launch_order_wave_list)
@@ -144,12 +150,14 @@ static void ordered_wave_pass(slk_stream *st, const ClassifyCall &c, const LaneP
   launch_order_wave_list(W, st->s2);
   W.work_list = A.hand_lists + HandOn::ordered_at(A.R, plan.long_cap); W.work_count = A.hand_hdr + HandOn::ORDERED; W.work_draw = A.hand_hdr + HandOn::WAVE_DRAW;
   launch_fused(c.want_hits ? MODE_HITS : MODE_CLASSIFY, W, st->s2);
+  st->last_route |= SLK_ROUTE_WAVE;
 }
 
 // what the long variant handed on in turn (map overflows), when both streams are through
 static void late_list_pass(slk_stream *st, const ClassifyCall &c, const LanePlan &plan, FusedArgs A) {
   A.work_list = A.hand_lists + HandOn::list_at(HandOn::LATE, A.R, plan.long_cap); A.work_count = A.hand_hdr + HandOn::N_LATE; A.work_draw = A.hand_hdr + HandOn::LATE_DRAW;
   launch_fused(c.want_hits ? MODE_HITS : MODE_CLASSIFY, A, st->s);
+  st->last_route |= SLK_ROUTE_WAVE;
 }
 
 // The passes over the hand-on lists depend on the first pass only, and the long variant runs BESIDE the other two (which
@@ -166,6 +174,7 @@ static int32_t run_lane_path(slk_stream *st, const ClassifyCall &c, const LanePl
   if (!rc) rc = fork_ready(st);
   if (rc) return rc;
   HIPCHK(hipEventRecord(st->ev_fork, st->s));
+  if (A.long_max) st->last_route |= SLK_ROUTE_LONG;
   if (A.long_max) launch_lane_long(A, A.long_max, st->s);   // (first: its chain of steps is the longest, whoever comes first gets the CUs)
   HIPCHK(hipStreamWaitEvent(st->s2, st->ev_fork, 0));
   if (plan.piece_min_len && (rc = piece_pass(st, c, plan, A, taxa_bound))) return rc;
@@ -178,17 +187,17 @@ static int32_t run_lane_path(slk_stream *st, const ClassifyCall &c, const LanePl
 }
 
 // the batch by the fused kernels: the lane path where the index and the plan allow it, else the wave-per-fragment kernel alone
-static int32_t run_fused(slk_index *ix, slk_stream *st, const ClassifyCall &c) {
+static int32_t run_fused(slk_index *ix, slk_stream *st, const ClassifyCall &c, const PlanSwitches &sw) {
   const Reads &in = c.in;
   const FusedArgs A = call_args(ix, st, c);
   const uint32_t taxa_bound = 1u << std::min(ix->internal_taxon_bits(), 22);   // (lane_path_ok: at most 22 bits)
   LanePlan plan;
-  if (lane_path_ok(ix)) {
+  if (lane_path_ok(ix, sw.force_v1)) {
     PlanInput pi;
     pi.R = in.R; pi.all_bases = in.total + in.mate_total; pi.paired = in.paired(); pi.want_hits = c.want_hits;
     pi.w = ix->sp.w; pi.k = ix->sp.k; pi.split_long = st->split_long; pi.split_hits = st->split_hits;
     pi.taxa_bound = taxa_bound; pi.h_offsets = c.h_offsets;
-    plan = plan_lane(pi, read_plan_switches());
+    plan = plan_lane(pi, sw);
   }
   st->last_used_pieces = false;
   st->split_reported = false;
@@ -197,6 +206,7 @@ static int32_t run_fused(slk_index *ix, slk_stream *st, const ClassifyCall &c) {
     if (rc) return rc;
   } else {
     launch_fused(c.want_hits ? MODE_HITS : MODE_CLASSIFY, A, st->s);
+    st->last_route |= SLK_ROUTE_WAVE;
   }
   HIPCHK(hipEventRecord(st->ev[1], st->s));   // (no stages to tell apart: slk_stream_last_stage_ms reports all of it as the first)
   HIPCHK(hipEventRecord(st->ev[2], st->s));
@@ -206,9 +216,11 @@ static int32_t run_fused(slk_index *ix, slk_stream *st, const ClassifyCall &c) {
 // the batch by the three staged kernels (wide minimizers, windows over 32 m-mers, SLK_FORCE_V1)
 static int32_t run_staged(slk_index *ix, slk_stream *st, const ClassifyCall &c) {
   const Reads &in = c.in;
+  st->last_route |= SLK_ROUTE_STAGED;
   uint64_t *const keys = st->span_keys.as<uint64_t>();
   int32_t *const meta = st->span_meta.as<int32_t>(), *const taxa = st->span_taxon.as<int32_t>(), *const count = st->span_count.as<int32_t>();
-  launch_spans(ix, st, in, keys, meta, count);   // (not the fused kernel here)
+  if (ix->W > 1) launch_wide_scan(ix->wp, in.bases, in.offsets, in.mate_bases, in.mate_offsets, in.R, keys, meta, count, st->s);
+  else launch_scan(ix->sp, in.bases, in.offsets, in.mate_bases, in.mate_offsets, in.R, keys, meta, count, st->s);
   HIPCHK(hipEventRecord(st->ev[1], st->s));
   if (ix->W > 1) launch_wide_probe(ix->wt, ix->W, in.offsets, in.mate_offsets, in.R, keys, meta, count, taxa, st->s);
   else launch_probe(ix->view(), in.offsets, in.mate_offsets, in.R, keys, meta, count, taxa, st->s);
@@ -218,13 +230,19 @@ static int32_t run_staged(slk_index *ix, slk_stream *st, const ClassifyCall &c) 
   return SLK_OK;
 }
 
-int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call) {
+int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call) { return run_classify(ix, st, call, read_plan_switches()); }
+
+int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call, const PlanSwitches &sw) {
   ClassifyCall c = call;
   if (c.out.stride == 0) c.out.stride = c.in.R;
   const Reads &in = c.in;
-  const bool fused = use_fused(ix);
+  // The switches, read once per call (above, or by the host entry that cuts its batch up): the branch taken here, the scratch sized
+  // for it, the plan of the lane path and whether check_status may run the call again (Queued.valid) all follow from that one reading,
+  // whatever the environment says a moment later.
+  const bool fused = use_fused(ix, sw.force_v1);
   int32_t rc;
   st->last_used_lane = false;
+  st->last_route = 0;
   if (!fused || c.want_hits) {
     rc = ensure_scratch(st, span_slots(in.total, in.mate_total, in.R, in.paired()) + c.span_shift, in.R);
     if (rc) return rc;
@@ -236,7 +254,7 @@ int32_t slk::run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &cal
     if (rc) return rc;
   }
   st->queued.push_back({c, fused});
-  rc = fused ? run_fused(ix, st, c) : run_staged(ix, st, c);
+  rc = fused ? run_fused(ix, st, c, sw) : run_staged(ix, st, c);
   if (rc) return rc;
   HIPCHK(hipEventRecord(st->ev[3], st->s));
   HIPCHK(hipMemcpyAsync(st->h_status, st->d_status, sizeof(int32_t), hipMemcpyDeviceToHost, st->s));

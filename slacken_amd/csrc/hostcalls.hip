@@ -291,7 +291,7 @@ int32_t slk::size_host_buffers(slk_stream *st, uint64_t R, int32_t C, uint64_t t
 // their spans in the batch's span arrays (sub_call: span_shift) and the lists are put together for the whole batch at the end.
 // *early_down: the result rows came down beside the kernels (below).
 static int32_t run_sub_batches(slk_index *ix, slk_stream *st, const ReadSource &src, const uint64_t *offsets, const uint64_t *mate_offsets,
-                               const ClassifyCall &whole, uint64_t SUB, const HostRows &out, bool *early_down) {
+                               const ClassifyCall &whole, uint64_t SUB, const HostRows &out, bool *early_down, const PlanSwitches &sw) {
   const uint64_t R = whole.in.R;
   const bool paired = whole.in.paired(), pk = src.packed();
   int32_t rc, C = whole.C;
@@ -327,7 +327,7 @@ static int32_t run_sub_batches(slk_index *ix, slk_stream *st, const ReadSource &
     if (rc) return rc;
     HIPCHK(hipEventRecord(st->up_ev[i], st->cs));
     HIPCHK(hipStreamWaitEvent(st->s, st->up_ev[i], 0));
-    rc = run_classify(ix, st, sub_call(whole, r0, r1, offsets, mate_offsets));
+    rc = run_classify(ix, st, sub_call(whole, r0, r1, offsets, mate_offsets), sw);
     if (rc) return rc;
     if (*early_down) {
       HIPCHK(hipEventRecord(st->dn_ev[i], st->s));
@@ -466,15 +466,18 @@ static int32_t classify_batch_host(slk_index *ix, slk_stream *st, const ReadSour
   const uint64_t SUB = (uint64_t)std::max(1L, env_long("SLK_HOST_SUBBATCH", 1L << 19));
   const ClassifyCall whole = host_call(st, R, total, mate_total, paired, thresholds, C, min_hit_groups, out_hit_offsets != nullptr && out_hits != nullptr, offsets);
   DrainOnExit drain(st);   // (from the first copy queued below, no return leaves work behind that touches the caller's memory)
-  if (use_fused(ix) && R >= 2 * SUB) {
-    rc = run_sub_batches(ix, st, src, offsets, mate_offsets, whole, SUB, out.rows, &early_down);
+  // (the switches as this call reads them, once: cutting the batch up is the fused kernels' -- the staged ones take no span_shift --, so
+  //  the sub-batches' run_classify must see what this line saw)
+  const PlanSwitches sw = read_plan_switches();
+  if (use_fused(ix, sw.force_v1) && R >= 2 * SUB) {
+    rc = run_sub_batches(ix, st, src, offsets, mate_offsets, whole, SUB, out.rows, &early_down, sw);
     if (rc) return rc;
     if (call_timing) tm.uploaded = now();
   } else {
     rc = upload_whole(st, src, offsets, mate_offsets, whole.in);
     if (rc) return rc;
     if (call_timing) { (void)hipStreamSynchronize(st->s); tm.uploaded = now(); }
-    rc = run_classify(ix, st, whole);
+    rc = run_classify(ix, st, whole, sw);
     if (rc) return rc;
   }
   return finish_host_call(st, whole, out, early_down, call_timing ? &tm : nullptr);

@@ -4,6 +4,7 @@
 #pragma once
 #include "../../include/slacken_amd.h"
 #include "engine.h"
+#include "laneplan.h"   // PlanSwitches: what a classify call reads of the environment, once
 
 #include <algorithm>
 #include <cmath>
@@ -313,6 +314,7 @@ struct slk_stream {
   std::vector<Event> dn_ev;
   bool reran = false;           // check_status classified queued calls again (a taxon map had overflowed): results on the host are stale
   bool timed = false;
+  uint32_t last_route = 0;      // SLK_ROUTE_* of the kernels the last classify call launched (slk_stream_last_route), set where they are issued
   bool last_used_lane = false;  // the last classify call ran the lane kernel (defer_list[0] is its deferral count)
   // the piece route (engine.h: PieceArgs): slk_stream_set_split_long, its scratch (header, slots, units, records | the HBM maps), and
   // whether the last classify call ran it (piece_scratch then starts with its header: slk_stream_last_split)
@@ -472,13 +474,16 @@ int32_t check_ready(const slk_index *ix, const slk_stream *st, bool need_tax);
 int32_t check_status(slk_stream *st);   // call after the stream has been synchronised
 int32_t fork_ready(slk_stream *st);     // st->s2 and the events that fork it from st->s and join it again
 // classify.hip: the dispatch
-bool use_fused(const slk_index *ix);
+bool use_fused(const slk_index *ix, bool force_v1);      // with SLK_FORCE_V1 as a classify call read it (PlanSwitches.force_v1)
+bool lane_path_ok(const slk_index *ix, bool force_v1);
+bool use_fused(const slk_index *ix);                      // ... and as the environment has it now: decisions per index, outside a classify call
 bool lane_path_ok(const slk_index *ix);
 uint64_t span_slots(uint64_t total_bases, uint64_t total_mate_bases, uint64_t R, bool paired);
 int32_t ensure_scratch(slk_stream *st, uint64_t slots, uint64_t R);
 Thresholds thresholds_of(const double *v, int32_t C);
 FusedArgs fused_args(const slk_index *ix, const slk_stream *st, const Reads &in);
 void launch_spans(const slk_index *ix, slk_stream *st, const Reads &in, uint64_t *keys, int32_t *meta, int32_t *count);
+int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call, const PlanSwitches &sw);   // (the switches as the caller read them)
 int32_t run_classify(slk_index *ix, slk_stream *st, const ClassifyCall &call);   // the kernels of a batch and the status word's copy, queued on st->s
 int32_t run_unbounded(slk_stream *st, const ClassifyCall &c);   // the batch again by the staged kernels (check_status); synchronises st->s
 // hostcalls.hip: the pieces of the host entries, which pipe.hip queues per slot and shardset.hip and bracken.hip use too

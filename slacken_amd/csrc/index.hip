@@ -4,6 +4,7 @@
 // beside its kernels in export.hip, as slk_index_taxon_counts does in taxstats.hip.)
 #include "chunkcut.h"
 #include "hostside.h"
+#include "laneplan.h"
 
 // Geometry of the record table.  Any number of buckets (engine.h: the multiply-shift range reduction); a cell holds
 //   [flag] remainder (64 - q, + 1 unless the count is a power of two) | displacement | taxon     in 64 bits,
@@ -122,6 +123,10 @@ int32_t slk_index_create(const slk_params *p, const slk_table_config *cfg, int32
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(SLK_E_NO_GPU, "device %d is %s; this library holds gfx950 (MI355X) code objects only", device,
                 prop.gcnArchName);
+  // (one id column: the staged scan's ring of a wave, 512 bytes per m-mer of the window, has to fit a workgroup's LDS -- laneplan.h: plan_scan)
+  if (W == 1 && p->k - p->m + 1 > scan_max_window(prop.sharedMemPerBlock))
+    return fail(SLK_E_UNSUPPORTED, "k - m + 1 = %d m-mers per window: the scan's ring needs %zu bytes of LDS, a workgroup of this device has %zu (at most %d m-mers)",
+                p->k - p->m + 1, plan_scan(p->k - p->m + 1).lds, (size_t)prop.sharedMemPerBlock, scan_max_window(prop.sharedMemPerBlock));
 
   std::unique_ptr<slk_index> ix(new slk_index());   // (released into *out on success only)
   ix->device = device;

@@ -13,6 +13,7 @@
 //                    (S/slacken/TaxonCounts.scala:70-87), LowestCommonAncestor.apply/resolveTree
 //                    (S/slacken/LowestCommonAncestor.scala:49-146), Taxonomy.hasAncestor (S/slacken/Taxonomy.scala:236-244).
 #include "engine.h"
+#include "laneplan.h"
 
 #include <algorithm>
 
@@ -576,10 +577,11 @@ void launch_scan(const ScanParams &P, const uint8_t *bases, const uint64_t *offs
                  const uint64_t *mate_offsets, uint64_t R, uint64_t *span_keys, int32_t *span_meta, int32_t *span_count,
                  hipStream_t s) {
   if (R == 0) return;
-  // one lane per fragment; the w-key ring lives in LDS: blockDim * w * 8 bytes <= 64 KiB
-  int block = 256;
-  while (block > 64 && (size_t)block * P.w * 8 > 65536) block >>= 1;
-  size_t lds = (size_t)block * P.w * 8;
+  // one lane per fragment; the w-key ring lives in LDS: blockDim * w * 8 bytes, at most 64 KiB up to w = 128 and a wave's 512 w
+  // beyond -- which the device holds, or slk_index_create would have refused the splitter (laneplan.h: plan_scan, scan_max_window)
+  const ScanLaunch L = plan_scan(P.w);
+  const int block = L.block;
+  const size_t lds = L.lds;
   uint64_t blocks = (R + block - 1) / block;
   hipLaunchKernelGGL(scan_kernel, dim3((unsigned)blocks), dim3(block), lds, s, P, bases, offsets, mate_bases,
                      mate_offsets, R, span_keys, span_meta, span_count);

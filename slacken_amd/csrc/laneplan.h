@@ -1,5 +1,5 @@
 // laneplan.h -- the host's plan of a batch as plain arithmetic: which passes of the lane path run and where their limits lie
-// (plan_lane), how the piece route's scratch is carved (piece_layout), whether a sharded step's lookups ride in its scan
+// (plan_lane), how the piece route's scratch is carved (piece_layout), the staged scan's block and ring (plan_scan), whether a sharded step's lookups ride in its scan
 // (shard_side_per_tile).  No HIP header: tests/test_laneplan_cpu.py compiles it alone -- a wrong bound here is a device buffer too small.
 #pragma once
 #include "layouts.h"
@@ -30,19 +30,20 @@ struct LanePlan {
 };
 
 // The SLK_* switches the plan depends on, as values, each under its name in lower case (where unset means something: an int is
-// -1, an Opt not set) -- read per call, so that tests can move them; SLK_FORCE_WAVE, an A/B switch, alone once per process.
+// -1, an Opt not set) -- read per call, so that tests can move them.  The two A/B switches among them say which implementation runs
+// as a batch's only one: SLK_FORCE_WAVE (force_wave) the wave-per-fragment kernel instead of the lane path, SLK_FORCE_V1 (force_v1)
+// the staged kernels instead of either (classify.hip: use_fused).  A classify call reads them once (run_classify) and carries them.
 struct PlanSwitches {
   struct Opt { bool set = false; long long v = 0; };
-  bool force_wave = false, seg_hits = false;
+  bool force_wave = false, force_v1 = false, seg_hits = false;
   long long_max = 4999, piece_windows = (long)PIECE_DEFAULT_WINDOWS;   // (SLK_LANE_LONG_MAX)
   int route_first = -1, piece_hits = -1;
   Opt seg_min_len, piece_min_len;
 };
 inline PlanSwitches read_plan_switches() {
-  static const bool force_wave = env_on("SLK_FORCE_WAVE");
   const auto tri = [](const char *name) { const char *e = getenv(name); return e ? (e[0] == '1' ? 1 : 0) : -1; };
   PlanSwitches s;
-  s.force_wave = force_wave; s.seg_hits = env_on("SLK_SEG_HITS");
+  s.force_wave = env_on("SLK_FORCE_WAVE"); s.force_v1 = env_on("SLK_FORCE_V1"); s.seg_hits = env_on("SLK_SEG_HITS");
   s.long_max = env_long("SLK_LANE_LONG_MAX", s.long_max); s.piece_windows = env_long("SLK_PIECE_WINDOWS", s.piece_windows);
   s.route_first = tri("SLK_ROUTE_FIRST"); s.piece_hits = tri("SLK_PIECE_HITS");
   if (const char *e = getenv("SLK_SEG_MIN_LEN")) s.seg_min_len = {true, atol(e)};
@@ -168,6 +169,18 @@ inline PieceLayout piece_layout(const LanePlan &p) {
   l.hits_bytes = p.piece_hits ? p.piece_units * sizeof(PieceHitRecord) : 0;
   return l;
 }
+
+// The staged scan (kernels.hip: scan_kernel) keeps a lane's last w keys in LDS, 8 bytes each: a block of 256 lanes while that stays
+// within 64 KiB, halved down to one wave beyond (w > 32).  A wave's ring is 512 w bytes, more than 64 KiB from w = 129 on; what a
+// workgroup may have is the device's to say (160 KiB on MI355X: w <= 320), so slk_index_create asks scan_max_window and refuses the
+// splitter whose ring no block can hold -- launch_scan never asks for more than the device gives.
+struct ScanLaunch { int block; size_t lds; };
+inline ScanLaunch plan_scan(int w) {
+  int block = 256;
+  while (block > 64 && (size_t)block * (size_t)w * 8 > 65536) block >>= 1;
+  return {block, (size_t)block * (size_t)w * 8};
+}
+inline int scan_max_window(size_t lds_per_workgroup) { return (int)std::min<size_t>(lds_per_workgroup / (64 * 8), 512); }
 
 // A sharded step's lookups (slk_shard_step_device) ride in the scan, their 64-key batches dealt out to its tiles -- unless the scan
 // is far too short for them (a tile sends off about 2 / (w + 1) keys per base; a tile handed several times as many lookups as that

@@ -931,6 +931,7 @@ int32_t run_rounds(slk_shardset *set, slk_shard_batch *batches, int rounds, bool
   Pipe P{set, batches, rounds, on_device, min_hit_groups, C, thresholds, W, {}};
   P.deferred.assign((size_t)rounds * W, {});
   bool fast = true;
+  // (per member index, with SLK_FORCE_V1 as the environment has it when the rounds begin: one reading for all of them, the staged rounds if set)
   for (int g = 0; g < W; g++) fast = fast && lane_path_ok(set->m[g].ix);
   if (!fast) {   // a splitter outside the lane kernel's range: everything takes the staged kernels, round by round
     if (on_device) return fail(SLK_E_UNSUPPORTED, "device-resident rounds need a splitter the lane kernel takes");

@@ -31,6 +31,7 @@ int32_t slk_shard_step_device(slk_index *ix, slk_stream *st, const slk_shard_lis
   int32_t rc = check_ready(ix, st, apply != nullptr);
   if (rc) return rc;
   if ((rc = check_one_id_column(ix))) return rc;
+  // (per index, with SLK_FORCE_V1 as the environment has it at this call: the switch set refuses the step, which has no staged form)
   if (!lane_path_ok(ix)) return fail(SLK_E_UNSUPPORTED, "splitter outside the fused kernel's range: use the staged calls");
   if ((apply_lists == nullptr) != (apply == nullptr)) return fail(SLK_E_INVALID, "apply_lists and apply must be given together");
   if (emit && (rc = check_lists(*emit, "emit"))) return rc;

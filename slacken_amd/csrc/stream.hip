@@ -122,6 +122,14 @@ int32_t slk_stream_last_deferred(slk_stream *st, uint64_t *out_count) {
   return SLK_OK;
 }
 
+// (host-side bookkeeping alone, no device call: the bits are set where the launches are issued -- classify.hip --, the re-run's when
+//  check_status issues it, i.e. in the caller's slk_stream_synchronize or at the end of a host entry)
+int32_t slk_stream_last_route(slk_stream *st, uint32_t *mask) {
+  if (!st || !mask) return fail(SLK_E_INVALID, "null argument");
+  *mask = st->last_route;
+  return SLK_OK;
+}
+
 int32_t slk_stream_last_split(slk_stream *st, uint64_t *fragments, uint64_t *pieces, uint64_t *spills) {
   if (!st || !fragments || !pieces || !spills) return fail(SLK_E_INVALID, "null argument");
   { int32_t rc_ = set_device(st->ix); if (rc_) return rc_; }

@@ -26,6 +26,17 @@ def test_library_exports_every_declared_symbol():
     assert sorted(capi.EXPORTS) == syms
 
 
+def test_route_constants_are_the_headers():
+    """SLK_ROUTE_* (slk_stream_last_route): eight bits, one per kernel family, under the same names in capi.py"""
+    text = open(os.path.join(ROOT, "include", "slacken_amd.h")).read()
+    header = {name.lower(): int(v) for name, v in re.findall(r"\bSLK_ROUTE_([A-Z]+) = (\d+)", text)}
+    assert header == dict(lane=1, routing=2, long=4, segment=8, pieces=16, wave=32, staged=64, rerun=128)
+    assert {n: bit for bit, n in capi.ROUTE_NAMES.items()} == header
+    for n, bit in header.items():
+        assert getattr(capi, "ROUTE_" + n.upper()) == bit
+    assert "slk_stream_last_route" in capi.EXPORTS and hasattr(capi.Stream, "last_route")
+
+
 def test_version_and_error_text():
     L = slacken_amd.lib()
     assert b"gfx950" in L.slk_version()

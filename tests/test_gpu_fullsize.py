@@ -114,13 +114,21 @@ def test_reverse_complement_invariance(big):
     assert same(fwd, rev, keys=("taxon", "cls", "nd", "tk", "nh", "np_"))
 
 
-def test_lane_and_wave_kernels_agree(big):
-    # host-pointer entry with hit lists runs the wave-per-read kernel; compare with the device-pointer hot path
+def test_lane_and_wave_kernels_agree(big, monkeypatch):
+    # The host-pointer entry with hit lists under SLK_FORCE_WAVE=1 runs the wave-per-read kernel alone (hit lists by themselves do not
+    # select it: the lane kernel writes them too); compare with the device-pointer hot path, the lane kernel.  Which kernels ran is
+    # asserted on both legs (slk_stream_last_route).
+    from slacken_amd import capi
     R = 200_000
     host_b = big["bases"][:R * 150].cpu().numpy()
     host_o = np.arange(0, (R + 1) * 150, 150, dtype=np.uint64)
+    monkeypatch.delenv("SLK_FORCE_V1", raising=False)
+    monkeypatch.setenv("SLK_FORCE_WAVE", "1")
     wave = big["st"].classify_batch(host_b, host_o, thresholds=(0.0, 0.1), with_hits=True)
+    assert big["st"].last_route() == capi.ROUTE_WAVE
+    monkeypatch.delenv("SLK_FORCE_WAVE")
     lane = run(big, big["bases"], big["offsets"][:R + 1], R)
+    assert big["st"].last_route() & capi.ROUTE_LANE and not big["st"].last_route() & (capi.ROUTE_STAGED | capi.ROUTE_RERUN | capi.ROUTE_ROUTING)
     assert np.array_equal(wave["taxon"].reshape(-1), lane["taxon"].cpu().numpy())
     assert np.array_equal(wave["classified"].reshape(-1), lane["cls"].cpu().numpy())
     assert np.array_equal(wave["num_distinct"], lane["nd"].cpu().numpy())
@@ -200,9 +208,13 @@ def test_long_reads_of_mixed_lengths_all_routes_agree(big, orc, monkeypatch):
     assert int((want["num_distinct"] > 1).sum()) > 50          # (fragments over several source reads: several taxa each)
 
 
-def test_pairs_lane_and_wave_kernels_agree_and_a_sample_against_the_oracle(big, orc):
+def test_pairs_lane_and_wave_kernels_agree_and_a_sample_against_the_oracle(big, orc, monkeypatch):
     """2 x 150-base pairs at full table size: the device entry (lane kernel, both mates in one lane) against the host entry with hit
-    lists (wave kernel) pair for pair, and a sample of the pairs classified by the oracle through point lookups of the big table."""
+    lists under SLK_FORCE_WAVE=1 (the wave kernel alone) pair for pair, which kernels ran asserted on both legs, and a sample of the
+    pairs classified by the oracle through point lookups of the big table."""
+    from slacken_amd import capi
+    monkeypatch.delenv("SLK_FORCE_V1", raising=False)
+    monkeypatch.delenv("SLK_FORCE_WAVE", raising=False)
     torch = big["torch"]
     dev = big["dev"]
     R = min(big["R"] // 2, 400_000)
@@ -217,9 +229,13 @@ def test_pairs_lane_and_wave_kernels_agree_and_a_sample_against_the_oracle(big, 
                                     out["nd"].data_ptr(), out["tk"].data_ptr(), out["nh"].data_ptr(), d_mate_bases=d_b2.data_ptr(),
                                     d_mate_offsets=d_o.data_ptr(), total_mate_bases=R * 150, thresholds=thr)
     big["st"].synchronize()
+    assert big["st"].last_route() & capi.ROUTE_LANE and not big["st"].last_route() & (capi.ROUTE_STAGED | capi.ROUTE_RERUN | capi.ROUTE_ROUTING)
     h1, h2 = d_b1.cpu().numpy(), d_b2.cpu().numpy()
     ho = np.arange(0, (R + 1) * 150, 150, dtype=np.uint64)
+    monkeypatch.setenv("SLK_FORCE_WAVE", "1")
     wave = big["st"].classify_batch(h1, ho, h2, ho, thresholds=thr, with_hits=True)
+    assert big["st"].last_route() == capi.ROUTE_WAVE
+    monkeypatch.delenv("SLK_FORCE_WAVE")
     assert np.array_equal(wave["taxon"].reshape(-1), out["taxon"].cpu().numpy())
     assert np.array_equal(wave["classified"].reshape(-1), out["cls"].cpu().numpy())
     assert np.array_equal(wave["num_distinct"], out["nd"].cpu().numpy()) and np.array_equal(wave["total_kmers"], out["tk"].cpu().numpy())

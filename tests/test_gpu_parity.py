@@ -386,13 +386,19 @@ def test_streams_on_threads_share_one_index(orc, world):
     assert not errors, errors
 
 
-@pytest.mark.parametrize("taxonomy_first", [False, True], ids=["ids-as-given", "dense-ids"])
-def test_taxon_ids_beyond_22_bits(orc, taxonomy_first):
+@pytest.mark.parametrize("variant", ["ids-as-given", "dense-ids", "renumbering-declined"])
+def test_taxon_ids_beyond_22_bits(orc, variant, monkeypatch):
     """The lane kernel packs (taxon << 10 | count) into one LDS word.  With the taxonomy set before slk_index_finalize the table
     is renumbered to dense internal ids and the lane kernel serves ids of 2^22 and more at full speed (nothing deferred);
-    without it (taxonomy set after the records were finalized) the ids stay as given and the wave kernel takes every fragment.
+    without it (taxonomy set after the records were finalized) the ids stay as given and the wave kernel takes every fragment --
+    as it does when the taxonomy came first but the renumbering is declined, because one record's taxon is not a node of the
+    taxonomy (the id stays what it is: a root of its own, above nothing).  Which kernels ran is asserted by slk_stream_last_route.
     Either way every taxon that crosses the ABI -- calls, hit lists, lookups, exported records -- is the caller's id."""
     import slacken_amd
+    from slacken_amd import capi
+    for env in ("SLK_FORCE_WAVE", "SLK_FORCE_V1"):
+        monkeypatch.delenv(env, raising=False)
+    taxonomy_first = variant != "ids-as-given"
     rng = np.random.default_rng(2222)
     small = taxgen.taxonomy(8 * 16, rng)
     parents, remap = taxgen.sparse_relabel(small, 6_000_000, rng)
@@ -414,15 +420,21 @@ def test_taxon_ids_beyond_22_bits(orc, taxonomy_first):
     # give some minimizers an inner node (an LCA, as a real library has): reads then hit several taxa of a lineage
     inner = np.array([t for t in np.nonzero(parents)[0] if t > (1 << 22) and (parents == t).any()], np.int32)
     tx[::7] = inner[np.arange(len(tx[::7])) % len(inner)]
+    if variant == "renumbering-declined":
+        # one genome's records under an id the taxonomy does not define
+        stray = next(t for t in range(len(parents) - 1, 1 << 22, -1) if parents[t] == 0 and not (parents == t).any())
+        tx[tx == big_taxa[4]] = stray
+        assert (tx == stray).sum() > 100
     ix = slacken_amd.Index(expected_records=len(keys), max_taxon=len(parents) - 1)
     assert ix.info().taxon_bits > 22
     ix.append(keys, tx)
     if taxonomy_first:
         ix.set_taxonomy(parents)
         ix.finalize()
-        assert ix.info().dense_taxa == len(taxgen.defined_taxa(parents))
-        with pytest.raises(slacken_amd.SlackenError):
-            ix.set_taxonomy(parents)          # the dense ids derive from it
+        assert ix.info().dense_taxa == (0 if variant == "renumbering-declined" else len(taxgen.defined_taxa(parents)))
+        if variant == "dense-ids":
+            with pytest.raises(slacken_amd.SlackenError):
+                ix.set_taxonomy(parents)          # the dense ids derive from it
     else:
         ix.finalize()
         ix.set_taxonomy(parents)
@@ -431,7 +443,20 @@ def test_taxon_ids_beyond_22_bits(orc, taxonomy_first):
     world = dict(p=p, st=ix.stream(), oix=orc.Index(1, keys, tx), parents=parents)
     got = check_classify(orc, world, reads, thresholds=(0.0, 0.2))
     assert (got["taxon"][0] > (1 << 22)).any()
-    assert world["st"].last_deferred() == 0     # (dense ids: the lane kernel kept every fragment; ids as given: it did not run)
+    if variant == "renumbering-declined":
+        assert (got["taxon"][0] == stray).sum() > 20          # (reads of that genome: the detached id is their answer)
+    # the last call (check_classify ends on hit lists): dense ids -- the lane kernel, which kept every fragment; ids as given -- the wave kernel alone
+    assert world["st"].last_deferred() == 0
+    route = world["st"].last_route()
+    if variant == "dense-ids":
+        assert route & capi.ROUTE_LANE and not route & (capi.ROUTE_STAGED | capi.ROUTE_RERUN)
+    else:
+        assert route == capi.ROUTE_WAVE
+    bases, offsets = synth.pack(reads)
+    fast = world["st"].classify_batch(bases, offsets, thresholds=(0.0, 0.2), with_hits=False)     # ... and the hot path likewise
+    assert np.array_equal(fast["taxon"], got["taxon"])
+    route = world["st"].last_route()
+    assert (route & capi.ROUTE_LANE and not route & (capi.ROUTE_STAGED | capi.ROUTE_RERUN)) if variant == "dense-ids" else route == capi.ROUTE_WAVE
     assert np.array_equal(ix.lookup(keys), tx)
     ek, et = ix.export()
     order = np.argsort(keys, kind="stable")

@@ -20,7 +20,8 @@ using namespace slk;
 // stdin, a case a line, `name=value` separated by blanks; one line out per case.
 //   plan:  R bases paired hits w k split_long split_hits taxa | lens=a,b,.. (sets R and bases) host=1 (plan from the offsets)
 //          switches: force_wave long_max route_first seg_min_len seg_hits piece_min_len piece_hits piece_windows | env=1 (read them)
-//   lists: R long_cap route_first          shard: scans R bases w lookups          consts
+//   lists: R long_cap route_first          shard: scans R bases w lookups          consts          scan: w lds (the device's bytes per workgroup)
+//   setenv SLK_NAME=value ...: moves the process's environment for the lines that follow (an empty value unsets); prints "ok"
 int main() {
   char line[1 << 16];
   while (fgets(line, sizeof(line), stdin)) {
@@ -28,13 +29,18 @@ int main() {
     PlanSwitches sw;
     std::vector<uint64_t> offsets(1, 0);   // (exactly R + 1 entries: a read past them is the sanitizer's to report)
     bool host = false, env = false;
-    unsigned long long scans = 0, long_cap = 0, lookups = 0, route = 0;
+    unsigned long long scans = 0, long_cap = 0, lookups = 0, route = 0, lds = 0;
     std::string what;
     for (char *tok = strtok(line, " \n"); tok; tok = strtok(nullptr, " \n")) {
       char *eq = strchr(tok, '=');
       if (!eq) { what = tok; continue; }
       const std::string name(tok, eq - tok);
       const long long v = atoll(eq + 1);
+      if (what == "setenv") {
+        if (name.compare(0, 4, "SLK_") != 0) { fprintf(stderr, "setenv takes SLK_ names, not %s\n", name.c_str()); return 2; }
+        if (eq[1]) setenv(name.c_str(), eq + 1, 1); else unsetenv(name.c_str());
+        continue;
+      }
       if (name == "R") in.R = (uint64_t)strtoull(eq + 1, nullptr, 10);
       else if (name == "bases") in.all_bases = (uint64_t)strtoull(eq + 1, nullptr, 10);
       else if (name == "paired") in.paired = v != 0;
@@ -65,12 +71,18 @@ int main() {
       else if (name == "scans") scans = (unsigned long long)v;
       else if (name == "long_cap") long_cap = (unsigned long long)v;
       else if (name == "lookups") lookups = strtoull(eq + 1, nullptr, 10);
+      else if (name == "lds") lds = strtoull(eq + 1, nullptr, 10);
       else { fprintf(stderr, "unknown name %s\n", name.c_str()); return 2; }
     }
     if (what == "consts") {
       printf("frag=%zu record=%zu hit=%zu hdr_words=%d hand_words=%d min_windows=%u default_windows=%u default_min_len=%lld map_bytes=%llu per_base=%llu\n",
              sizeof(PieceFrag), sizeof(PieceRecord), sizeof(PieceHitRecord), (int)PieceHdr::WORDS, (int)HandOn::WORDS, PIECE_MIN_WINDOWS,
              PIECE_DEFAULT_WINDOWS, (long long)PIECE_DEFAULT_MIN_LEN, (unsigned long long)PIECE_DEFAULT_MAP_BYTES, (unsigned long long)PIECE_DEFAULT_MAP_PER_BASE);
+    } else if (what == "setenv") {
+      printf("ok\n");
+    } else if (what == "scan") {
+      const ScanLaunch L = plan_scan(in.w);
+      printf("block=%d lds=%zu max_window=%d\n", L.block, L.lds, scan_max_window((size_t)lds));
     } else if (what == "lists") {
       for (int l = 0; l < HandOn::LISTS; l++) printf("%llu ", (unsigned long long)HandOn::list_at(l, in.R, long_cap));
       printf("%llu %llu\n", (unsigned long long)HandOn::ordered_at(in.R, long_cap), (unsigned long long)HandOn::entries(in.R, long_cap, route != 0));
@@ -371,3 +383,32 @@ def test_switches_are_read_as_the_plan_takes_them(exe):
         for c in (dict(base), dict(base, hits=1, split_hits=1, split_long=300_000)):
             env = {ENV_NAMES[name]: str(v) for name, v in sw.items()}
             assert plans(exe, [dict(c, env=1)], env) == plans(exe, [dict(c, **sw)])
+
+
+def test_the_ab_switches_move_within_one_process(exe):
+    """SLK_FORCE_WAVE and SLK_FORCE_V1 are read with the rest, per call: one process of the planner sees them come and go"""
+    c = case_line(dict(READS, env=1))
+    lines = [c, "setenv SLK_FORCE_WAVE=1", c, "setenv SLK_FORCE_WAVE=0", c, "setenv SLK_FORCE_WAVE=1 SLK_FORCE_V1=1", c, "setenv SLK_FORCE_WAVE=", c,
+             "setenv SLK_FORCE_V1=", c]
+    out = run_lines(exe, lines)
+    assert out[1::2] == ["ok"] * 5
+    lane = [int(dict(t.split("=") for t in line.split())["lane"]) for line in out[0::2]]
+    assert lane == [1, 0, 1, 0, 1, 1]          # (force_v1 is not the plan's to act on: classify.hip takes the staged kernels before any plan)
+    # ... and a process started with the switch set can drop it
+    out = run_lines(exe, [c, "setenv SLK_FORCE_WAVE=", c], {"SLK_FORCE_WAVE": "1"})
+    assert [int(dict(t.split("=") for t in line.split())["lane"]) for line in (out[0], out[2])] == [0, 1]
+
+
+def test_scan_ring_fits_what_the_device_gives(exe):
+    """plan_scan / scan_max_window: 256 lanes while 2048 w bytes fit 64 KiB, halved down to one wave; a wave's ring is 512 w bytes, and
+    the widest window is the device's LDS per workgroup over 512, at most 512 (MI355X_MICROARCH: 160 KiB -- 320 m-mers)"""
+    ws = (1, 5, 32, 33, 64, 65, 128, 129, 320, 321, 512)
+    got = [{k: int(v) for k, v in (t.split("=") for t in line.split())} for line in run_lines(exe, [f"scan w={w} lds=163840" for w in ws])]
+    for w, g in zip(ws, got):
+        block = 256 if w <= 32 else 128 if w <= 64 else 64
+        assert (g["block"], g["lds"]) == (block, block * w * 8) and g["max_window"] == 320
+        assert g["lds"] <= 65536 or (g["block"] == 64 and w > 128)
+        assert (g["lds"] <= 163840) == (w <= g["max_window"])          # what is accepted is what fits
+    limits = {65536: 128, 65535: 127, 163840: 320, 163839: 319, 262144: 512, 1 << 20: 512, 0: 0}
+    got = run_lines(exe, [f"scan w=5 lds={v}" for v in limits])
+    assert [int(line.split()[2].split("=")[1]) for line in got] == list(limits.values())
