@@ -158,35 +158,25 @@ __device__ __forceinline__ void br_dec(MapRef &M, int32_t t, int32_t by) {
   else { M.at(s) = M.at(M.n - 1); M.n--; }
 }
 
-// resolveTree(countSummary, 0.0) (:101-146 via :276-285): the LCA of the taxa of maximal root-path score; with a required score of
-// 0 the lifting loop never runs.  NONE scores 0 and is not in the map.  The same interval test and tie walk as kernels.hip.
+// MapRef as resolve.h reads it (NONE is not in the map)
+struct BrMapView {
+  const int4 *e;
+  uint32_t stride;
+  int32_t len;
+  __device__ __forceinline__ int n() const { return len; }
+  __device__ __forceinline__ int32_t taxon(int j) const { return e[(uint32_t)j * stride].x; }
+  __device__ __forceinline__ int32_t count(int j) const { return e[(uint32_t)j * stride].y; }
+  __device__ __forceinline__ uint32_t tin(int j) const { return (uint32_t)e[(uint32_t)j * stride].z; }
+  __device__ __forceinline__ uint32_t tout(int j) const { return (uint32_t)e[(uint32_t)j * stride].w; }
+  __device__ __forceinline__ bool live(int) const { return true; }
+};
+
+// resolveTree(countSummary, 0.0) (:101-146 via :276-285): the LCA of the taxa of maximal root-path score (resolve.h, step 1); with a
+// required score of 0 the lifting loop never runs.  NONE scores 0 and is not in the map.
 __device__ int32_t br_resolve(const BrArgs &A, MapRef &M) {
   if (M.n == 0) return 0;
   if (M.n == 1) return M.at(0).x;
-  int32_t maxTaxon = 0, best = 0;
-  uint32_t m_in = 0, m_out = 0;
-  for (int32_t a = 0; a < M.n; a++) {
-    const int4 ea = M.at(a);
-    const uint32_t ain = (uint32_t)ea.z;
-    int32_t score = 0;
-    for (int32_t b = 0; b < M.n; b++) {
-      const int4 eb = M.at(b);
-      score += ((uint32_t)eb.z <= ain && ain <= (uint32_t)eb.w) ? eb.y : 0;
-    }
-    if (score > best) { maxTaxon = ea.x; best = score; m_in = ain; m_out = (uint32_t)ea.w; }
-    else if (score == best) {   // LowestCommonAncestor.apply :49-78 of (maxTaxon, ea.x)
-      if (m_in <= ain && ain <= m_out) {
-      } else if (ain <= m_in && m_in <= (uint32_t)ea.w) { maxTaxon = ea.x; m_in = ain; m_out = (uint32_t)ea.w; }
-      else {
-        int32_t x = (int32_t)tax_node(A.nodes, A.T, maxTaxon).x;
-        uint4 nx = make_uint4(0, 0, 0, 0);
-        while (x != 0) { nx = tax_node(A.nodes, A.T, x); if (nx.y <= ain && ain <= nx.z) break; x = (int32_t)nx.x; }
-        if (x == 0) { x = 1; nx = tax_node(A.nodes, A.T, 1); }
-        maxTaxon = x; m_in = nx.y; m_out = nx.z;
-      }
-    }
-  }
-  return maxTaxon;
+  return resolve_best(BrMapView{M.e, M.stride, M.n}, tax_tour(A.nodes, A.T)).taxon;
 }
 
 __device__ __forceinline__ void br_flush(const BrArgs &A, int32_t source, int32_t dest, uint64_t reads) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "resolve.h"   // the taxonomy's views, tax_lca and the resolveTree core: plain C++, also compiled without HIP
 #include "layouts.h"   // HandOn, the piece route's records and constants, env_on / env_long: shared with the host's plan (laneplan.h)
 
 namespace slk {
@@ -179,31 +180,14 @@ __device__ __forceinline__ int32_t table_lookup_cell(const TableView &t, uint64_
   return 0;
 }
 
-__device__ __forceinline__ int32_t tax_parent(const int32_t *parents, int32_t ntax, int32_t t) {
-  return ((uint32_t)t < (uint32_t)ntax) ? parents[t] : 0;
-}
-
-// LowestCommonAncestor.apply (LowestCommonAncestor.scala:49-78): the first node of b's path to the root that lies on a's
-// path; ROOT when the paths never meet; NONE is the identity.  Computed by levelling the depths (O(depth) loads).
-__device__ inline int32_t tax_lca(const int32_t *parents, int32_t ntax, int32_t a, int32_t b) {
-  if (a == 0 || b == 0) return b == 0 ? a : b;
-  if (a == b) return a;
-  int da = 0, db = 0;
-  for (int32_t x = a; x != 0; x = tax_parent(parents, ntax, x)) da++;
-  for (int32_t y = b; y != 0; y = tax_parent(parents, ntax, y)) db++;
-  for (; da > db; da--) a = tax_parent(parents, ntax, a);
-  for (; db > da; db--) b = tax_parent(parents, ntax, b);
-  while (a != b && a != 0) {
-    a = tax_parent(parents, ntax, a);
-    b = tax_parent(parents, ntax, b);
-  }
-  return a != 0 ? a : 1;
-}
-
-// {parent, tin, tout, -} of taxon t in an Euler-tour array (FusedArgs.nodes; index.hip: build_tax_nodes); an id outside the taxonomy is a
-// tree of its own.  A wave-uniform t makes it a scalar load.
+// The Euler-tour array (FusedArgs.nodes; index.hip: build_tax_nodes) as resolve.h's tour view; an id outside the taxonomy is a tree of
+// its own there.  A wave-uniform t makes node(t) a scalar load.
+static_assert(sizeof(TourNode) == sizeof(uint4) && alignof(TourNode) == alignof(uint4), "nodes[] is an array of TourNode");
+__device__ __forceinline__ Tour tax_tour(const uint4 *nodes, int32_t ntax) { return Tour{reinterpret_cast<const TourNode *>(nodes), ntax}; }
+// {parent, tin, tout, -} of taxon t
 __device__ __forceinline__ uint4 tax_node(const uint4 *nodes, int32_t ntax, int32_t t) {
-  return ((uint32_t)t < (uint32_t)ntax) ? nodes[t] : make_uint4(0u, 0x40000000u + (uint32_t)t, 0x40000000u + (uint32_t)t, 0u);
+  const TourNode n = tax_tour(nodes, ntax).node(t);
+  return make_uint4(n.parent, n.tin, n.tout, 0u);
 }
 
 // ---- device helpers the kernel files share ----------------------------------------------------------------------------------

@@ -16,9 +16,8 @@
 //          (S/slacken/Classifier.scala:84-88, KeyValueIndex.scala:176-185).
 //   LCA    a fragment whose hits name ONE taxon (the common case) is resolved without touching the tree; otherwise the
 //          hits are folded into a 128-slot LDS hash map (taxon -> k-mer count) and resolveTree runs with one lane per
-//          distinct taxon.  Reference: TaxonCounts.toMap/totalKmers (S/slacken/TaxonCounts.scala:70-87),
-//          LowestCommonAncestor.apply/resolveTree (S/slacken/LowestCommonAncestor.scala:49-146), Classifier.classify
-//          (Classifier.scala:439-454).
+//          distinct taxon.  Reference: TaxonCounts.toMap/totalKmers (S/slacken/TaxonCounts.scala:70-87), resolveTree (its tie and
+//          lift steps: resolve.h), Classifier.classify (Classifier.scala:439-454).
 // Control flow per fragment: a producer state machine (START -> FAST rounds over the mate, or over its runs of valid
 // characters one after the other (RUNS) when it holds others -> NEXT mate) fills the LDS span buffer; ONE flush site probes and
 // folds whatever is buffered; repeat until the fragment is exhausted.
@@ -263,15 +262,6 @@ __device__ __forceinline__ int char_code2(uint8_t c) {  // 0..3 nucleotide, 5 an
   }
 }
 
-// LowestCommonAncestor.apply :49-78 (wave-uniform arguments and control flow)
-__device__ int32_t lca_uniform(const int32_t *parents, int32_t ntax, int32_t a, int32_t b) {
-  if (a == 0 || b == 0) return b == 0 ? a : b;
-  for (int32_t y = b; y != 0; y = ((uint32_t)y < (uint32_t)ntax) ? parents[y] : 0)
-    for (int32_t x = a; x != 0; x = ((uint32_t)x < (uint32_t)ntax) ? parents[x] : 0)
-      if (x == y) return y;
-  return 1;
-}
-
 // resolveTree over the LDS map on the taxonomy's Euler-tour intervals (lane.hip has the same for its 12-slot maps):
 // one lane per distinct taxon.  Each loads its taxon's interval once; a taxon's root-path score is the count of the entries whose
 // interval holds its tin, a candidate's clade sum that of the entries whose tin its interval holds; the confidence walk jumps to
@@ -292,8 +282,9 @@ template <class MapView>
 __device__ __forceinline__ void resolve_intervals(WaveLds *L, const FusedArgs &A, uint64_t r, int lane, int32_t total, int32_t nd, const MapView &M,
                                                   int D) {
   // step 1 (:101-123): the LCA of the taxa with the maximal root-path score
-  int32_t maxTaxon = 0, best = 0, sum_all = 0;
-  uint32_t m_in = 0, m_out = 0;
+  const Tour tour = tax_tour(A.nodes, A.ntax);
+  Best cand = {0, 0u, 0u, 0};   // the candidate, wave-uniform
+  int32_t best = 0;
   for (int b0 = 0; b0 < D; b0 += 64) {
     const int i = b0 + lane;
     const int32_t t = i < D ? M.taxon(i) : 0;
@@ -301,9 +292,9 @@ __device__ __forceinline__ void resolve_intervals(WaveLds *L, const FusedArgs &A
     const uint32_t ain = act ? M.in(i) : 0u, aout = act ? M.out(i) : 0u;
     int32_t score = 0;
     for (int j = 0; j < D; j++) score += (act && M.in(j) <= ain && ain <= M.out(j)) ? M.count(j) : 0;   // (uniform j: LDS broadcasts)
-    sum_all += wave_sum(act ? M.count(i) : 0);
+    cand.sum_all += wave_sum(act ? M.count(i) : 0);
     const int32_t mx = wave_max(act ? score : -1);
-    if (mx > best) { best = mx; maxTaxon = 0; }
+    if (mx > best) { best = mx; cand.taxon = 0; }
     if (mx == best && best > 0) {
       uint64_t tie = __ballot(act && score == best && t != 0);
       while (tie) {
@@ -311,27 +302,16 @@ __device__ __forceinline__ void resolve_intervals(WaveLds *L, const FusedArgs &A
         tie &= tie - 1;
         const int32_t tt = __builtin_amdgcn_readlane(t, bl);
         const uint32_t tin_t = __builtin_amdgcn_readlane(ain, bl), tout_t = __builtin_amdgcn_readlane(aout, bl);
-        if (maxTaxon == 0 || (tin_t <= m_in && m_in <= tout_t)) {   // LowestCommonAncestor.apply :49-78 by intervals
-          maxTaxon = tt; m_in = tin_t; m_out = tout_t;
-        } else if (!(m_in <= tin_t && tin_t <= m_out)) {          // neither holds the other: the first node above that holds tt
-          int32_t x = (int32_t)tax_node(A.nodes, A.ntax, maxTaxon).x;
-          uint4 nx = make_uint4(0, 0, 0, 0);
-          while (x != 0) {
-            nx = tax_node(A.nodes, A.ntax, x);
-            if (nx.y <= tin_t && tin_t <= nx.z) break;
-            x = (int32_t)nx.x;
-          }
-          if (x == 0) { x = 1; nx = tax_node(A.nodes, A.ntax, 1); }             // no common node: ROOT (:77)
-          maxTaxon = x; m_in = nx.y; m_out = nx.z;
-        }
+        if (cand.taxon == 0) { cand.taxon = tt; cand.tin = tin_t; cand.tout = tout_t; }   // the first taxon of a new maximum
+        else tie_lca(tour, cand, tt, tin_t, tout_t);
       }
     }
   }
   for (int32_t c = 0; c < A.C; c++) {
     const double required = ceil(__dmul_rn(A.thr.v[c], (double)total));  // Math.ceil(confidence * totalKmers) :94
-    int32_t mt = maxTaxon;
-    uint32_t cin = m_in, cout = m_out;
-    uint4 cur = make_uint4(0, 0, 0, 0);
+    int32_t mt = cand.taxon;
+    uint32_t cin = cand.tin, cout = cand.tout;
+    TourNode cur = {0u, 0u, 0u, 0u};
     bool have_cur = false;
     while (mt != 0) {  // :125-144
       int32_t sum = 0;
@@ -350,7 +330,7 @@ __device__ __forceinline__ void resolve_intervals(WaveLds *L, const FusedArgs &A
       }
       const int32_t ms = wave_sum(sum);
       if ((double)ms >= required) break;
-      if (ms == sum_all) { mt = 0; break; }        // the clade holds the whole map: no ancestor can do better
+      if (ms == cand.sum_all) { mt = 0; break; }   // the clade holds the whole map: no ancestor can do better
       if (__ballot(side) == 0) {
         // everything left lies above the candidate, on its root path: the next clade that differs is the nearest of them
         const uint32_t nearest = (uint32_t)wave_max((int)up_in);
@@ -363,9 +343,7 @@ __device__ __forceinline__ void resolve_intervals(WaveLds *L, const FusedArgs &A
         have_cur = false;
         wave_sync();
       } else {
-        if (!have_cur) cur = tax_node(A.nodes, A.ntax, mt);
-        mt = (int32_t)cur.x;                       // Taxonomy.parents
-        if (mt != 0) { cur = tax_node(A.nodes, A.ntax, mt); have_cur = true; cin = cur.y; cout = cur.z; }
+        lift_parent(tour, mt, cin, cout, cur, have_cur);
       }
     }
     const bool classified = (mt != 0) && (nd >= A.min_hit_groups);  // Classifier.scala:445
@@ -422,7 +400,7 @@ __device__ __forceinline__ void resolve_map(WaveLds *L, const FusedArgs &A, uint
       while (tie) {
         int bl = __builtin_ctzll(tie);
         tie &= tie - 1;
-        maxTaxon = lca_uniform(A.parents, A.ntax, maxTaxon, __builtin_amdgcn_readlane(t, bl));
+        maxTaxon = tax_lca(A.parents, A.ntax, maxTaxon, __builtin_amdgcn_readlane(t, bl));   // (wave-uniform arguments: scalar loads, uniform control flow)
       }
     }
   }

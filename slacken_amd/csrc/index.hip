@@ -449,42 +449,12 @@ int32_t slk_index_append(slk_index *ix, const int64_t *keys, const int32_t *taxa
   return read_build_counters(ix);
 }
 
-// The taxonomy as the lane kernel reads it: per id {parent, tin, tout, 0}, tin / tout from a depth-first tour of the forest
-// (every id whose parent is NONE is a root: ROOT, unused ids, the top of a detached subtree), so that "a is an ancestor-or-self
-// of b" (Taxonomy.hasAncestor, Taxonomy.scala:236-244) is tin[a] <= tin[b] <= tout[a] -- two compares on values that are loaded
-// once per taxon of a read's map -- instead of a walk of b's root path: NCBI lineages are 25-40 nodes deep, and resolveTree
-// (LowestCommonAncestor.scala:101-146) asks it for every pair of map taxa and again at every step of the confidence walk.
+// The taxonomy as the interval resolvers read it, on the device: resolve.h's build_tour of the forest (nothing for fewer than two ids
+// or more than max_n: those callers walk)
 static int32_t build_tax_nodes(const int32_t *parents, int32_t n, int32_t max_n, DevPtr<uint4> &out) {
   out.reset();
   if (n < 2 || n > max_n) return SLK_OK;
-  std::vector<uint32_t> first((size_t)n + 1, 0), kids;   // children of p: kids[first[p] .. first[p + 1]), in increasing id order
-  for (int32_t t = 1; t < n; t++) if (parents[t] != 0) first[(size_t)parents[t] + 1]++;
-  for (int32_t p = 0; p < n; p++) first[(size_t)p + 1] += first[p];
-  kids.resize(first[n]);
-  {
-    std::vector<uint32_t> at(first.begin(), first.end() - 1);
-    for (int32_t t = 1; t < n; t++) if (parents[t] != 0) kids[at[parents[t]]++] = (uint32_t)t;
-  }
-  std::vector<uint4> nodes((size_t)n, make_uint4(0, 0, 0, 0));
-  std::vector<std::pair<uint32_t, uint32_t>> stack;   // (node, next child)
-  uint32_t clock = 0;
-  for (int32_t r = 1; r < n; r++) {
-    if (parents[r] != 0) continue;
-    stack.emplace_back((uint32_t)r, first[r]);
-    nodes[r].y = ++clock;
-    while (!stack.empty()) {
-      auto &top = stack.back();
-      if (top.second < first[(size_t)top.first + 1]) {
-        const uint32_t c = kids[top.second++];
-        nodes[c].x = top.first;
-        nodes[c].y = ++clock;
-        stack.emplace_back(c, first[c]);
-      } else {
-        nodes[top.first].z = clock;   // the largest tin of the subtree
-        stack.pop_back();
-      }
-    }
-  }
+  const std::vector<TourNode> nodes = build_tour(parents, n);
   HIPCHK(hipMalloc((void **)out.put(), (size_t)n * sizeof(uint4)));
   HIPCHK(hipMemcpy(out, nodes.data(), (size_t)n * sizeof(uint4), hipMemcpyHostToDevice));
   return SLK_OK;

@@ -10,8 +10,7 @@
 //                    value + run-length merge of equal minima (the equivalence is a property test under tests/).
 //   probe_kernel     the left equi-join + spanToHit (S/slacken/Classifier.scala:84-88, KeyValueIndex.scala:176-185).
 //   classify_kernel  Classifier.classify (Classifier.scala:439-454), TaxonCounts.toMap/totalKmers
-//                    (S/slacken/TaxonCounts.scala:70-87), LowestCommonAncestor.apply/resolveTree
-//                    (S/slacken/LowestCommonAncestor.scala:49-146), Taxonomy.hasAncestor (S/slacken/Taxonomy.scala:236-244).
+//                    (S/slacken/TaxonCounts.scala:70-87), resolveTree (resolve.h).
 #include "engine.h"
 #include "laneplan.h"
 
@@ -245,26 +244,20 @@ struct Tax {
   const int32_t *parents;
   const uint4 *nodes;   // {parent, tin, tout, -} per id from a depth-first tour (index.hip: build_tax_nodes), or null
   int32_t T;
-  __device__ __forceinline__ int32_t parent(int32_t t) const { return ((uint32_t)t < (uint32_t)T) ? parents[t] : 0; }
-  __device__ __forceinline__ uint4 node(int32_t t) const { return tax_node(nodes, T, t); }
 };
 
-// LowestCommonAncestor.apply :49-78 without the path buffer: first node on b's path that lies on a's path.
-__device__ int32_t lca_pair(const Tax &tx, int32_t a, int32_t b) {
-  if (a == 0 || b == 0) return b == 0 ? a : b;
-  for (int32_t y = b; y != 0; y = tx.parent(y))
-    for (int32_t x = a; x != 0; x = tx.parent(x))
-      if (x == y) return y;
-  return 1;  // ROOT
-}
-
-struct MapView {  // insertion-ordered taxon -> count map (Int2IntArrayMap) in this fragment's scratch slots
-  int2 *e;
-  int32_t n;
-  __device__ __forceinline__ int32_t get(int32_t t) const {
-    for (int32_t i = 0; i < n; i++) { int2 v = e[i]; if (v.x == t) return v.y; }
-    return 0;
-  }
+// The insertion-ordered taxon -> count map (Int2IntArrayMap) in this fragment's scratch slots, as resolve.h reads it: NONE is kept
+// (TaxonCounts.toMap) and is not live; the intervals are loaded again where they are needed (no room in HBM for them: the loads hit the L2).
+struct StagedMap {
+  const int2 *e;
+  int32_t len;
+  Tour tour;
+  __device__ __forceinline__ int n() const { return len; }
+  __device__ __forceinline__ int32_t taxon(int j) const { return e[j].x; }
+  __device__ __forceinline__ int32_t count(int j) const { return e[j].y; }
+  __device__ __forceinline__ bool live(int j) const { return e[j].x != 0; }
+  __device__ __forceinline__ uint32_t tin(int j) const { return tour.node(e[j].x).tin; }
+  __device__ __forceinline__ uint32_t tout(int j) const { return tour.node(e[j].x).tout; }
 };
 
 __global__ void __launch_bounds__(256) classify_kernel(Tax tx, const uint64_t *__restrict__ offsets,
@@ -283,9 +276,8 @@ __global__ void __launch_bounds__(256) classify_kernel(Tax tx, const uint64_t *_
   if (r >= R) return;
   uint64_t base = span_region(offsets, mate_offsets, r);
   int32_t n = span_count[r];
-  MapView map;
-  map.e = (int2 *)(map_scratch + base);
-  map.n = 0;
+  int2 *const e = (int2 *)(map_scratch + base);
+  int32_t len = 0;
   int32_t total = 0, nd = 0, nprobe = 0;
   for (int32_t j = 0; j < n; j++) {
     int32_t meta = span_meta[base + j];
@@ -298,110 +290,21 @@ __global__ void __launch_bounds__(256) classify_kernel(Tax tx, const uint64_t *_
     if (taxon == -1 || taxon == -2) continue;                 // TaxonCounts.toMap :70-81
     nprobe++;
     int32_t i = 0;
-    for (; i < map.n; i++) if (map.e[i].x == taxon) break;
-    if (i == map.n) { map.e[i] = make_int2(taxon, count); map.n++; }
-    else map.e[i].y += count;
+    for (; i < len; i++) if (e[i].x == taxon) break;
+    if (i == len) { e[i] = make_int2(taxon, count); len++; }
+    else e[i].y += count;
   }
 
-  if (tx.nodes != nullptr) {
-    // resolveTree on the taxonomy's Euler-tour intervals (a is an ancestor-or-self of b iff tin[a] <= tin[b] <= tout[a]; lane.hip
-    // and fused.hip do the same on their LDS maps): no walks of root paths.  The intervals are loaded again where
-    // they are needed -- this map lives in HBM and has no room for them; the loads hit the L2.  NONE is kept in the map
-    // (TaxonCounts.toMap) and is on no root path and in no clade.
-    int32_t maxTaxon = 0, best = 0, sum_all = 0;
-    uint32_t m_in = 0, m_out = 0;
-    for (int32_t it = 0; it < map.n; it++) {           // step 1 (:101-123)
-      const int2 a = map.e[it];
-      if (a.x == 0) continue;
-      sum_all += a.y;
-      const uint4 na = tx.node(a.x);
-      int32_t score = 0;
-      for (int32_t j = 0; j < map.n; j++) {
-        const int2 b = map.e[j];
-        if (b.x == 0) continue;
-        const uint4 nb = tx.node(b.x);
-        score += (nb.y <= na.y && na.y <= nb.z) ? b.y : 0;
-      }
-      if (score > best) { maxTaxon = a.x; best = score; m_in = na.y; m_out = na.z; }
-      else if (score == best) {                          // LowestCommonAncestor.apply :49-78 of (maxTaxon, a.x)
-        if (m_in <= na.y && na.y <= m_out) {
-        } else if (na.y <= m_in && m_in <= na.z) { maxTaxon = a.x; m_in = na.y; m_out = na.z; }
-        else {
-          int32_t x = (int32_t)tx.node(maxTaxon).x;
-          uint4 nx = make_uint4(0, 0, 0, 0);
-          while (x != 0) { nx = tx.node(x); if (nx.y <= na.y && na.y <= nx.z) break; x = (int32_t)nx.x; }
-          if (x == 0) { x = 1; nx = tx.node(1); }
-          maxTaxon = x; m_in = nx.y; m_out = nx.z;
-        }
-      }
-    }
-    for (int32_t c = 0; c < C; c++) {                    // step 2 (:125-144), jumping from map taxon to map taxon
-      const double required = ceil(__dmul_rn(thr.v[c], (double)total));
-      int32_t mt = maxTaxon;
-      uint32_t cin = m_in, cout = m_out;
-      uint4 cur = make_uint4(0, 0, 0, 0);
-      bool have_cur = false;
-      while (mt != 0) {
-        int32_t ms = 0, up_taxon = 0;
-        bool side = false;
-        uint32_t up_in = 0, up_out = 0;
-        for (int32_t j = 0; j < map.n; j++) {
-          const int2 b = map.e[j];
-          if (b.x == 0) continue;
-          const uint4 nb = tx.node(b.x);
-          const bool inside = cin <= nb.y && nb.y <= cout;
-          const bool above = !inside && nb.y <= cin && cin <= nb.z;
-          ms += inside ? b.y : 0;
-          side = side || (!inside && !above);
-          if (above && (up_taxon == 0 || nb.y > up_in)) { up_taxon = b.x; up_in = nb.y; up_out = nb.z; }
-        }
-        if ((double)ms >= required) break;
-        if (ms == sum_all) { mt = 0; break; }
-        if (!side) { mt = up_taxon; cin = up_in; cout = up_out; have_cur = false; }
-        else {
-          if (!have_cur) cur = tx.node(mt);
-          mt = (int32_t)cur.x;
-          if (mt != 0) { cur = tx.node(mt); have_cur = true; cin = cur.y; cout = cur.z; }
-        }
-      }
-      const bool classified = (mt != 0) && (nd >= min_hit_groups);   // Classifier.scala:445
-      out_taxon[(uint64_t)c * out_stride + r] = classified ? mt : 0;
-      out_classified[(uint64_t)c * out_stride + r] = classified ? 1 : 0;
-    }
-    if (out_num_distinct) out_num_distinct[r] = nd;
-    if (out_total_kmers) out_total_kmers[r] = total;
-    if (out_num_hits) out_num_hits[r] = n;
-    if (out_num_probes) out_num_probes[r] = nprobe;
-    return;
-  }
-  // (no Euler tour -- a taxonomy of more than 2^26 ids: the reference's walks)
-  // resolveTree step 1 (:101-123): LCA of all taxa with the maximal root-path score; threshold independent
-  int32_t maxTaxon = 0, maxScore = 0;
-  for (int32_t it = 0; it < map.n; it++) {
-    int32_t taxon = map.e[it].x;
-    int32_t score = 0;
-    for (int32_t node = taxon; node != 0; node = tx.parent(node)) score += map.get(node);
-    if (score > maxScore) { maxTaxon = taxon; maxScore = score; }
-    else if (score == maxScore) maxTaxon = lca_pair(tx, maxTaxon, taxon);
-  }
-
+  // resolveTree (resolve.h): on the taxonomy's Euler-tour intervals, or -- no tour, a taxonomy of more than 2^26 ids -- by the
+  // reference's walks.  Step 1 is threshold independent.
+  const bool tour = tx.nodes != nullptr;
+  const StagedMap map{e, len, tax_tour(tx.nodes, tx.T)};
+  const Parents par{tx.parents, tx.T};
+  const Best best = tour ? resolve_best(map, map.tour) : Best{resolve_walk_best(map, par), 0u, 0u, 0};
   for (int32_t c = 0; c < C; c++) {
-    // Math.ceil(confidenceThreshold * totalKmers) in binary64 (:94)
-    double required = ceil(__dmul_rn(thr.v[c], (double)total));
-    int32_t mt = maxTaxon;
-    int32_t ms = map.get(mt);                                // :125
-    while (mt != 0 && (double)ms < required) {               // :126-144
-      ms = 0;
-      for (int32_t it = 0; it < map.n; it++) {
-        int2 v = map.e[it];
-        bool in_clade = false;                               // Taxonomy.hasAncestor(v.x, mt) :236-244
-        for (int32_t x = v.x; x != 0; x = tx.parent(x)) if (x == mt) { in_clade = true; break; }
-        if (in_clade) ms += v.y;
-      }
-      if ((double)ms >= required) break;
-      mt = tx.parent(mt);
-    }
-    bool classified = (mt != 0) && (nd >= min_hit_groups);   // Classifier.scala:445
+    const double required = ceil(__dmul_rn(thr.v[c], (double)total));   // Math.ceil(confidenceThreshold * totalKmers) in binary64 (:94)
+    const int32_t mt = tour ? resolve_lift(map, map.tour, best, required) : resolve_walk_lift(map, par, best.taxon, required);
+    const bool classified = (mt != 0) && (nd >= min_hit_groups);   // Classifier.scala:445
     out_taxon[(uint64_t)c * out_stride + r] = classified ? mt : 0;
     out_classified[(uint64_t)c * out_stride + r] = classified ? 1 : 0;
   }

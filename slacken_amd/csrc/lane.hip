@@ -571,6 +571,20 @@ void launch_route(const FusedArgs &A, hipStream_t s) {
   hipLaunchKernelGGL(route_kernel, dim3((unsigned)std::min<uint64_t>((A.R + 2047) / 2048, 2048)), dim3(256), 0, s, A);
 }
 
+// A lane's map as resolve.h reads it: entry j of the lane's column (stride 64) after resolve_lane moved the entries to its front --
+// one word {taxon, count} per entry, LONG: taxon and full 32-bit count in words of their own -- with the intervals beside it.
+template <bool LONG>
+struct LaneMap {
+  const uint32_t *omap, *ecnt, *in, *out;
+  int lane, D;
+  __device__ __forceinline__ int n() const { return D; }
+  __device__ __forceinline__ int32_t taxon(int j) const { return LONG ? (int32_t)omap[j * 64 + lane] : (int32_t)(omap[j * 64 + lane] >> OMAP_CNT_BITS); }
+  __device__ __forceinline__ int32_t count(int j) const { return LONG ? (int32_t)ecnt[j * 64 + lane] : (int32_t)(ecnt[j * 64 + lane] & OMAP_CNT_MASK); }
+  __device__ __forceinline__ uint32_t tin(int j) const { return in[j * 64 + lane]; }
+  __device__ __forceinline__ uint32_t tout(int j) const { return out[j * 64 + lane]; }
+  __device__ __forceinline__ bool live(int) const { return true; }   // (NONE never enters this map)
+};
+
 // Per-read classification, one lane per read: the map the probe batches (or the APPLY job's replay) folded for the lane's fragment
 // -> TaxonCounts / resolveTree / the minHitGroups test -> the fragment's output rows.  oflags = the lane's o_flags word.
 template <bool HITS, bool LONG>
@@ -588,103 +602,37 @@ __device__ __forceinline__ void resolve_lane(LaneLds *L, uint32_t *ocnt, const F
       D++;
     }
   }
-#define ENT_TAXON(j) (LONG ? (int32_t)L->omap[(j) * 64 + lane] : (int32_t)(L->omap[(j) * 64 + lane] >> OMAP_CNT_BITS))
-#define ENT_COUNT(j) (LONG ? (int32_t)ecnt[(j) * 64 + lane] : (int32_t)(ecnt[(j) * 64 + lane] & OMAP_CNT_MASK))
-  int32_t maxTaxon = D ? ENT_TAXON(0) : 0;  // D <= 1: the single taxon (or NONE)
-  const int32_t c0 = D ? ENT_COUNT(0) : 0;
-  // D >= 2: resolveTree on Euler-tour intervals (engine.h: FusedArgs.nodes).  One 16-byte load per map taxon, issued back
-  // to back, brings its interval; "is a an ancestor-or-self of b" is then two compares, for the root-path scores (step 1)
-  // as for the clade sums of the confidence walk (step 2).  The intervals live in the probe queue's LDS, idle by now.
+  // D >= 2: resolveTree on Euler-tour intervals (engine.h: FusedArgs.nodes; resolve.h).  One 16-byte load per map taxon, issued
+  // back to back, brings its interval; "is a an ancestor-or-self of b" is then two compares, for the root-path scores (step 1) as
+  // for the clade sums of the confidence walk (step 2).  The intervals live in the probe queue's LDS, idle by now.
   uint32_t *const tin = (uint32_t *)L, *const tout = tin + OMAP * 64;
   static_assert(offsetof(LaneLds, omap) >= 2 * OMAP * 64 * sizeof(uint32_t), "the intervals alias the queue and the read stream's slots");
-  uint32_t m_in = 0, m_out = 0;   // maxTaxon's interval
-  int32_t sum_all = c0;
+  const LaneMap<LONG> M{L->omap, ecnt, tin, tout, lane, D};
+  const Tour tour = tax_tour(A.nodes, A.ntax);
+  Best best = {D ? M.taxon(0) : 0, 0u, 0u, D ? M.count(0) : 0};  // D <= 1: the single taxon (or NONE)
+  const int32_t c0 = best.sum_all;
   if (D >= 2 && !SLK_TUNE_ON(16)) {  // (16: timing experiment)
 #pragma unroll
     for (int j = 0; j < OMAP; j++) {
       if (j < D) {
-        const uint4 nj = tax_node(A.nodes, A.ntax, ENT_TAXON(j));
-        tin[j * 64 + lane] = nj.y;
-        tout[j * 64 + lane] = nj.z;
+        const TourNode nj = tour.node(M.taxon(j));
+        tin[j * 64 + lane] = nj.tin;
+        tout[j * 64 + lane] = nj.tout;
       }
     }
-    // step 1 (:101-123): the LCA of the taxa with the maximal root-path score -- a taxon's score is the k-mer count of the
-    // map taxa on its root path, i.e. of the entries whose interval holds its tin
-    maxTaxon = 0;
-    sum_all = 0;
-    int32_t best = 0;
-    for (int a = 0; a < D; a++) {
-      const uint32_t ain = tin[a * 64 + lane], aout = tout[a * 64 + lane];
-      int32_t score = 0;
-      for (int b = 0; b < D; b++)
-        score += (tin[b * 64 + lane] <= ain && ain <= tout[b * 64 + lane]) ? ENT_COUNT(b) : 0;
-      sum_all += ENT_COUNT(a);
-      if (score > best) {
-        maxTaxon = ENT_TAXON(a); best = score; m_in = ain; m_out = aout;
-      } else if (score == best) {   // LowestCommonAncestor.apply :49-78 of (maxTaxon, this taxon)
-        if (m_in <= ain && ain <= m_out) {
-          // maxTaxon is an ancestor-or-self of this taxon: it stays
-        } else if (ain <= m_in && m_in <= aout) {
-          maxTaxon = ENT_TAXON(a); m_in = ain; m_out = aout;
-        } else {                   // neither: the first node above maxTaxon whose interval holds this taxon
-          int32_t x = (int32_t)tax_node(A.nodes, A.ntax, maxTaxon).x;
-          uint4 nx = make_uint4(0, 0, 0, 0);
-          while (x != 0) {
-            nx = tax_node(A.nodes, A.ntax, x);
-            if (nx.y <= ain && ain <= nx.z) break;
-            x = (int32_t)nx.x;
-          }
-          if (x == 0) { x = 1; nx = tax_node(A.nodes, A.ntax, 1); }   // no common node: ROOT (:77)
-          maxTaxon = x; m_in = nx.y; m_out = nx.z;
-        }
-      }
-    }
+    best = resolve_best(M, tour);
   }
   for (int32_t c = 0; c < A.C; c++) {
     const double required = ceil(__dmul_rn(A.thr.v[c], (double)total));  // Math.ceil(confidence * totalKmers) :94
-    int32_t mt = maxTaxon;
+    int32_t mt = best.taxon;
     if (D < 2 || SLK_TUNE_ON(16)) {
       // one taxon: its clade sum never grows (NONE is in no clade), so it is the call or there is none (:125-144)
       if ((double)c0 < required) mt = 0;
-    } else {
-      // step 2 (:125-144): from maxTaxon towards the root until the clade of the candidate holds `required` k-mers of the
-      // map.  The clade sum only changes where the candidate's interval comes to hold another map taxon, and once it holds
-      // them all no ancestor can do better: the walk ends there (the reference goes on to the root and finds nothing).
-      uint32_t cin = m_in, cout = m_out;
-      uint4 cur = make_uint4(0, 0, 0, 0);
-      bool have_cur = false;
-      while (mt != 0) {
-        int32_t ms = 0;
-        bool side = false;          // a map taxon outside the clade that is NOT an ancestor of the candidate
-        int up = -1;                // the nearest map taxon above the candidate
-        uint32_t up_in = 0;
-        for (int j = 0; j < D; j++) {
-          const uint32_t jin = tin[j * 64 + lane], jout = tout[j * 64 + lane];
-          const bool inside = cin <= jin && jin <= cout;
-          ms += inside ? ENT_COUNT(j) : 0;
-          const bool above = !inside && jin <= cin && cin <= jout;
-          side = side || (!inside && !above);
-          if (above && (up < 0 || jin > up_in)) { up = j; up_in = jin; }   // (deeper on one root path = later in the tour)
-        }
-        if ((double)ms >= required) break;
-        if (ms == sum_all) { mt = 0; break; }
-        if (!side) {
-          // everything left lies above the candidate, on its root path: the next clade that differs is the nearest of them
-          mt = ENT_TAXON(up); cin = up_in; cout = tout[up * 64 + lane];
-          have_cur = false;
-        } else {
-          if (!have_cur) cur = tax_node(A.nodes, A.ntax, mt);
-          mt = (int32_t)cur.x;                                           // Taxonomy.parents
-          if (mt != 0) { cur = tax_node(A.nodes, A.ntax, mt); have_cur = true; cin = cur.y; cout = cur.z; }
-        }
-      }
-    }
+    } else mt = resolve_lift(M, tour, best, required);
     bool classified = (mt != 0) && (nd >= A.min_hit_groups);            // Classifier.scala:445
     A.out_taxon[(uint64_t)c * A.out_stride + r] = classified ? ext_taxon(A.T, mt) : 0;
     A.out_classified[(uint64_t)c * A.out_stride + r] = classified ? 1 : 0;
   }
-#undef ENT_TAXON
-#undef ENT_COUNT
   if (A.out_nd) A.out_nd[r] = nd;
   if (A.out_tk) A.out_tk[r] = total;
   if (A.out_nh) A.out_nh[r] = nhits;
