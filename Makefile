@@ -27,9 +27,9 @@ $(STREAM_SUM): tools/stream_sum.hip
 	@mkdir -p slacken_amd/lib
 	$(HIPCC) -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -shared -o $@ tools/stream_sum.hip
 
-HIPSRC := $(addprefix $(CSRC)/,kernels.hip fused.hip lane.hip build.hip shard.hip wide.hip capi.hip index.hip stream.hip classify.hip shardstep.hip hostcalls.hip shardset.hip bracken.hip migration.hip taxstats.hip respace.hip export.hip coverage.hip support.hip textparse.hip readform.hip pipe.hip mask.hip compare.hip)
+HIPSRC := $(addprefix $(CSRC)/,kernels.hip fused.hip lane.hip build.hip shard.hip wide.hip capi.hip index.hip stream.hip classify.hip shardstep.hip hostcalls.hip shardset.hip bracken.hip migration.hip taxstats.hip respace.hip merge.hip export.hip coverage.hip support.hip textparse.hip readform.hip pipe.hip mask.hip compare.hip)
 
-$(LIB): $(HIPSRC) $(CSRC)/tablebuild.h $(CSRC)/engine.h $(CSRC)/resolve.h $(CSRC)/layouts.h $(CSRC)/laneplan.h $(CSRC)/hostside.h $(CSRC)/pairmap.h $(CSRC)/chunkscan.h $(CSRC)/wavetools.h $(CSRC)/chunkcut.h $(CSRC)/pieces.h $(CSRC)/textlines.h slacken_amd/host/pack.hpp include/slacken_amd.h
+$(LIB): $(HIPSRC) $(CSRC)/tablebuild.h $(CSRC)/tablewalk.h $(CSRC)/engine.h $(CSRC)/resolve.h $(CSRC)/layouts.h $(CSRC)/laneplan.h $(CSRC)/hostside.h $(CSRC)/pairmap.h $(CSRC)/chunkscan.h $(CSRC)/wavetools.h $(CSRC)/chunkcut.h $(CSRC)/pieces.h $(CSRC)/textlines.h slacken_amd/host/pack.hpp include/slacken_amd.h
 	@mkdir -p slacken_amd/lib
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $(HIPSRC) -ldl
 

@@ -173,7 +173,8 @@ int32_t slk_index_set_taxonomy(slk_index *ix, const int32_t *parents, int32_t T)
  * skipped (the reference filters on Taxonomy.isDefined, KeyValueIndex.scala:118-120 -- the caller applies that filter).
  * Needs the taxonomy (slk_index_set_taxonomy) and an unfinalized index whose slk_table_config.expected_records bounds
  * the number of distinct minimizers.  May be called any number of times, also mixed with slk_index_append of records
- * whose keys do not occur in the sequences; the result does not depend on the order or batching of the calls. */
+ * whose keys do not occur in the sequences; the result does not depend on the order or batching of the calls.  Records whose keys
+ * may occur in the sequences go in through slk_index_merge_records, which merges by LCA as this call does. */
 int32_t slk_index_add_sequences(slk_index *ix, const uint8_t *bases, const uint64_t *offsets, const int32_t *taxa,
                                 uint64_t n_sequences);
 /* The same with the bases already resident on the index's GPU (d_bases: device pointer to offsets[n_sequences] bytes;
@@ -243,6 +244,36 @@ int32_t slk_index_taxon_counts(const slk_index *ix, int32_t *taxa, uint64_t *cou
  * The reference's remark that the result equals a library built at `spaces` from the genomes is not exact: this is
  * respace, not build.  Synchronous, on the source's build stream; not to be called while another thread adds records to the source. */
 int32_t slk_index_respace(const slk_index *src, int32_t spaces, const slk_table_config *cfg /* nullable */, slk_index **out);
+/* Libraries united: records merged into what the table holds, per key by LCA.  A record's taxon is the LCA of the taxa of all
+ * sequences that hold its minimizer (KeyValueIndex.makeRecords, S/slacken/KeyValueIndex.scala:85-93: groupBy(id).agg(TaxonLCA);
+ * LowestCommonAncestor.scala:152-170), and LCA is associative, commutative and idempotent.  So after ANY sequence of
+ * slk_index_merge_records[_device], slk_index_merge_index and slk_index_add_sequences[_device] calls the table holds, per key, the
+ * LCA of every taxon that arrived for it -- in any order of the calls, any chunking, and with keys repeated inside one call.  Under
+ * one taxonomy the merge of build(A) and build(B) is therefore the record set of build(A u B).  slk_index_info.records
+ * counts the distinct keys; duplicate_keys is not touched (merging is the purpose, as in the builder).
+ *   destination   one id column, not finalized, with its taxonomy set (slk_index_set_taxonomy).  A shard (slk_index_set_shard) merges
+ *                 its share and drops the rest.  The table grows when a record finds no cell within reach, as with slk_index_append:
+ *                 no call fails for an expected_records that was too low.
+ *   taxa          taxon NONE is skipped, as slk_index_append skips it.  Every other taxon t is translated as remap[t] where a remap
+ *                 is set (slk_index_set_merge_remap: t >= n or remap[t] == 0 means the destination has no such node; NULL / 0 clears
+ *                 it; the table is copied to the device once, there) and must then be a node the destination's taxonomy defines
+ *                 (1 <= t' < T, ROOT or with a parent) that fits the taxon field (slk_table_config.max_taxon).  Records that fail --
+ *                 a negative taxon among them -- are not stored; the call stores all others and then returns SLK_E_INVALID with
+ *                 "N records name a taxon the destination's taxonomy does not define (smallest: T)", T in the caller's ids.  The
+ *                 index stays usable.
+ *   merge_records keys / taxa in host memory, staged in chunks as slk_index_append stages them; _device: arrays on the index's GPU.
+ *   merge_index   the records of another resident index on the same device: its table is walked where it lies (merge.hip; the walk
+ *                 of slk_index_respace) and no record crosses to the host.  The source may be finalized or not, renumbered to dense
+ *                 ids by slk_index_finalize or not (its taxa travel as the caller's ids), a dynamic library or a shard.  It is only
+ *                 read.
+ *   errors        SLK_E_STATE: destination finalized or without a taxonomy; either index spent.  SLK_E_UNSUPPORTED: several id
+ *                 columns on either side, as slk_index_respace and slk_index_export_range.  SLK_E_INVALID for merge_index: src == dst,
+ *                 different devices, splitters that differ in k, m, spaces, canonical or xor_mask.  n == 0 is SLK_OK.
+ * Synchronous, on the destination's build stream; not to be called while another thread adds records to either index. */
+int32_t slk_index_set_merge_remap(slk_index *ix, const int32_t *remap /* nullable */, int32_t n);
+int32_t slk_index_merge_records(slk_index *ix, const int64_t *keys, const int32_t *taxa, uint64_t n);
+int32_t slk_index_merge_records_device(slk_index *ix, const int64_t *d_keys, const int32_t *d_taxa, uint64_t n);
+int32_t slk_index_merge_index(slk_index *dst, const slk_index *src);
 int32_t slk_index_get_info(const slk_index *ix, slk_index_info *out);
 /* The table's bucket choice as host arithmetic (no GPU): the range reduction of a 64-bit hash onto ANY number of buckets
  * (32 <= nbuckets <= 2^32) -- home = (top q bits of hash) * nbuckets >> q, q = ceil(log2(nbuckets)) -- with the remainder a cell

@@ -78,7 +78,8 @@ HIT_DTYPE = np.dtype([("taxon", "<i4"), ("count", "<i4")])
 # every symbol include/slacken_amd.h declares
 EXPORTS = ["slk_device_count", "slk_last_error", "slk_version", "slk_host_alloc", "slk_host_register", "slk_host_free", "slk_index_create", "slk_index_append",
            "slk_index_append_device", "slk_index_set_shard", "slk_index_set_taxonomy", "slk_index_finalize", "slk_index_get_info",
-           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_export_range", "slk_index_taxon_counts", "slk_index_respace", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
+           "slk_index_lookup", "slk_index_add_sequences", "slk_index_add_sequences_device", "slk_index_export", "slk_index_export_range", "slk_index_taxon_counts", "slk_index_respace",
+           "slk_index_set_merge_remap", "slk_index_merge_records", "slk_index_merge_records_device", "slk_index_merge_index", "slk_index_destroy", "slk_stream_create", "slk_stream_synchronize",
            "slk_stream_hip_stream", "slk_stream_destroy", "slk_spans_batch", "slk_spans_batch_wide", "slk_classify_batch",
            "slk_classify_batch_packed", "slk_pack_bases",
            "slk_classify_batch_device", "slk_classify_hits", "slk_stream_last_stage_ms", "slk_scan_device", "slk_lookup_device",
@@ -182,6 +183,10 @@ def lib():
     L.slk_index_export_range.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int32, i64p, i32p, C.c_uint64, u64p, C.POINTER(C.c_uint64)]
     L.slk_index_taxon_counts.argtypes = [vp, i32p, u64p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.slk_index_respace.argtypes = [vp, C.c_int32, C.POINTER(_TableConfig), C.POINTER(vp)]
+    L.slk_index_set_merge_remap.argtypes = [vp, i32p, C.c_int32]
+    L.slk_index_merge_records.argtypes = [vp, i64p, i32p, C.c_uint64]
+    L.slk_index_merge_records_device.argtypes = [vp, i64p, i32p, C.c_uint64]
+    L.slk_index_merge_index.argtypes = [vp, vp]
     L.slk_index_destroy.argtypes = [vp]
     L.slk_index_destroy.restype = None
     L.slk_stream_create.argtypes = [vp, C.POINTER(vp)]
@@ -461,6 +466,28 @@ class Index:
         new = Index.__new__(Index)
         new.k, new.m, new.spaces, new.W, new.h = self.k, self.m, int(spaces), self.W, h
         return new
+
+    def set_merge_remap(self, remap):
+        """Later merge calls translate every source taxon t as remap[t] (t >= len(remap) or remap[t] == 0: the destination has no
+        such node); None clears it (slk_index_set_merge_remap)."""
+        remap = _np(remap, np.int32) if remap is not None else None
+        _check(lib().slk_index_set_merge_remap(self.h, _ptr(remap), remap.size if remap is not None else 0))
+
+    def merge_records(self, keys, taxa):
+        """Records merged into what the table holds, per key by LCA (slk_index_merge_records): any order, any chunking, keys may
+        repeat and may be in the table already.  Needs the taxonomy and an unfinalized index."""
+        keys, taxa = _np(keys, np.int64), _np(taxa, np.int32)
+        assert keys.size == taxa.size
+        _check(lib().slk_index_merge_records(self.h, _ptr(keys), _ptr(taxa), taxa.size))
+
+    def merge_records_device(self, d_keys_ptr, d_taxa_ptr, n):
+        """merge_records with both arrays resident on the index's GPU (raw device addresses)."""
+        _check(lib().slk_index_merge_records_device(self.h, d_keys_ptr, d_taxa_ptr, n))
+
+    def merge_index(self, src):
+        """The records of another resident Index on the same device merged into this one (slk_index_merge_index): its table is
+        walked on the device; the source is only read."""
+        _check(lib().slk_index_merge_index(self.h, src.h))
 
     def finalize(self):
         _check(lib().slk_index_finalize(self.h))

@@ -444,6 +444,20 @@ void launch_export_range(const TableView &T, uint64_t bucket0, uint64_t bucket1,
                          unsigned long long *counter, hipStream_t s);
 // respace.hip: every record of `src` with its key ANDed with new_smask, inserted or LCA-merged into `dst` (taxa as the cells hold them)
 void launch_respace(const TableView &src, const TableBuild &dst, uint64_t new_smask, const int32_t *parents, int32_t ntax, hipStream_t s);
+// merge.hip: records -- from arrays, or from the cells of `src` -- with their taxa translated into the destination's taxonomy and
+// checked against it, inserted or LCA-merged into `dst`.  A source taxon t (the caller's id) becomes remap[t] where a remap is set
+// (t >= n_remap or remap[t] == 0: no such node); the result must be a defined node of `parents` that fits dst's taxon field.  Records
+// that fail are not stored: bad[0] counts them, the low word of bad[1] keeps the smallest such t as t ^ 0x80000000 (an unsigned
+// minimum in signed order; the caller sets it to all ones).
+struct MergeCheck {
+  const int32_t *remap;     // nullable
+  int32_t n_remap;
+  const int32_t *parents;   // the destination's taxonomy, T ids
+  int32_t T;
+  unsigned long long *bad;
+};
+void launch_merge_records(const TableBuild &dst, const MergeCheck &c, const int64_t *keys, const int32_t *taxa, uint64_t n, hipStream_t s);
+void launch_merge_index(const TableView &src, const TableBuild &dst, const MergeCheck &c, hipStream_t s);
 void launch_table_lookup(const TableView &t, const int64_t *keys, uint64_t n, int32_t *out, hipStream_t s);
 void launch_scan(const ScanParams &P, const uint8_t *bases, const uint64_t *offsets, const uint8_t *mate_bases,
                  const uint64_t *mate_offsets, uint64_t R, uint64_t *span_keys, int32_t *span_meta, int32_t *span_count,

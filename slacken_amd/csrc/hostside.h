@@ -245,6 +245,11 @@ struct slk_index {
   uint32_t grown = 0;              // times the table was moved to a larger one because of that
   float load_target = 0;           // the load factor the table was sized for (given, or chosen by the free memory: slk_index_create)
   bool spent = false;              // the table was lost while it was growing (index.hip: grow_table): only slk_index_destroy takes the index
+  // slk_index_merge_*: the translation of source taxa (slk_index_set_merge_remap; null: none) and what a pass leaves of the records
+  // it refused (engine.h: MergeCheck.bad)
+  DevPtr<int32_t> d_merge_remap;
+  int32_t n_merge_remap = 0;
+  DevPtr<unsigned long long> d_merge_bad;
   Stream build_stream;
   DevBuf stage_keys, stage_taxa;
   Staging staging;    // host -> HBM copies of the build calls

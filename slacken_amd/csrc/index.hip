@@ -1,6 +1,6 @@
 // index.hip -- the library side of the C ABI (include/slacken_amd.h): the record table's shape and sizing, create, append with a
-// table that grows, the taxonomy and its Euler tours, library construction from sequences, export, respace, finalize.
-// Host-side only: the kernels it launches are in kernels.hip, build.hip, wide.hip and respace.hip.  (slk_index_export_range lives
+// table that grows, merge, the taxonomy and its Euler tours, library construction from sequences, export, respace, finalize.
+// Host-side only: the kernels it launches are in kernels.hip, build.hip, wide.hip, respace.hip and merge.hip.  (slk_index_export_range lives
 // beside its kernels in export.hip, as slk_index_taxon_counts does in taxstats.hip.)
 #include "chunkcut.h"
 #include "hostside.h"
@@ -447,6 +447,116 @@ int32_t slk_index_append(slk_index *ix, const int64_t *keys, const int32_t *taxa
     if (rc) return rc;
   }
   return read_build_counters(ix);
+}
+
+// ---- slk_index_merge_*: records united with what the table holds, per key by LCA (merge.hip) ---------------------------------------
+// what every merge entry asks of its destination
+static int32_t check_merge_dst(slk_index *ix) {
+  int32_t rc = set_device(ix);   // (a spent index: SLK_E_STATE)
+  if (rc) return rc;
+  if (ix->W > 1) return fail(SLK_E_UNSUPPORTED, "slk_index_merge_* supports minimizers of up to 32 nt (one id column)");
+  if (ix->finalized) return fail(SLK_E_STATE, "index is finalized");
+  if (!ix->d_parents) return fail(SLK_E_STATE, "slk_index_merge_* needs the destination's taxonomy (LCA merging): call slk_index_set_taxonomy first");
+  if (!ix->d_merge_bad) HIPCHK(hipMalloc((void **)ix->d_merge_bad.put(), 2 * sizeof(unsigned long long)));
+  return SLK_OK;
+}
+
+// the records a call refused, summed over its passes
+struct MergeRefused {
+  unsigned long long n = 0;
+  int32_t smallest = INT32_MAX;
+  int32_t result() const {
+    return n == 0 ? SLK_OK
+                  : fail(SLK_E_INVALID, "%llu records name a taxon the destination's taxonomy does not define (smallest: %d)", n, smallest);
+  }
+};
+
+// One pass of records into the table, which grows if it must.  `launch` queues the pass on the build stream and can be run again:
+// the merge is idempotent, and the counters of the refused records belong to the attempt that completes.
+static int32_t merge_growing(slk_index *ix, MergeRefused *refused, const std::function<void(const MergeCheck &)> &launch) {
+  const MergeCheck check{ix->d_merge_remap, ix->n_merge_remap, ix->d_parents, ix->T, ix->d_merge_bad};
+  int32_t rc = insert_growing(ix, false, [&]() -> int32_t {
+    HIPCHK(hipMemsetAsync(ix->d_merge_bad, 0, sizeof(unsigned long long), ix->build_stream));
+    HIPCHK(hipMemsetAsync(ix->d_merge_bad + 1, 0xff, sizeof(unsigned long long), ix->build_stream));
+    launch(check);
+    HIPCHK(hipGetLastError());
+    return SLK_OK;
+  });
+  if (rc) return rc;
+  unsigned long long bad[2];   // (insert_growing has synchronised the stream)
+  HIPCHK(hipMemcpy(bad, ix->d_merge_bad, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad[0]) {
+    refused->n += bad[0];
+    refused->smallest = std::min(refused->smallest, (int32_t)((uint32_t)bad[1] ^ 0x80000000u));
+  }
+  return SLK_OK;
+}
+
+int32_t slk_index_set_merge_remap(slk_index *ix, const int32_t *remap, int32_t n) {
+  if (!ix || n < 0 || (n > 0 && !remap)) return fail(SLK_E_INVALID, "null argument");
+  int32_t rc = set_device(ix);
+  if (rc) return rc;
+  HIPCHK(hipStreamSynchronize(ix->build_stream));
+  ix->d_merge_remap.reset();
+  ix->n_merge_remap = 0;
+  if (!remap || n == 0) return SLK_OK;
+  HIPCHK(hipMalloc((void **)ix->d_merge_remap.put(), (size_t)n * sizeof(int32_t)));
+  HIPCHK(hipMemcpy(ix->d_merge_remap, remap, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  ix->n_merge_remap = n;
+  return SLK_OK;
+}
+
+int32_t slk_index_merge_records_device(slk_index *ix, const int64_t *d_keys, const int32_t *d_taxa, uint64_t n) {
+  if (!ix || (n && (!d_keys || !d_taxa))) return fail(SLK_E_INVALID, "null argument");
+  int32_t rc = check_merge_dst(ix);
+  if (rc) return rc;
+  MergeRefused refused;
+  rc = merge_growing(ix, &refused, [&](const MergeCheck &c) { launch_merge_records(build_view(ix), c, d_keys, d_taxa, n, ix->build_stream); });
+  return rc ? rc : refused.result();
+}
+
+int32_t slk_index_merge_records(slk_index *ix, const int64_t *keys, const int32_t *taxa, uint64_t n) {
+  if (!ix || (n && (!keys || !taxa))) return fail(SLK_E_INVALID, "null argument");
+  int32_t rc = check_merge_dst(ix);
+  if (rc) return rc;
+  const uint64_t CH = 1ULL << 24;
+  MergeRefused refused;
+  for (uint64_t o = 0; o < n; o += CH) {
+    const uint64_t c = std::min(CH, n - o);
+    HIPCHK(ix->stage_keys.ensure(c * 8));
+    HIPCHK(ix->stage_taxa.ensure(c * 4));
+    rc = copy_in(&ix->staging, ix->build_stream, ix->stage_keys.p, keys + o, c * 8);
+    if (!rc) rc = copy_in(&ix->staging, ix->build_stream, ix->stage_taxa.p, taxa + o, c * 4);
+    if (!rc)
+      rc = merge_growing(ix, &refused, [&](const MergeCheck &mc) {
+        launch_merge_records(build_view(ix), mc, ix->stage_keys.as<int64_t>(), ix->stage_taxa.as<int32_t>(), c, ix->build_stream);
+      });
+    if (rc) {   // (nothing queued may still read the caller's memory)
+      if (hipStreamSynchronize(ix->build_stream) != hipSuccess) (void)hipGetLastError();
+      return rc;
+    }
+  }
+  rc = read_build_counters(ix);
+  return rc ? rc : refused.result();
+}
+
+int32_t slk_index_merge_index(slk_index *dst, const slk_index *src) {
+  if (!dst || !src) return fail(SLK_E_INVALID, "null argument");
+  if (src == dst) return fail(SLK_E_INVALID, "an index cannot be merged into itself");
+  int32_t rc = check_spent(src);
+  if (!rc) rc = check_merge_dst(dst);
+  if (rc) return rc;
+  if (src->W > 1) return fail(SLK_E_UNSUPPORTED, "slk_index_merge_index supports minimizers of up to 32 nt (one id column)");
+  if (src->device != dst->device) return fail(SLK_E_INVALID, "the source is on device %d, the destination on device %d", src->device, dst->device);
+  const slk_params &a = src->params, &b = dst->params;
+  if (a.k != b.k || a.m != b.m || a.spaces != b.spaces || (a.canonical != 0) != (b.canonical != 0) || a.xor_mask != b.xor_mask)
+    return fail(SLK_E_INVALID, "the splitters differ: source k=%d m=%d spaces=%d canonical=%d xor_mask=%016llx, destination k=%d m=%d spaces=%d "
+                "canonical=%d xor_mask=%016llx", a.k, a.m, a.spaces, a.canonical, (unsigned long long)a.xor_mask, b.k, b.m, b.spaces, b.canonical,
+                (unsigned long long)b.xor_mask);
+  HIPCHK(hipStreamSynchronize(src->build_stream));   // the pass runs on the destination's stream: the source's records are all in
+  MergeRefused refused;
+  rc = merge_growing(dst, &refused, [&](const MergeCheck &c) { launch_merge_index(src->view(), build_view(dst), c, dst->build_stream); });
+  return rc ? rc : refused.result();
 }
 
 // The taxonomy as the interval resolvers read it, on the device: resolve.h's build_tour of the forest (nothing for fewer than two ids

@@ -12,6 +12,7 @@
 #include "compare.hpp"
 #include "coverage.hpp"
 #include "mask.hpp"
+#include "merge.hpp"
 #include "migration.hpp"
 #include "repeated_titles.hpp"
 #include "support.hpp"
@@ -963,7 +964,7 @@ static void export_to_writer(const slk_index *ix, LibraryWriter &w, int buckets,
 // ---- build (Slacken.scala:123-171): a library from the genomes of LIBRARY_DIR and the labels of LIBRARY_DIR/seqid2taxid.map ----
 static const char *BUILD_USAGE =
     "usage: [--partitions N] build -i INDEX -t TAXONOMY_DIR -l LIBRARY_DIR [-k 35] [-m 31] [-s|--spaces 7] [--check] [--format parquet|slkrec] "
-    "[--expected-records N] [--mask] [--devices D]";
+    "[--expected-records N] [--mask] [--base LIB] [--devices D]";
 static int g_partitions = 200;          // --partitions, the reference's global option: `buckets` of a library that `build` writes
 constexpr int BUILD_MAX_WINDOW = 28;    // m-mers per window the library builder takes (slk_index_add_sequences)
 
@@ -1037,9 +1038,9 @@ static std::string input_stats_text(const std::string &label_file, const std::ve
 
 static int cmd_build(int argc, char **argv) {
   const char *why_one = "the library's table must fit one GPU";
-  std::string index, taxonomy, library, ordering = "xor";
+  std::string index, taxonomy, library, ordering = "xor", base;
   int k = 35, m = 31, spaces = 7;
-  bool check = false, mask = false;
+  bool check = false, mask = false, k_given = false, m_given = false, spaces_given = false;
   uint64_t expected = 0;
   std::vector<int> devices{0};
   LibraryWriter::Format format = LibraryWriter::AUTO;
@@ -1047,9 +1048,10 @@ static int cmd_build(int argc, char **argv) {
     if (a == "-i" || a == "--index") index = a.next();
     else if (a == "-t" || a == "--taxonomy") taxonomy = a.next();
     else if (a == "-l" || a == "--library") library = a.next();
-    else if (a == "-k") k = std::stoi(a.next());
-    else if (a == "-m" || a == "--minimizer-width") m = std::stoi(a.next());
-    else if (a == "-s" || a == "--spaces") spaces = std::stoi(a.next());
+    else if (a == "-k") { k = std::stoi(a.next()); k_given = true; }
+    else if (a == "-m" || a == "--minimizer-width") { m = std::stoi(a.next()); m_given = true; }
+    else if (a == "-s" || a == "--spaces") { spaces = std::stoi(a.next()); spaces_given = true; }
+    else if (a == "--base") base = a.next();
     else if (a == "--ordering") ordering = a.next();
     else if (a == "--check") check = true;
     else if (a == "--mask") mask = true;
@@ -1060,6 +1062,21 @@ static int cmd_build(int argc, char **argv) {
     else die("unknown option " + a.opt + "\n" + BUILD_USAGE);
   }
   if (index.empty() || taxonomy.empty() || library.empty()) die(BUILD_USAGE);
+  // --base LIB: the splitter is LIB's (its records and the genomes' minimizers must be comparable); -k / -m / -s may repeat it
+  if (!base.empty()) {
+    const IndexParams bp = read_index_params(base);
+    refuse_wide("build --base", bp);
+    auto same = [&](const char *opt, bool given, int &mine, int theirs) {
+      if (given && mine != theirs) die(std::string("build --base: ") + opt + " " + std::to_string(mine) + ", but " + base + " has " + std::to_string(theirs));
+      mine = theirs;
+    };
+    same("-k", k_given, k, bp.k);
+    same("-m", m_given, m, bp.m);
+    same("-s", spaces_given, spaces, bp.spaces);
+    if (bp.xorMask != SLK_DEFAULT_TOGGLE_MASK || !bp.canonical)
+      die("build --base: " + base + " has another XORmask or is not canonical: build writes the default splitter only");
+    if (fs::weakly_canonical(base) == fs::weakly_canonical(index)) die("build --base: INDEX is the base library");
+  }
   // what this engine does not build is refused on the command line alone, before any file is read
   if (ordering != "xor" && ordering != "random")
     die("--ordering " + ordering + " is not supported by this engine (randomXOR only: xor or random)");
@@ -1091,10 +1108,17 @@ static int cmd_build(int argc, char **argv) {
     uint64_t bytes = 0;
     for (auto &f : library_fna_files(library)) bytes += (uint64_t)fs::file_size(f);
     expected = (uint64_t)((double)bytes * std::min(1.0, 2.5 / (w + 1))) + 1024;
+    if (!base.empty()) expected += library_record_count(base, 1);
   }
   DeviceIndex dev;
   dev.devices = devices;
   dev.create(ip, tax, expected, std::max<int32_t>(tax.size() - 1, 1));
+  // --base: the base library's records first, translated into the taxonomy of -t; the genomes' minimizers merge into them by LCA
+  if (!base.empty()) {
+    Timer t("Merge base library " + base);
+    const uint64_t n = merge_library_into(dev, base, tax);
+    std::cerr << "build: --base " << base << ": " << n << " records merged into the table" << std::endl;
+  }
 
   // the walk: batches of whole sequences of about SLK_BUILD_BATCH_BASES bases (a longer sequence is a batch of its own); the next
   // batch is read and parsed while slk_index_add_sequences runs on the last.  Host memory: two batches.
@@ -1180,6 +1204,70 @@ static int cmd_build(int argc, char **argv) {
             << t_write << " s in all" << std::endl;
   // showIndexStats(None) and GenomeLibrary.inputStats (Slacken.scala:166-168)
   std::cout << index_stats_text(tax, device_taxon_counts(dev.ix), m) << input_stats_text(label_file, all_labels, tax);
+  std::cout.flush();
+  return 0;
+}
+
+// ---- merge: libraries united by LCA (merge.hpp).  The reference has no such command. ----
+static const char *MERGE_USAGE =
+    "usage: [--partitions N] merge -i OUT [-t TAXONOMY_DIR] [--format parquet|slkrec] [--expected-records N] [--devices D] LIB LIB [LIB ...]";
+
+static int cmd_merge(int argc, char **argv) {
+  const char *why_one = "the merged library's table must fit one GPU";
+  std::string out, taxonomy;
+  std::vector<std::string> sources;
+  uint64_t expected = 0;
+  std::vector<int> devices{0};
+  LibraryWriter::Format format = LibraryWriter::AUTO;
+  for (Args a(argc, argv); a.take();) {
+    if (a == "-i" || a == "--index") out = a.next();
+    else if (a == "-t" || a == "--taxonomy") taxonomy = a.next();
+    else if (a == "--format") format = LibraryWriter::parse_format(a.next());
+    else if (a == "--expected-records") expected = std::stoull(a.next());
+    else if (a == "--devices") devices = parse_single_device(a.next(), "merge", why_one);
+    else if (a == "--shard-table") refuse_shard_table("merge", why_one, MERGE_USAGE);
+    else if (a.opt.size() > 1 && a.opt[0] == '-') die("unknown option " + a.opt + "\n" + MERGE_USAGE);
+    else sources.push_back(a.opt);
+  }
+  if (out.empty() || sources.empty()) die(MERGE_USAGE);
+  if (g_partitions < 1) die("--partitions must be positive");
+  if (format == LibraryWriter::PARQUET && !parquet_available()) die("--format parquet: this build has no Parquet support");
+  const IndexParams ip = check_merge_sources(out, sources);   // (from the .properties files alone)
+
+  if (taxonomy.empty()) taxonomy = sources[0] + "_taxonomy";
+  const Taxonomy tax = Taxonomy::load(taxonomy);
+  if (expected == 0)
+    for (const std::string &s : sources) expected += library_record_count(s, 1);
+  DeviceIndex dev;
+  dev.devices = devices;
+  dev.create(ip, tax, std::max<uint64_t>(expected, 1024), std::max<int32_t>(tax.size() - 1, 1));
+
+  std::ostringstream per_source;
+  const double t0 = wall_seconds();
+  {
+    Timer t("Merge records");
+    for (const std::string &s : sources) per_source << (per_source.tellp() > 0 ? ", " : "") << s << " " << merge_library_into(dev, s, tax);
+    SLK_CALL(slk_index_finalize(dev.ix));
+  }
+  const double t_merge = wall_seconds() - t0;
+  slk_index_info info;
+  SLK_CALL(slk_index_get_info(dev.ix, &info));
+
+  // written as `build` writes: whatever library is at OUT is replaced only by a finished one
+  LibraryProperties lp = writer_properties(sources[0], ip);
+  lp.buckets = g_partitions;
+  ExportTimes et;
+  const double t_write0 = wall_seconds();
+  {
+    Timer t("Write records to " + out);
+    LibraryWriter wr(out, lp, taxonomy, format);
+    export_to_writer(dev.ix, wr, lp.buckets, &et);
+    wr.finish();
+  }
+  std::cerr << "merge: records read: " << per_source.str() << "; " << info.records << " records out (table grown " << info.grown << " times); merge "
+            << t_merge << " s; export " << et.export_s << " s in " << et.pieces << " pieces beside the writer (waited for it " << et.write_wait_s
+            << " s), " << wall_seconds() - t_write0 << " s in all" << std::endl;
+  std::cout << index_stats_text(tax, device_taxon_counts(dev.ix), ip.m);
   std::cout.flush();
   return 0;
 }
@@ -1616,13 +1704,22 @@ static const char *HELP =
     "  _sS -- .properties, _taxonomy and the records as bucketed Parquet (as .slkrec with --format slkrec or without Arrow) -- followed\n"
     "  by `Stats for <location>` and the two lines `stats` prints\n"
     "  slacken-amd [--partitions N] build -i INDEX -t TAXONOMY_DIR -l LIBRARY_DIR [-k 35] [-m 31] [-s|--spaces 7] [--check]\n"
-    "  [--format parquet|slkrec] [--expected-records N] [--mask] [--devices D] (Slacken.scala:123-171): a library from the genomes of\n"
+    "  [--format parquet|slkrec] [--expected-records N] [--mask] [--base LIB] [--devices D] (Slacken.scala:123-171): a library from the genomes of\n"
     "  LIBRARY_DIR/library/**/*.fna labelled in LIBRARY_DIR/seqid2taxid.map -- minimizers found and merged by LCA on the GPU, the table\n"
     "  exported piece by piece, grouped by Spark's bucket, into --partitions (200) Parquet files (or INDEX.slkrec), with\n"
     "  INDEX.properties and a copy of TAXONOMY_DIR as INDEX_taxonomy -- followed by the two lines `stats` prints and the label file's\n"
     "  statistics.  --check only reports the sequences without a minimizer (host only, nothing is written).  --mask: every batch of\n"
     "  genomes is masked on the GPU as `mask` would with its defaults (window 64, threshold 20, letters replaced by x) before it is\n"
-    "  scanned, so low-complexity sequence yields no minimizers; the files are not touched (--check ignores it)\n"
+    "  scanned, so low-complexity sequence yields no minimizers; the files are not touched (--check ignores it).  --base LIB: the\n"
+    "  records of the library LIB, translated into TAXONOMY_DIR, are merged into the table before the genomes are walked -- genomes\n"
+    "  added to a library whose own genomes are not at hand; -k, -m and -s default to LIB's and are refused when they differ from them\n"
+    "  slacken-amd [--partitions N] merge -i OUT [-t TAXONOMY_DIR] [--format parquet|slkrec] [--expected-records N] [--devices D]\n"
+    "  LIB LIB [LIB ...] (no counterpart in the reference): the libraries united on the GPU -- every record of every LIB into one table,\n"
+    "  the taxa of a shared minimizer merged by LCA, which under one taxonomy is the library `build` makes of all their genomes; no\n"
+    "  genome is read.  The taxonomy is TAXONOMY_DIR or the first LIB's; every LIB's taxa are translated into it (its merged.dmp is\n"
+    "  honoured) and a taxon it lacks ends the run with nothing written.  The libraries must share k, m, minimizerSpaces, XORmask and\n"
+    "  canonical (m <= 32).  Written as `build` writes, into --partitions (200) Parquet files or OUT.slkrec, followed by the two lines\n"
+    "  `stats` prints.  One device\n"
     "  slacken-amd mask [-l LIBRARY_DIR | FILES...] [--window 64] [--threshold 20] [--replace x | --soft] [--host] [--devices D]\n"
     "  (scripts/k2/mask_low_complexity.sh, which runs `k2mask -r x` before a library is built): low-complexity masking of genome files\n"
     "  on the GPU -- symmetric DUST (Morgulis et al. 2006) with a window of 8..64 letters and a threshold of 1..255 tenths, as k2mask\n"
@@ -1669,7 +1766,7 @@ int main(int argc, char **argv) {
     if (i + 1 < argc) g_partitions = atoi(argv[i + 1]);
     i += 2;
   }
-  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|mask|bracken-build|compare-index|compare|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
+  if (i >= argc) die("usage: slacken-amd [--partitions N] classify|classify2|build|merge|mask|bracken-build|compare-index|compare|respace|coverage|support|stats|inspect|copy-records|report|parse|props|records ... (--help for the options)");
   std::string cmd = argv[i++];
   if (cmd == "--help" || cmd == "-h" || cmd == "help") { std::cout << HELP; return 0; }
   if (cmd == "--version") { std::cout << slk_version() << "\n"; return 0; }
@@ -1680,7 +1777,7 @@ int main(int argc, char **argv) {
       {"compareIndex", cmd_compare_index}, {"migration-report", cmd_migration_report}, {"stats", cmd_stats}, {"inspect", cmd_inspect},
       {"stats-report", cmd_stats_report}, {"respace", cmd_respace}, {"copy-records", cmd_copy_records}, {"build", cmd_build},
       {"coverage", cmd_coverage}, {"coverage-report", cmd_coverage_report}, {"support", cmd_support}, {"mask", cmd_mask},
-      {"compare", cmd_compare}};
+      {"compare", cmd_compare}, {"merge", cmd_merge}};
   // (`stats` or `inspect` with nothing behind it is answered below, by the list of what this engine implements, as it was before
   //  they were commands)
   const bool bare = (cmd == "stats" || cmd == "inspect") && i >= argc;
@@ -1690,6 +1787,6 @@ int main(int argc, char **argv) {
   } catch (const std::exception &e) {
     die(e.what());
   }
-  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `mask`, `bracken-build`, `compare-index`, `compare`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
+  die("unknown command line `" + cmd + "` (this engine implements `classify`, `classify2`, `build`, `merge`, `mask`, `bracken-build`, `compare-index`, `compare`, `respace`, `coverage`, `support`, `stats -i INDEX` and "
       "`inspect -i INDEX -o OUTPUT`; the reference's other subcommands are out of scope; --help for the options)");
 }
